@@ -12,6 +12,13 @@ process, started before anything here touches the GPU), relays the child's singl
 torchrun (RANK set) the script is one of the ranks.  At N > 1 the line carries `rccl`: what the live process group and the
 gradient reducer report (ranks, backend, buckets, bytes all-reduced per step).
 
+A plain run (the form above) times the headline inference only: set-up, `--warmup` steps, `--steps` timed steps, the
+result line.  `--full` adds everything else the line has carried (the default `--mode both`: config-4 inference, the two
+training steps, the overlay latency; the `sustained` loop; the CPU baselines and the fidelity against the oracle):
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+`--dump-outputs DIR` writes what the last timed step of the headline returned as float32 .npy files (see dump_outputs); the
+inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
+
 Inference shards by images with no data-path collective (replicas, weak scaling).  Prints ONE JSON
 line on rank 0 (contract in the task statement).  ``roofline`` describes the kernel with the largest
 total time per forward, decided live from event timings on the launch stream: the whole-block kernel
@@ -19,8 +26,8 @@ total time per forward, decided live from event timings on the launch stream: th
 FLOPs = the window-attention GEMM set of SURVEY 8(d), 86.1 GF per image) or the 64->64 3x3
 implicit-GEMM conv (conv2 + decoder_conv1, 2 launches per forward); the other one is reported as
 ``roofline_second`` -- since round 4 the two convs together (0.85 ms) outweigh the block launch (0.78 ms), so the
-window-attention GEMM set, north_star's 0.40 target, is the SECOND entry.  ``sustained`` = the same forward loop
-for >= 2 s after the timed steps with the shader clock it held.  ``cpu_baseline`` = the oracle (CPU restatement of the reference, "port") on a
+window-attention GEMM set, north_star's 0.40 target, is the SECOND entry.  ``sustained`` (--full) = the same forward loop
+for >= 2 s after the timed steps with the shader clock it held.  ``cpu_baseline`` (--full) = the oracle (CPU restatement of the reference, "port") on a
 bounded sample: forward, forward+backward (train.py:117-140), and the PSNR of the build's output
 against the oracle's output for the same image (``psnr_vs_ref_db``, plus ΔPSNR against a synthetic HR).
 """
@@ -218,21 +225,51 @@ def build_info():
         return {"hipcc": None, "note": f"build/resource_usage.json unavailable ({type(e).__name__})"}
 
 
-def main():
+DUMP_SAMPLE = 1 << 20          # elements of the seeded sample over the whole batch
+
+
+def dump_outputs(y, out_dir):
+    """--dump-outputs: the headline output of the last timed step, [B, 3, 1080, 1920], as float32 .npy files in out_dir:
+    output_image0.npy = image 0 whole (24.9 MB), output_sample.npy = DUMP_SAMPLE elements of the whole batch at fixed seeded
+    positions (4.2 MB; the full batch of 8 is 199 MB).  Both depend on the batch size only, not on the run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat = y.detach().reshape(-1)
+    idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    np.save(os.path.join(out_dir, "output_image0.npy"), y[0].detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, "output_sample.npy"), flat[idx.to(flat.device)].float().cpu().numpy())
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the other modes (default --mode both), the sustained loop, "
+                         "the CPU baselines and the fidelity against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the headline output of the last timed step to DIR (dump_outputs)")
     ap.add_argument("--batch", type=int, default=8, help="inference images per GPU per step")
     ap.add_argument("--train-batch", type=int, default=4, help="training images per GPU per step (config 3: 32 / 8 GPUs)")
     ap.add_argument("--rt-batch", type=int, default=2, help="ResidualTransformer 6x training images per GPU per step (config 5: 16 / 8 GPUs)")
     ap.add_argument("--x4-batch", type=int, default=4, help="config 4 (4x 540p -> 2160p inference) images per GPU per step")
-    ap.add_argument("--mode", choices=["infer", "train", "rt", "x4", "both"], default="both",
+    ap.add_argument("--mode", choices=["infer", "train", "rt", "x4", "both"], default=None,
                     help="both = headline inference + 4x 540p inference (config 4) + FastTransformer training step + "
-                         "ResidualTransformer 6x training step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sustained", action="store_true", help="skip the 2-second sustained loop (profiling runs)")
-    args = ap.parse_args()
+                         "ResidualTransformer 6x training step (default: infer, or both with --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the fidelity")
+    ap.add_argument("--no-sustained", action="store_true", help="with --full: skip the 2-second sustained loop (profiling runs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.mode is None:
+        args.mode = "both" if args.full else "infer"
+    if args.dump_outputs and args.mode not in ("infer", "both"):
+        ap.error("--dump-outputs writes the headline inference output: --mode infer or both")
+    return args
+
+
+def main():
+    args = parse_args()
 
     if launcher_decision(args.gpus, os.environ) == "spawn":          # before any GPU call in this process
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -549,12 +586,14 @@ def main():
         dt = time.perf_counter() - t0
     timing_on[0] = False
     assert tuple(y.shape) == (args.batch, 3) + OUT
+    if args.dump_outputs and rank == 0:
+        dump_outputs(y, args.dump_outputs)
 
     # What the hardware sustains: the same loop for >= 2 s, OUTSIDE the headline number (the 20 timed steps are 0.07 s, a stretch in
     # which the chip still holds its boost clock).  The shader clock of the stretch = shader cycles / 100 MHz ticks between two one-wave
     # probes in stream order (MI355X_MICROARCH.md, 'DVFS give-back' item 6).
     sustained = None
-    if rank == 0 and not args.no_sustained:
+    if rank == 0 and args.full and not args.no_sustained:
         from transformerupscaler_amd import ops as _ops
         with torch.no_grad():
             torch.cuda.synchronize()
@@ -656,7 +695,7 @@ def main():
             out["x4"] = x4_result
         if overlay_result is not None:
             out["overlay"] = overlay_result
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"], out["fidelity"] = cpu_baseline(model, dev)
             out["psnr_vs_ref_db"] = out["fidelity"]["psnr_vs_ref_db"]
             if train_result is not None:
@@ -664,7 +703,7 @@ def main():
                                                 "kind": "port", "sample": out["cpu_baseline"]["train_sample"]}
             if rt_result is not None:
                 rt_result["cpu_baseline"] = rt_cpu_baseline()
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = None     # measured on rank 0 at N=1 only (see BENCH at n_gpus=1)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -21,7 +21,7 @@ if [ "$part" = a ]; then
     rm -rf $O/stats_$m
     echo "stats $m done"
   done
-  timeout -k 10 400 python3 bench.py > $O/r04_bench_default.json 2> $O/bench.err
+  timeout -k 10 400 python3 bench.py --full > $O/r04_bench_default.json 2> $O/bench.err
   tail -c 600 $O/r04_bench_default.json
 elif [ "$part" = c ]; then
   # durations: part a's stats (copied to profiles/ between the calls: gpurun_out/ does not travel to the box)

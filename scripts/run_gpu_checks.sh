@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/checks; rm -rf $O; mkdir -p $O
 timeout -k 10 1000 python3 -m pytest tests -m gpu -q -s > $O/tests.log 2>&1 || (grep -n "^FAILED\|^E " $O/tests.log | head -30; echo TESTS FAILED)
 tail -2 $O/tests.log
-timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err
 python3 - <<'PY'
 import json
 d=json.loads(open('gpurun_out/checks/bench.json').read().strip().splitlines()[-1])
