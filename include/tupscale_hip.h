@@ -422,6 +422,23 @@ int tup_resize_u8_rows(const void* src, void* dst, const int* xmin, const int* x
 int tup_resize_u8_cols(const void* src, void* dst_u8, float* dst_f32, const int* ymin, const int* ysize, const int* k,
                        int ksize, int B, int H, int W, int Ho, int swap_rb, void* stream);
 
+/* ---- image-quality metrics (reference inference.py:128-145 skimage SSIM / PSNR, ab_test.py:96-124 MSE; csrc/metrics.hip) ---- */
+
+/* skimage.metrics.structural_similarity(a, b, data_range, channel_axis=-1) with its defaults (7x7 uniform window,
+ * use_sample_covariance, K1 = 0.01, K2 = 0.03, mean over [3:H-3, 3:W-3]) and the sum of squared errors, in one pass, as
+ * per-workgroup partials: partial fp64 [B][3][nparts][2] = {sum of SSIM, sum of squared errors} per image, channel and workgroup,
+ * nparts = ceil((W - 6) / 250) * ceil((H - 6) / 96) (any other value, or H / W < 7, returns hipErrorInvalidValue).
+ * f32: a, b fp32 planar [B][3][H][W]; window moments of data shifted by one constant per workgroup.
+ * u8hwc: a, b uint8 [B][H][W][3]; integer window moments, fp64 formula; squared errors in the input's units. */
+int tup_quality_f32_partial(const float* a, const float* b, double* partial, int B, int H, int W, int nparts,
+                            float data_range, void* stream);
+int tup_quality_u8hwc_partial(const void* a, const void* b, double* partial, int B, int H, int W, int nparts,
+                              float data_range, void* stream);
+/* The partials of either launcher -> out fp64 [6][B] = {mse, psnr = 10 log10(data_range^2 / mse) (+inf when mse == 0), ssim
+ * (mean of the channels), ssim of channels 0, 1, 2}; each image's slots are added in index order in fp64 (no atomics), so an
+ * image's result does not depend on the run or on the other images of the batch. */
+int tup_quality_reduce(const double* partial, double* out, int B, int H, int W, int nparts, float data_range, void* stream);
+
 /* nblk (<= 8) consecutive WindowTransformerBlocks in ONE launch (the loop `for block in self.window_blocks`, model.py:288-289), with
  * the default kernel's geometry (two waves per window, two workgroups per CU): between blocks the residual stream passes through
  * memory as each wave's own stores followed by its own loads (L2), so the launch boundaries and their chip-wide load / store bursts

@@ -11,7 +11,7 @@ from ctypes import c_float, c_int, c_longlong, c_uint, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TUP_LIB_PATH") or os.path.join(_HERE, "libtupscale_hip.so")      # override: A/B of two builds
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 P = c_void_p
 I = c_int
@@ -75,6 +75,10 @@ SIGNATURES = {
     "tup_resize_u8_rows": [P, P, P, P, P, I, I, I, I, I, P],
     "tup_resize_u8_cols": [P, P, P, P, P, P, I, I, I, I, I, I, P],
     "tup_rt_bicubic_sum_fwd": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P],
+    # image-quality metrics (csrc/metrics.hip)
+    "tup_quality_f32_partial": [P, P, P, I, I, I, I, F, P],
+    "tup_quality_u8hwc_partial": [P, P, P, I, I, I, I, F, P],
+    "tup_quality_reduce": [P, P, I, I, I, I, F, P],
     # backward
     "tup_gemm_wgrad": [P, I, I, P, I, I, P, I, I, I, I, P],
     "tup_gemm_wgrad_bias": [P, I, I, P, I, I, P, I, P, I, I, I, P],
