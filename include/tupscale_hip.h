@@ -48,6 +48,16 @@ int tup_conv3x3_c64_fwd(const void* x, const void* wp, const float* bias, const 
                         const void* mask, void* out, int B, int H, int W, int ntiles, int r,
                         int cout_valid, int relu, int out_mode, int in_r, void* stream);
 
+/* Inference decoder (decoder_conv1 64->64 +bias ReLU, then decoder_conv2 64->3 +bias; model.py:228-229,312-313) with the
+ * 64-channel map between them kept in registers: decoder_conv2 is evaluated in scatter form inside decoder_conv1's epilogue,
+ * and a finishing launch adds the terms that cross a wave boundary in a fixed order (csrc/decoder_fused.hip).
+ * x bf16 NHWC [B][H][W][64]; w1 bf16 [1][1][9][64][64] + b1 fp32 [64] (tup_conv3x3_c64_fwd's out_mode 0 packing);
+ * wz bf16 [48][64] (decoder_conv2 with permuted columns, packing.pack_dec2_scatter); b2 fp32 [3];
+ * seamv fp32 [B][3][H][W] and cseam fp32 [B][H][ceil(W/32)][32] workspaces (no initialisation needed);
+ * out fp32 [B][3][H][W].  Requires 12*H*W < 2^31. */
+int tup_decoder_fused_fwd(const void* x, const void* w1, const float* b1, const void* wz, const float* b2,
+                          float* seamv, float* cseam, float* out, int B, int H, int W, void* stream);
+
 /* Inference-only composition of branch A: the LAST Upsampler conv (64->64rr, +bias) + PixelShuffle(r)
  * (utils.py:62-63,74-75,83-84) and up1_conv (64->3, no bias, ReLU; utils.py:32-40), called back to back at
  * model.py:264-265 with no non-linearity between them, evaluated as one 5x5-tap conv with 3rr outputs

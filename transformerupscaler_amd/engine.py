@@ -58,6 +58,10 @@ stream_bf16_tokens = True
 fuse_blocks = True      # inference: fused MLP half (csrc/fused_blocks.hip); False = one kernel per op
 fuse_tail = True        # inference: fused output tail (csrc/tail_fused.hip)
 stream_tail = True     # A/B attribute; last stage x2: the register-streaming tail (csrc/tail_stream.hip) [+ separable Resize]
+# inference (A/B attribute): decoder_conv1 + decoder_conv2 as one conv with decoder_conv2 in its epilogue plus a finishing launch
+# (csrc/decoder_fused.hip); the 64-channel map between them never reaches HBM.  Rides on fuse_tail so that the unfused arm of the
+# fused-vs-unfused tests runs the two-kernel decoder.
+fuse_decoder = True
 
 
 def _block_operands(pk, i, bias_frags):
@@ -158,10 +162,14 @@ def forward(pk: Dict[str, torch.Tensor], bias_frags, x: torch.Tensor, scale: int
         xw = transformer_blocks(pk, xw, bias_frags, cap, bf16_out=cap is None)
     with _stage("unembed"):
         combined = ops.patch_unembed(xw, pk["pu.w"], pk["pu.b"], feat)
-    with _stage("dec1"):
-        dec = ops.conv_c64(combined, pk["dec1.w"], pk["dec1.b"], 1, relu=True)
-    with _stage("dec2"):
-        residual = ops.conv_c64_thin(dec, pk["dec2.w"], pk["dec2.b"], 3, relu=False)
+    if fuse_decoder and fuse_tail and cap is None and "dec2.wz" in pk:
+        with _stage("decoder"):
+            residual = ops.decoder_fused(combined, pk["dec1.w"], pk["dec1.b"], pk["dec2.wz"], pk["dec2.b"])
+    else:
+        with _stage("dec1"):
+            dec = ops.conv_c64(combined, pk["dec1.w"], pk["dec1.b"], 1, relu=True)
+        with _stage("dec2"):
+            residual = ops.conv_c64_thin(dec, pk["dec2.w"], pk["dec2.b"], 3, relu=False)
     if cap is not None:
         cap["combined"] = combined; cap["dec"] = dec; cap["residual"] = residual
     t = residual

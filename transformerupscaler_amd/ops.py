@@ -121,6 +121,20 @@ def conv_c64_thin(x, wp, bias, cout, relu=False, out=None):
     return out
 
 
+def decoder_fused(x, w1, b1, wz, b2):
+    """decoder_conv1 (64->64, +bias, ReLU) + decoder_conv2 (64->3, +bias) without the 64-channel map in HBM:
+    NHWC bf16 [B][H][W][64] -> fp32 planar [B][3][H][W] (csrc/decoder_fused.hip)."""
+    B, H, W, C = x.shape
+    assert C == 64
+    out = torch.empty((B, 3, H, W), dtype=F32, device=x.device)
+    seamv = torch.empty((B, 3, H, W), dtype=F32, device=x.device)
+    cseam = torch.empty((B, H, (W + 31) // 32, 32), dtype=F32, device=x.device)
+    _lib.call("tup_decoder_fused_fwd", _chk(x, BF16, None, "x"), _chk(w1, BF16, (1, 1, 9, 64, 64), "w1"), _chk(b1, F32, (1, 64), "b1"),
+              _chk(wz, BF16, (48, 64), "wz"), _chk(b2, F32, (3,), "b2"), seamv.data_ptr(), cseam.data_ptr(), out.data_ptr(),
+              B, H, W, _stream())
+    return out
+
+
 def branch_a_composed(x, wp, bias, wv, bv, r, relu=True):
     """Composed (last up-conv + PixelShuffle + up1_conv [+ReLU]) 5x5 conv: NHWC bf16 [B][H][W][64] -> fp32 [B][3][H*r][W*r]."""
     B, H, W, C = x.shape

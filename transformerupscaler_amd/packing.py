@@ -60,6 +60,18 @@ def pack_conv_c64_thin(weight: torch.Tensor):
     return w.view(1, 1, 9, 16, 64).contiguous().to(torch.bfloat16)
 
 
+def pack_dec2_scatter(weight: torch.Tensor):
+    """decoder_conv2 Conv2d(64, 3, 3) in scatter form (csrc/decoder_fused.hip) -> bf16 [48][64]: row m = 16*dy + 4*c + dx
+    (c, dx < 3; the rest zero) holds W[c, :, dy, dx] with its columns in the K order of decoder_conv1's epilogue registers:
+    column kk = 32*s + 8*g + j <- input channel 16*g + 8*s + j."""
+    assert tuple(weight.shape) == (3, 64, 3, 3)
+    kk = torch.arange(64)
+    ch = 16 * ((kk % 32) // 8) + 8 * (kk // 32) + kk % 8
+    w = torch.zeros(3, 4, 4, 64, dtype=weight.dtype, device=weight.device)                  # [dy][c][dx][kk]
+    w[:, :3, :3, :] = weight[:, ch.to(weight.device), :, :].permute(2, 0, 3, 1)             # [c][kk][dy][dx] -> [dy][c][dx][kk]
+    return w.reshape(48, 64).contiguous().to(torch.bfloat16)
+
+
 def pack_conv1(weight: torch.Tensor):
     """Conv2d(3, 64, 3) -> bf16 [64][32], k = tap*3 + cin, rows permuted."""
     assert tuple(weight.shape) == (64, 3, 3, 3)
@@ -436,6 +448,7 @@ def pack_state_dict(sd: Dict[str, torch.Tensor], scale: int, backward: bool = Fa
     pk["dec1.w"], pk["dec1.b"] = pack_conv_c64(sd["decoder_conv1.weight"].detach(), sd["decoder_conv1.bias"].detach(), 1)
     pk["dec2.w"] = pack_conv_c64_thin(sd["decoder_conv2.weight"].detach()); pk["dec2.b"] = f32(sd["decoder_conv2.bias"])
     if not backward:
+        pk["dec2.wz"] = pack_dec2_scatter(sd["decoder_conv2.weight"].detach())      # the fused inference decoder
         return pk
     # ---- extra packings the backward needs ----
     t = lambda k: sd[k].detach()
