@@ -58,6 +58,16 @@ int tup_conv3x3_c64_fwd(const void* x, const void* wp, const float* bias, const 
 int tup_decoder_fused_fwd(const void* x, const void* w1, const float* b1, const void* wz, const float* b2,
                           float* seamv, float* cseam, float* out, int B, int H, int W, void* stream);
 
+/* Inference conv1 + conv2 (model.py:202-204,251-252: Conv2d(3,64)+ReLU, Conv2d(64,64)+ReLU) without the 64-channel map between
+ * them in HBM (csrc/conv12_fused.hip).  tup_conv1_compact_fwd: x fp32 [B][3][H][W] -> xc bf16 [B][Hp][Wp][4], Hp = 8 ceil(H/8) + 4,
+ * Wp = 32 ceil(W/32) + 4 (image at (+2, +2), zero border, channel 3 = 0).  tup_conv12_fused_fwd: xc -> out bf16 NHWC [B][H][W][64]
+ * = ReLU(conv2(ReLU(conv1(x)))), conv1 recomputed per conv2 tile; w1 bf16 [64][32] + b1 fp32 [64] (tup_conv3x3_c3_fwd's packing),
+ * w2 bf16 [1][1][9][64][64] + b2 fp32 [1][64] (tup_conv3x3_c64_fwd's out_mode 0 packing).  Bit-identical to the two kernels.
+ * Requires 8*Hp*Wp < 2^31. */
+int tup_conv1_compact_fwd(const float* x, void* xc, int B, int H, int W, void* stream);
+int tup_conv12_fused_fwd(const void* xc, const void* w1, const float* b1, const void* w2, const float* b2, void* out,
+                         int B, int H, int W, void* stream);
+
 /* Inference-only composition of branch A: the LAST Upsampler conv (64->64rr, +bias) + PixelShuffle(r)
  * (utils.py:62-63,74-75,83-84) and up1_conv (64->3, no bias, ReLU; utils.py:32-40), called back to back at
  * model.py:264-265 with no non-linearity between them, evaluated as one 5x5-tap conv with 3rr outputs

@@ -26,6 +26,9 @@ KEYS = {
         "branch_a_5x5": ("bra_rows_persistent_kernel", "conv3x3_c64.hip", 8 * F64 + 8 * 3 * 1440 * 2560 * 4),
         "conv1": ("conv3x3_c3_persistent_kernel", "conv_thin.hip", 8 * 3 * 720 * 1280 * 4 + 8 * F64),
         "decoder_conv2": ("conv3_thin_rows_kernel", "conv3x3_c64.hip", 8 * F64 + 8 * 3 * 720 * 1280 * 4),
+        # engine.fuse_conv12: the compact padded input (8 B per pixel of the 724 x 1284 padded image), then conv2 with conv1 recomputed
+        "conv1_compact": ("conv1_compact_kernel", "conv12_fused.hip", 8 * 3 * 720 * 1280 * 4 + 8 * 724 * 1284 * 8),
+        "conv12_fused": ("conv12_fused_kernel", "conv12_fused.hip", 8 * 724 * 1284 * 8 + 8 * F64),
     },
     "x4": {      # B = 4, 4x 540p -> 2160p: the tail's last stage runs 1080p -> 2160p without a Resize
         "tail": ("tail_stream_r2_kernel<false>", "tail_stream.hip", 4 * 3 * (1080 * 1920 + 2 * 2160 * 3840) * 4),

@@ -25,6 +25,8 @@ SIGNATURES = {
     "tup_conv3x3_c64_fwd": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],
     "tup_conv5x5_c64_planar_fwd": [P, P, P, P, P, P, I, I, I, I, I, P],
     "tup_decoder_fused_fwd": [P, P, P, P, P, P, P, P, I, I, I, P],
+    "tup_conv1_compact_fwd": [P, P, I, I, I, P],
+    "tup_conv12_fused_fwd": [P, P, P, P, P, P, I, I, I, P],
     "tup_conv3x3_planar_fwd": [P, P, P, P, P, I, I, I, I, I, P],
     "tup_resize_aa_fwd": [P, P, P, P, P, I, P, P, P, I, I, I, I, I, I, I, P],
     "tup_tail_fused_fwd": [P, P, P, P, P, P, P, P, P, P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, P],

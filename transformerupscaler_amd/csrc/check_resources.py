@@ -25,6 +25,7 @@ GUARDED = [
     ("conv3x3_c64.hip", ["conv_c64_persistent_kernel", "bra_rows_persistent_kernel", "conv3_thin_rows_kernel"]),
     ("conv_thin.hip", ["conv3x3_c3_persistent_kernel"]),
     ("decoder_fused.hip", ["decoder_fused_kernel"]),
+    ("conv12_fused.hip", ["conv12_fused_kernel"]),
     ("gemm_tokens.hip", ["gemm_panel2_kernel", "patch_embed_kernel"]),
     # no counted hand-off here: guarded because the unrolled halo-row loops sit at 240 / 202 registers and a build that hoists their
     # read addresses out of the tile loop spills (seen twice while they were written)

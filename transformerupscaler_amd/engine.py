@@ -62,6 +62,9 @@ stream_tail = True     # A/B attribute; last stage x2: the register-streaming ta
 # (csrc/decoder_fused.hip); the 64-channel map between them never reaches HBM.  Rides on fuse_tail so that the unfused arm of the
 # fused-vs-unfused tests runs the two-kernel decoder.
 fuse_decoder = True
+# inference (A/B attribute): conv1 recomputed per conv2 tile inside conv2's idle wave group from a compact bf16 copy of the input
+# (csrc/conv12_fused.hip); the 64-channel conv1 map never reaches HBM
+fuse_conv12 = True
 
 
 def _block_operands(pk, i, bias_frags):
@@ -129,11 +132,18 @@ def forward(pk: Dict[str, torch.Tensor], bias_frags, x: torch.Tensor, scale: int
     # (measured and dropped in round 4: conv1 -> conv2 and decoder_conv1 -> decoder_conv2 one or two images at a time, so that the
     # 118 MB-per-image map between them would come back from the 256 MB memory-side cache: 0.693 -> 0.74-0.80 ms and 0.675 ->
     # 0.70-0.72 ms per forward -- the consumers are not faster on cache-resident input, and eight small launches cost their tails)
-    with _stage("conv1"):
-        feat1 = ops.conv1(x, pk["conv1.w"], pk["conv1.b"], relu=True)
-    with _stage("conv2"):
-        feat = ops.conv_c64(feat1, pk["conv2.w"], pk["conv2.b"], 1, relu=True)
-    del feat1
+    if fuse_conv12 and cap is None:
+        with _stage("conv1"):
+            xc = ops.conv1_compact(x)
+        with _stage("conv2"):
+            feat = ops.conv12_fused(xc, H, W, pk["conv1.w"], pk["conv1.b"], pk["conv2.w"], pk["conv2.b"])
+        del xc
+    else:
+        with _stage("conv1"):
+            feat1 = ops.conv1(x, pk["conv1.w"], pk["conv1.b"], relu=True)
+        with _stage("conv2"):
+            feat = ops.conv_c64(feat1, pk["conv2.w"], pk["conv2.b"], 1, relu=True)
+        del feat1
     # branch A: Upsampler + up1_conv (conv, no bias, ReLU)
     stages = upsampler_layout(scale)
     up = feat

@@ -91,6 +91,27 @@ def conv1(x, wp, bias, relu=True, in_mask=None, out_mask=None):
     return out
 
 
+def conv1_compact(x):
+    """planar fp32 [B][3][H][W] -> the fused conv1 -> conv2's input: bf16 [B][8 ceil(H/8) + 4][32 ceil(W/32) + 4][4], the image at
+    (+2, +2) inside a zero border, channel 3 = 0 (csrc/conv12_fused.hip)."""
+    B, C, H, W = x.shape
+    assert C == 3
+    xc = torch.empty((B, (H + 7) // 8 * 8 + 4, (W + 31) // 32 * 32 + 4, 4), dtype=BF16, device=x.device)
+    _lib.call("tup_conv1_compact_fwd", _chk(x, F32, None, "x"), xc.data_ptr(), B, H, W, _stream())
+    return xc
+
+
+def conv12_fused(xc, H, W, w1, b1, w2, b2):
+    """ReLU(conv2(ReLU(conv1(x)))) from conv1_compact(x) without the conv1 map in HBM: NHWC bf16 [B][H][W][64], bit-identical to
+    conv_c64(conv1(x, w1, b1), w2, b2, 1, relu=True) (csrc/conv12_fused.hip; inference only)."""
+    B = xc.shape[0]
+    _chk(xc, BF16, (B, (H + 7) // 8 * 8 + 4, (W + 31) // 32 * 32 + 4, 4), "xc")
+    out = torch.empty((B, H, W, 64), dtype=BF16, device=xc.device)
+    _lib.call("tup_conv12_fused_fwd", xc.data_ptr(), _chk(w1, BF16, (64, 32), "w1"), _chk(b1, F32, (64,), "b1"),
+              _chk(w2, BF16, (1, 1, 9, 64, 64), "w2"), _chk(b2, F32, (1, 64), "b2"), out.data_ptr(), B, H, W, _stream())
+    return out
+
+
 def conv_c64(x, wp, bias, r=1, relu=False, add=None, mask=None, in_r=1, out=None):
     """NHWC bf16 conv 64*in_r^2 -> 64*r*r with fused PixelShuffle(r); returns [B][H*r][W*r][64] bf16.
     x is [B][H*in_r][W*in_r][64] (in_r > 1: channels read through PixelShuffle^-1)."""
