@@ -287,6 +287,25 @@ int tup_conv3x3_c3_wgrad(const float* x, const void* gmap, float* dw, float* dbi
 int tup_conv3x3_planar_wgrad(const float* x, const float* gpl, float* dw, float* dbias,
                              int B, int H, int W, int r, void* stream);
 
+/* Deterministic forms.  The forms above add per-workgroup partial sums with float atomics, so their result bits depend on the
+ * order the adds arrive in.  The *_det forms take the same arguments plus `slab`, an fp32 workspace of tup_conv_wgrad_slab(...)
+ * floats provided by the caller (contents ignored, no allocation inside): every persistent workgroup stores its partial sums into
+ * its own slice, and tup_slab_reduce adds the slices onto the outputs in a fixed order.  The grids
+ * depend on the shapes only, so the result is bitwise reproducible for a given build and device model.
+ *   tup_conv_wgrad_slab: kind 0 = c64 (and c64 s2d; H, W of gmap's plane), 1 = thin, 2 = planar with factor r.  Host only: returns
+ *   a float count (0 for invalid arguments), not a hipError_t.
+ *   tup_slab_reduce: out[i] (accumulate ? += : =) sum over s < nslab of slab[s * ld + i], i < n: group y (0..3) adds slices
+ *   y, y + 4, ... left to right, then ((group 0 + group 2) + (group 1 + group 3)) is written or added to out[i]. */
+long long tup_conv_wgrad_slab(int kind, int B, int H, int W, int r);
+int tup_slab_reduce(const float* slab, long long ld, int nslab, float* out, long long n, int accumulate, void* stream);
+int tup_conv3x3_c64_wgrad_det(const void* x, const void* gmap, float* dwp, float* dbias,
+                              int B, int H, int W, int gr, int sp, float* slab, void* stream);
+int tup_conv3x3_c64_wgrad_s2d_det(const void* x, const void* gmap, float* dwp, float* dbias,
+                                  int B, int H, int W, int xr, int xsp, float* slab, void* stream);
+int tup_conv3x3_thin_wgrad_det(const void* x, const float* gpl, float* dwp, float* dbias, int B, int H, int W, float* slab, void* stream);
+int tup_conv3x3_planar_wgrad_det(const float* x, const float* gpl, float* dw, float* dbias,
+                                 int B, int H, int W, int r, float* slab, void* stream);
+
 /* Input gradient of Conv2d(3,3rr,k3)+PixelShuffle(r) on planar fp32 (final_upscale): w fp32 [3rr][3][3][3]. */
 int tup_conv3x3_planar_dgrad(const float* gpl, const float* w, float* gx, int B, int H, int W, int r, void* stream);
 

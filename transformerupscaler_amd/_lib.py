@@ -105,6 +105,13 @@ SIGNATURES = {
     "tup_resize_aa_bwd": [P, P, P, P, P, I, P, P, I, P, P, P, P, I, I, I, I, I, P, P],
     "tup_mask_bwd": [P, P, P, P, c_longlong, P, P],
     "tup_feat_grad_combine": [P, P, P, P, P, I, I, I, P],
+    # deterministic training mode (csrc/deterministic.hip, csrc/conv_bwd.hip)
+    "tup_conv_wgrad_slab": [I, I, I, I, I],
+    "tup_slab_reduce": [P, c_longlong, I, P, c_longlong, I, P],
+    "tup_conv3x3_c64_wgrad_det": [P, P, P, P, I, I, I, I, I, P, P],
+    "tup_conv3x3_c64_wgrad_s2d_det": [P, P, P, P, I, I, I, I, I, P, P],
+    "tup_conv3x3_thin_wgrad_det": [P, P, P, P, I, I, I, P, P],
+    "tup_conv3x3_planar_wgrad_det": [P, P, P, P, I, I, I, I, P, P],
 }
 
 
@@ -115,7 +122,7 @@ class TupscaleLibraryError(RuntimeError):
 _lib = None
 
 
-COUNT_RETURNING = {"tup_window_attn_bwd_scratch"}      # return an element count, not a hipError_t
+COUNT_RETURNING = {"tup_window_attn_bwd_scratch", "tup_conv_wgrad_slab"}      # return an element count, not a hipError_t
 
 
 def load():

@@ -29,7 +29,7 @@ GUARDED = [
     ("gemm_tokens.hip", ["gemm_panel2_kernel", "patch_embed_kernel"]),
     # no counted hand-off here: guarded because the unrolled halo-row loops sit at 240 / 202 registers and a build that hoists their
     # read addresses out of the tile loop spills (seen twice while they were written)
-    ("conv_bwd.hip", ["conv3x3_wgrad_c64_kernel", "conv3x3_wgrad_thin_kernel"]),
+    ("conv_bwd.hip", ["conv3x3_wgrad_c64_kernel", "conv3x3_wgrad_thin_kernel", "conv3x3_wgrad_c64_det_kernel", "conv3x3_wgrad_thin_det_kernel"]),
     ("branch_a_train.hip", ["bra_wgrad_kernel"]),
     # counted vmcnt between its LDS-DMA stages, asm fragment reads with counted lgkmcnt
     ("gemm_wgrad.hip", ["gemm_wgrad_wide_kernel"]),

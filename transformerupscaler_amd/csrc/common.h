@@ -302,3 +302,7 @@ inline void drop_pair_params(float p, uint32_t& thresh_hi, float& inv_keep) {
 #endif
 
 #define TUP_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
+
+// Ordered slab reduce of the deterministic weight-gradient forms (deterministic.hip): out[i] (accumulate ? += : =) sum over
+// s < nslab of slab[s * ld + i], in a fixed order that depends on nslab only.
+extern "C" int tup_slab_reduce(const float* slab, long long ld, int nslab, float* out, long long n, int accumulate, void* stream);

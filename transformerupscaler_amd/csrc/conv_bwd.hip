@@ -35,7 +35,10 @@ TUP_DEVICE void stage_x_halo(char* lds, const bf16_t* xb, int H, int W, int ty0,
 // whole 64 x 576 partial result lives in registers (144 per lane) and is flushed once.
 // G may be the sub-pixel plane `sp` of a pixel-shuffled gradient [B][H*gr][W*gr][64].
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(512) void conv3x3_wgrad_c64_kernel(
+// DET: the deterministic form -- workgroup blockIdx.x stores its partial sums into slab slice blockIdx.x (dwp = the slab: [grid][64 * 9 * 64]
+// of weights, then [grid][64] of bias sums when dbias != NULL) instead of adding them; tup_slab_reduce adds the slices in order
+template <bool DET>
+TUP_DEVICE void conv3x3_wgrad_c64_body(
     const bf16_t* __restrict__ x, const bf16_t* __restrict__ gmap, float* __restrict__ dwp, float* __restrict__ dbias,
     int B, int H, int W, int gr, int sp, int tilesX, int tilesY, int xr, int xsp)
 {
@@ -211,6 +214,26 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_c64_kernel(
         __syncthreads();
     }
     // flush: D[row = co 4g+e][col = ci l16]; packed layout [co][tap][ci] keeps 16 lanes on one 64-B segment
+    if constexpr (DET) {
+        float* o = dwp + (size_t)blockIdx.x * (64 * 9 * 64);
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[((size_t)(16 * (2 * coh + c) + 4 * g + e) * 9 + tap) * 64 + 16 * cit + l16] = acc[tap][c][e];
+        if (dbias && cit == 0) {
+            float* ob = dwp + (size_t)gridDim.x * (64 * 9 * 64) + (size_t)blockIdx.x * 64;
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                float v = bsum[c];
+                v += __shfl_xor(v, 16);
+                v += __shfl_xor(v, 32);
+                if (g == 0) ob[16 * (2 * coh + c) + l16] = v;
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
@@ -233,6 +256,19 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_c64_kernel(
     }
 }
 
+__global__ __launch_bounds__(512) void conv3x3_wgrad_c64_kernel(
+    const bf16_t* __restrict__ x, const bf16_t* __restrict__ gmap, float* __restrict__ dwp, float* __restrict__ dbias,
+    int B, int H, int W, int gr, int sp, int tilesX, int tilesY, int xr, int xsp)
+{
+    conv3x3_wgrad_c64_body<false>(x, gmap, dwp, dbias, B, H, W, gr, sp, tilesX, tilesY, xr, xsp);
+}
+__global__ __launch_bounds__(512) void conv3x3_wgrad_c64_det_kernel(
+    const bf16_t* __restrict__ x, const bf16_t* __restrict__ gmap, float* __restrict__ dwp, float* __restrict__ dbias,
+    int B, int H, int W, int gr, int sp, int tilesX, int tilesY, int xr, int xsp)
+{
+    conv3x3_wgrad_c64_body<true>(x, gmap, dwp, dbias, B, H, W, gr, sp, tilesX, tilesY, xr, xsp);
+}
+
 // ------------------------------------------------------------------------------------------------
 // thin convs (cout = 3: up1_conv, decoder_conv2): G planar fp32 [B][3][H][W], X NHWC bf16.
 // dwp[co][tap][ci] += ..., dbias[co] += sum G.  The 64-cout kernel's scheme with the 3 real couts padded to one 16-row tile:
@@ -241,7 +277,10 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_c64_kernel(
 // the four waves split the taps on the 16x16x16 form and rebuilt every swizzled address from the pixel index: 740 vector
 // instructions per tile and wave for 144 half-rate MFMAs, 2.0 TB/s.)
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256, 2) void conv3x3_wgrad_thin_kernel(
+// DET: workgroup blockIdx.x stores into slab slice blockIdx.x (dwp = the slab: [grid][3 * 9 * 64] of weights, then [grid][4 waves][3]
+// of bias sums when dbias != NULL)
+template <bool DET>
+TUP_DEVICE void conv3x3_wgrad_thin_body(
     const bf16_t* __restrict__ x, const float* __restrict__ gpl, float* __restrict__ dwp, float* __restrict__ dbias,
     int B, int H, int W, int tilesX, int tilesY)
 {
@@ -362,6 +401,26 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_thin_kernel(
         __syncthreads();
     }
     // D[row = co 4g+e][col = ci l16]: only rows 0..2 (g == 0, e < 3) are real
+    if constexpr (DET) {
+        if (g == 0) {
+            float* o = dwp + (size_t)blockIdx.x * (3 * 9 * 64);
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+                for (int e = 0; e < 3; ++e) o[((size_t)e * 9 + tap) * 64 + 16 * cit + l16] = acc[tap][e];
+        }
+        if (dbias) {
+            float* ob = dwp + (size_t)gridDim.x * (3 * 9 * 64) + ((size_t)blockIdx.x * 4 + cit) * 3;
+#pragma unroll
+            for (int co = 0; co < 3; ++co) {
+                float v = bsum[co];
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+                if (lane == 0) ob[co] = v;
+            }
+        }
+        return;
+    }
     if (g == 0) {
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap)
@@ -377,6 +436,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_thin_kernel(
             if (lane == 0) atomicAdd(dbias + co, v);
         }
     }
+}
+
+__global__ __launch_bounds__(256, 2) void conv3x3_wgrad_thin_kernel(
+    const bf16_t* __restrict__ x, const float* __restrict__ gpl, float* __restrict__ dwp, float* __restrict__ dbias,
+    int B, int H, int W, int tilesX, int tilesY)
+{
+    conv3x3_wgrad_thin_body<false>(x, gpl, dwp, dbias, B, H, W, tilesX, tilesY);
+}
+__global__ __launch_bounds__(256, 2) void conv3x3_wgrad_thin_det_kernel(
+    const bf16_t* __restrict__ x, const float* __restrict__ gpl, float* __restrict__ dwp, float* __restrict__ dbias,
+    int B, int H, int W, int tilesX, int tilesY)
+{
+    conv3x3_wgrad_thin_body<true>(x, gpl, dwp, dbias, B, H, W, tilesX, tilesY);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -456,8 +528,11 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_c3_kernel(
 // RT / THT > 0: compile-time r and rows per tile -> the tile's operands are fetched into registers one tile AHEAD (all loads of a
 // tile in flight under the previous tile's arithmetic); RT = 0: generic r, staged in place (a load -> LDS-store loop with
 // run-time bounds is not unrolled and pays a global round trip per iteration: 20 us per 1,024-pixel tile, the whole 0.36 ms).
-template <int RT, int THT>
-__global__ __launch_bounds__(256, 2) void conv3x3_wgrad_planar_kernel(
+// DET: no LDS or global atomics.  The per-thread sums are combined in a fixed order through the (then free) tile area of LDS and
+// workgroup blockIdx.x stores its result into slab slice blockIdx.x (dw = the slab: [grid][cout * 27] of weights, then [grid][cout] of
+// bias sums when dbias != NULL).
+template <int RT, int THT, bool DET>
+TUP_DEVICE void conv3x3_wgrad_planar_body(
     const float* __restrict__ x, const float* __restrict__ gpl, float* __restrict__ dw, float* __restrict__ dbias,
     int B, int H, int W, int r_, int th_, int tilesX, int tilesY)
 {
@@ -581,6 +656,59 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_planar_kernel(
             }
         __syncthreads();
     }
+    if constexpr (DET) {
+        // the tile area (x_lds, g_lds: at least 3,468 floats for every r) is free after the loop's last barrier
+        float* stage = fl;
+        if (rr == 1 || rr == 4) {
+            // the butterfly of the atomic form, then the four waves' sums in wave order
+            const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+#pragma unroll
+                for (int k = 0; k < 28; ++k) {
+                    float v = (k < 27) ? acc[c][k < 27 ? k : 0] : bsum[c];
+                    if constexpr (RT > 0) {
+#pragma unroll
+                        for (int o = 32; o >= RT * RT; o >>= 1) v += __shfl_xor(v, o);
+                    } else {
+                        for (int o = 32; o >= rr; o >>= 1) v += __shfl_xor(v, o);
+                    }
+                    if (lane < rr) stage[wave * 336 + ph * 84 + c * 28 + k] = v;
+                }
+            }
+            __syncthreads();
+            for (int o = tid; o < rr * 84; o += 256) red[o] = ((stage[o] + stage[336 + o]) + stage[672 + o]) + stage[1008 + o];
+        } else {
+            // 7 passes of 12 values: every thread stages its 12, then (phase, value) pairs sum their nslot slots in slot order
+#pragma unroll
+            for (int q = 0; q < 7; ++q) {
+#pragma unroll
+                for (int kk = 0; kk < 12; ++kk) {
+                    const int idx = q * 12 + kk, c = idx / 28, k = idx % 28;
+                    stage[kk * 256 + tid] = worker ? (k < 27 ? acc[c][k < 27 ? k : 0] : bsum[c]) : 0.f;
+                }
+                __syncthreads();
+                for (int o = tid; o < rr * 12; o += 256) {
+                    const int p2 = o / 12, kk = o - p2 * 12;
+                    float v = 0.f;
+                    for (int sl = 0; sl < nslot; ++sl) v += stage[kk * 256 + sl * rr + p2];
+                    red[p2 * 84 + q * 12 + kk] = v;
+                }
+                __syncthreads();
+            }
+        }
+        __syncthreads();
+        float* odw = dw + (size_t)blockIdx.x * cout * 27;
+        float* ob = dw + (size_t)gridDim.x * cout * 27 + (size_t)blockIdx.x * cout;
+        for (int o = tid; o < rr * 84; o += 256) {
+            const int p2 = o / 84, rem = o - p2 * 84;
+            const int c = rem / 28, k = rem - c * 28;
+            const int co = c * rr + p2;
+            if (k < 27) odw[co * 27 + k] = red[o];
+            else if (dbias) ob[co] = red[o];
+        }
+        return;
+    }
     if (rr == 1 || rr == 4) {
         // lanes of one phase are rr apart: butterfly over the wave first, then ONE LDS atomic per wave and value (256 threads
         // adding to the same 84 LDS words serialised 64-fold per wave: this tail was most of the kernel's 0.39 ms)
@@ -615,6 +743,21 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_planar_kernel(
         if (k < 27) atomicAdd(dw + co * 27 + k, red[o]);
         else if (dbias) atomicAdd(dbias + co, red[o]);
     }
+}
+
+template <int RT, int THT>
+__global__ __launch_bounds__(256, 2) void conv3x3_wgrad_planar_kernel(
+    const float* __restrict__ x, const float* __restrict__ gpl, float* __restrict__ dw, float* __restrict__ dbias,
+    int B, int H, int W, int r_, int th_, int tilesX, int tilesY)
+{
+    conv3x3_wgrad_planar_body<RT, THT, false>(x, gpl, dw, dbias, B, H, W, r_, th_, tilesX, tilesY);
+}
+template <int RT, int THT>
+__global__ __launch_bounds__(256, 2) void conv3x3_wgrad_planar_det_kernel(
+    const float* __restrict__ x, const float* __restrict__ gpl, float* __restrict__ dw, float* __restrict__ dbias,
+    int B, int H, int W, int r_, int th_, int tilesX, int tilesY)
+{
+    conv3x3_wgrad_planar_body<RT, THT, true>(x, gpl, dw, dbias, B, H, W, r_, th_, tilesX, tilesY);
 }
 
 // dgrad of a planar up-conv: gx[ci][y][x] = sum_{co,ky,kx} W[co][ci][ky][kx] * G_pre[co][y+1-ky][x+1-kx]
@@ -921,6 +1064,7 @@ int persistent_grid(long long ntiles, int per_cu) {
 
 }  // namespace
 
+template <bool DET = false>
 static int conv_c64_wgrad_launch(const void* x, const void* gmap, float* dwp, float* dbias,
                                  int B, int H, int W, int gr, int sp, int xr, int xsp, void* stream)
 {
@@ -930,6 +1074,16 @@ static int conv_c64_wgrad_launch(const void* x, const void* gmap, float* dwp, fl
     const long long nt = (long long)tilesX * tilesY * B;
     if (nt > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     const size_t lds = X_TILE_BYTES + 256 * 128;
+    if constexpr (DET) {
+        // dwp = the slab; the grid of the product build (one workgroup per CU), whatever the tuning knob says
+        const int grid = persistent_grid(nt, 1);
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        TUP_SET_DYN_LDS((conv3x3_wgrad_c64_det_kernel), lds);
+        conv3x3_wgrad_c64_det_kernel<<<dim3(grid), dim3(512), lds, s>>>(
+            (const bf16_t*)x, (const bf16_t*)gmap, dwp, dbias, B, H, W, gr, sp, tilesX, tilesY, xr, xsp);
+        TUP_CHECK_LAUNCH();
+        return 0;
+    }
     TUP_SET_DYN_LDS((conv3x3_wgrad_c64_kernel), lds);
     static const int wg_per_cu = TUP_ENV_INT("TUP_WGRAD64_WG_PER_CU", 1);            // tuning knob (diagnostic build)
     conv3x3_wgrad_c64_kernel<<<dim3(persistent_grid(nt, wg_per_cu)), dim3(512), lds, reinterpret_cast<hipStream_t>(stream)>>>(
@@ -1079,4 +1233,90 @@ extern "C" int tup_feat_grad_combine(const void* a, const void* b, const void* g
         (const bf16_t*)a, (const bf16_t*)b, (const bf16_t*)gpe, (const bf16_t*)feat, (bf16_t*)out, B, H, W, Hp, Wp);
     TUP_CHECK_LAUNCH();
     return 0;
+}
+
+// ---- deterministic forms of the weight-gradient convs: the caller provides an fp32 slab of the matching *_slab size (contents
+// ignored); every persistent workgroup stores its partial sums into its own slice and tup_slab_reduce adds the slices in order onto
+// dwp / dbias (accumulated, as in the atomic forms) ----
+namespace {
+long long conv_tiles(int B, int H, int W, int th)
+{
+    return (long long)((W + TW - 1) / TW) * ((H + th - 1) / th) * B;
+}
+int planar_th(int r) { return (r >= 4) ? 2 : (r == 3 ? 4 : (r == 2 ? 16 : 32)); }
+}  // namespace
+
+// Slab floats of the deterministic weight-gradient convs.  kind 0: tup_conv3x3_c64_wgrad_det / _s2d_det (at the map size H x W of
+// the gradient), 1: tup_conv3x3_thin_wgrad_det, 2: tup_conv3x3_planar_wgrad_det with factor r.  Host only.
+extern "C" long long tup_conv_wgrad_slab(int kind, int B, int H, int W, int r)
+{
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    if (kind == 0) return (long long)persistent_grid(conv_tiles(B, H, W, TH), 1) * (64 * 9 * 64 + 64);
+    if (kind == 1) return (long long)persistent_grid(conv_tiles(B, H, W, TH), 2) * (3 * 9 * 64 + 4 * 3);
+    if (kind == 2 && r >= 1 && r <= 6) return (long long)persistent_grid(conv_tiles(B, H, W, planar_th(r)), r <= 2 ? 2 : 4) * (3 * r * r * 28);
+    return 0;
+}
+
+static int conv_c64_wgrad_det(const void* x, const void* gmap, float* dwp, float* dbias, int B, int H, int W, int gr, int sp,
+                              int xr, int xsp, float* slab, void* stream)
+{
+    if (B <= 0) return 0;
+    if (slab == nullptr) return (int)hipErrorInvalidValue;
+    int e = conv_c64_wgrad_launch<true>(x, gmap, slab, dbias, B, H, W, gr, sp, xr, xsp, stream);
+    if (e) return e;
+    const int grid = persistent_grid(conv_tiles(B, H, W, TH), 1);
+    e = tup_slab_reduce(slab, 64 * 9 * 64, grid, dwp, 64 * 9 * 64, 1, stream);
+    if (e || !dbias) return e;
+    return tup_slab_reduce(slab + (size_t)grid * (64 * 9 * 64), 64, grid, dbias, 64, 1, stream);
+}
+
+extern "C" int tup_conv3x3_c64_wgrad_det(const void* x, const void* gmap, float* dwp, float* dbias,
+                                         int B, int H, int W, int gr, int sp, float* slab, void* stream)
+{
+    return conv_c64_wgrad_det(x, gmap, dwp, dbias, B, H, W, gr, sp, 1, 0, slab, stream);
+}
+
+extern "C" int tup_conv3x3_c64_wgrad_s2d_det(const void* x, const void* gmap, float* dwp, float* dbias,
+                                             int B, int H, int W, int xr, int xsp, float* slab, void* stream)
+{
+    return conv_c64_wgrad_det(x, gmap, dwp, dbias, B, H, W, 1, 0, xr, xsp, slab, stream);
+}
+
+extern "C" int tup_conv3x3_thin_wgrad_det(const void* x, const float* gpl, float* dwp, float* dbias,
+                                          int B, int H, int W, float* slab, void* stream)
+{
+    if (B <= 0) return 0;
+    if (slab == nullptr) return (int)hipErrorInvalidValue;
+    const int tilesX = (W + TW - 1) / TW, tilesY = (H + TH - 1) / TH;
+    const long long nt = (long long)tilesX * tilesY * B;
+    if (nt > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    const int grid = persistent_grid(nt, 2);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    conv3x3_wgrad_thin_det_kernel<<<dim3(grid), dim3(256), X_TILE_BYTES + 256 * 32, s>>>((const bf16_t*)x, gpl, slab, dbias, B, H, W, tilesX, tilesY);
+    TUP_CHECK_LAUNCH();
+    const int e = tup_slab_reduce(slab, 3 * 9 * 64, grid, dwp, 3 * 9 * 64, 1, s);
+    if (e || !dbias) return e;
+    return tup_slab_reduce(slab + (size_t)grid * (3 * 9 * 64), 3, grid * 4, dbias, 3, 1, s);
+}
+
+extern "C" int tup_conv3x3_planar_wgrad_det(const float* x, const float* gpl, float* dw, float* dbias,
+                                            int B, int H, int W, int r, float* slab, void* stream)
+{
+    if (B <= 0) return 0;
+    if (r < 1 || r > 6 || slab == nullptr) return (int)hipErrorInvalidValue;
+    const int cout = 3 * r * r;
+    const int th = planar_th(r);
+    const int tilesX = (W + TW - 1) / TW, tilesY = (H + th - 1) / th;
+    const long long nt = (long long)tilesX * tilesY * B;
+    if (nt > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    const size_t lds = ((size_t)3 * (th + 2) * HALO_W + (size_t)cout * th * 32 + (size_t)r * r * 84) * sizeof(float);
+    const int grid = persistent_grid(nt, r <= 2 ? 2 : 4);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (r == 1) conv3x3_wgrad_planar_det_kernel<1, 32><<<dim3(grid), dim3(256), lds, st>>>(x, gpl, slab, dbias, B, H, W, r, th, tilesX, tilesY);
+    else if (r == 2) conv3x3_wgrad_planar_det_kernel<2, 16><<<dim3(grid), dim3(256), lds, st>>>(x, gpl, slab, dbias, B, H, W, r, th, tilesX, tilesY);
+    else conv3x3_wgrad_planar_det_kernel<0, 0><<<dim3(grid), dim3(256), lds, st>>>(x, gpl, slab, dbias, B, H, W, r, th, tilesX, tilesY);
+    TUP_CHECK_LAUNCH();
+    const int e = tup_slab_reduce(slab, cout * 27, grid, dw, cout * 27, 1, st);
+    if (e || !dbias) return e;
+    return tup_slab_reduce(slab + (size_t)grid * cout * 27, cout, grid, dbias, cout, 1, st);
 }

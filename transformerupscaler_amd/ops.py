@@ -650,12 +650,43 @@ def patch_embed_bwd_merge(gx, wt, add1, add2, relu_src, want_add1_colsum=False):
     return (out, cs.sum(0)) if want_add1_colsum else out
 
 
+# ---- deterministic forms: the weight-gradient convs below have *_det forms without float atomics (a slab of per-workgroup partial
+# sums, added in a fixed order), bitwise reproducible from run to run.  The other weight-gradient reductions of the backward still
+# use atomics, so a training step is not reproducible yet: the mode is explicit-only and does not follow
+# torch.use_deterministic_algorithms until every site has a deterministic form. ----
+deterministic = False            # A/B attribute: True routes the weight-gradient convs to their deterministic forms
+
+
+def deterministic_enabled():
+    """Whether the wrappers take the deterministic forms now (read at call time)."""
+    return bool(deterministic)
+
+
+def conv_wgrad_slab_floats(kind, B, H, W, r=1):
+    """fp32 slab size of the deterministic weight-gradient convs (kind 0 = c64 / c64 s2d, 1 = thin, 2 = planar with factor r).
+    Host only (tup_conv_wgrad_slab returns the count, not an error code)."""
+    n = int(_lib.load().tup_conv_wgrad_slab(int(kind), int(B), int(H), int(W), int(r)))
+    if n <= 0:
+        raise ValueError(f"tup_conv_wgrad_slab({kind}, {B}, {H}, {W}, {r}): invalid shape")
+    return n
+
+
+def _slab(kind, B, H, W, device, r=1):
+    return torch.empty((conv_wgrad_slab_floats(kind, B, H, W, r),), dtype=F32, device=device)
+
+
 def conv_c64_wgrad(x, gmap, gr=1):
     """-> (dwp fp32 [gr*gr][64][9][64] (sp, co, tap, ci), dbias fp32 [gr*gr][64])."""
     B, H, W, C = x.shape
     assert C == 64 and tuple(gmap.shape) == (B, H * gr, W * gr, 64)
     dwp = _zeros((gr * gr, 64, 9, 64), x.device)
     db = _zeros((gr * gr, 64), x.device)
+    if deterministic_enabled():
+        slab = _slab(0, B, H, W, x.device)
+        for sp in range(gr * gr):
+            _lib.call("tup_conv3x3_c64_wgrad_det", _chk(x, BF16, None, "x"), _chk(gmap, BF16, None, "gmap"), dwp[sp].data_ptr(),
+                      db[sp].data_ptr(), B, H, W, gr, sp, slab.data_ptr(), _stream())
+        return dwp, db
     for sp in range(gr * gr):
         _lib.call("tup_conv3x3_c64_wgrad", _chk(x, BF16, None, "x"), _chk(gmap, BF16, None, "gmap"), dwp[sp].data_ptr(),
                   db[sp].data_ptr(), B, H, W, gr, sp, _stream())
@@ -667,6 +698,11 @@ def conv_thin_wgrad(x, gpl, want_bias):
     assert C == 64
     dwp = _zeros((3, 9, 64), x.device)
     db = _zeros((3,), x.device) if want_bias else None
+    if deterministic_enabled():
+        slab = _slab(1, B, H, W, x.device)
+        _lib.call("tup_conv3x3_thin_wgrad_det", _chk(x, BF16, None, "x"), _chk(gpl, F32, (B, 3, H, W), "gpl"), dwp.data_ptr(),
+                  None if db is None else db.data_ptr(), B, H, W, slab.data_ptr(), _stream())
+        return dwp, db
     _lib.call("tup_conv3x3_thin_wgrad", _chk(x, BF16, None, "x"), _chk(gpl, F32, (B, 3, H, W), "gpl"), dwp.data_ptr(),
               None if db is None else db.data_ptr(), B, H, W, _stream())
     return dwp, db
@@ -700,6 +736,11 @@ def conv_planar_wgrad(x, gpl, r):
     cout = 3 * r * r
     dw = _zeros((cout, 3, 3, 3), x.device)
     db = _zeros((cout,), x.device)
+    if deterministic_enabled():
+        slab = _slab(2, B, H, W, x.device, r)
+        _lib.call("tup_conv3x3_planar_wgrad_det", _chk(x, F32, None, "x"), _chk(gpl, F32, (B, 3, H * r, W * r), "gpl"),
+                  dw.data_ptr(), db.data_ptr(), B, H, W, r, slab.data_ptr(), _stream())
+        return dw, db
     _lib.call("tup_conv3x3_planar_wgrad", _chk(x, F32, None, "x"), _chk(gpl, F32, (B, 3, H * r, W * r), "gpl"),
               dw.data_ptr(), db.data_ptr(), B, H, W, r, _stream())
     return dw, db
@@ -867,6 +908,12 @@ def conv_c64_wgrad_s2d(x, gmap, xr):
     assert tuple(x.shape) == (B, H * xr, W * xr, 64)
     dwp = _zeros((xr * xr, 64, 9, 64), x.device)
     db = _zeros((64,), x.device)
+    if deterministic_enabled():
+        slab = _slab(0, B, H, W, x.device)
+        for sp in range(xr * xr):
+            _lib.call("tup_conv3x3_c64_wgrad_s2d_det", _chk(x, BF16, None, "x"), _chk(gmap, BF16, None, "gmap"), dwp[sp].data_ptr(),
+                      db.data_ptr() if sp == 0 else None, B, H, W, xr, sp, slab.data_ptr(), _stream())
+        return dwp, db
     for sp in range(xr * xr):
         _lib.call("tup_conv3x3_c64_wgrad_s2d", _chk(x, BF16, None, "x"), _chk(gmap, BF16, None, "gmap"), dwp[sp].data_ptr(),
                   db.data_ptr() if sp == 0 else None, B, H, W, xr, sp, _stream())
