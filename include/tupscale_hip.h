@@ -306,6 +306,35 @@ int tup_conv3x3_thin_wgrad_det(const void* x, const float* gpl, float* dwp, floa
 int tup_conv3x3_planar_wgrad_det(const float* x, const float* gpl, float* dw, float* dbias,
                                  int B, int H, int W, int r, float* slab, void* stream);
 
+/* Deterministic forms of the token-path reductions (the weight-gradient GEMMs, the column sums, the LayerNorm backward): the
+ * arguments of the atomic twin plus `slab`, an fp32 workspace of tup_wgrad_slab(...) floats (contents ignored, no allocation
+ * inside).  Every static work item -- an M slice of a 64 x 64 tile, a wide-kernel workgroup's M slice, a column-sum row chunk, a
+ * LayerNorm workgroup -- stores its partial result into its own slab slice, and tup_slab_reduce adds the slices onto the outputs
+ * (accumulating: the caller zeroes them, as for the atomic forms).  The split of M depends on the shapes only.
+ *   tup_wgrad_slab(kind, M, NI, NJ): kind 0 = the 64 x 64-tile GEMM (tup_gemm_wgrad_bias_det and the three fp32 patch forms; M
+ *   token rows, output NI x NJ; a slice is NI x NJ with NI column sums behind it), 1 = the wide patch GEMM
+ *   (tup_patch_wgrad_bf16_det; NI = 192, NJ = 4096), 2 = tup_colsum_det (M rows, NI columns, NJ ignored), 3 = the LayerNorm
+ *   backward (M rows, NI = 192 or 128, NJ ignored; at most 256 slices of 2 x NI).  For the patch forms M is the token-row count
+ *   of the twin's P operand (B * windows * 64, or B * H/8 * W/8 for tup_rt_patch_wgrad_det).  Host only: returns a float count
+ *   (0 for an invalid request), not a hipError_t.
+ *   tup_gemm_wgrad_bias_det: colsum_out == NULL gives the deterministic tup_gemm_wgrad.  When colsum_out == out + NI * NJ (and
+ *   ldo == NJ) one reduce launch serves both; an output with ldo > NJ is reduced row by row.
+ *   tup_layernorm_bwd_det / tup_layernorm128_bwd_det: dbeta == dgamma + C likewise takes one reduce launch. */
+long long tup_wgrad_slab(int kind, long long M, int NI, int NJ);
+int tup_gemm_wgrad_bias_det(const void* P, int p_dtype, int ldp, const void* Q, int q_dtype, int ldq,
+                            float* out, int ldo, float* colsum_out, int M, int NI, int NJ, float* slab, void* stream);
+int tup_patch_wgrad_det(const float* P, const void* map, float* out, int B, int H, int W, int reflect, float* slab, void* stream);
+int tup_patch_wgrad_bf16_det(const void* P, const void* map, float* out, int B, int H, int W, int reflect, float* slab, void* stream);
+int tup_rt_patch_wgrad_det(const float* P, const void* map, float* out, int B, int H, int W, float* slab, void* stream);
+int tup_wt_patch_wgrad_det(const float* P, const void* map, float* out, int B, int H, int W, int NI, float* slab, void* stream);
+int tup_colsum_det(const void* G, int dtype, int ld, float* out, int M, int N, const void* rowmask, float* slab, void* stream);
+int tup_layernorm_bwd_det(const void* gy, const float* x, const float* mean, const float* rstd,
+                          const float* gamma, const float* gres, float* dx, float* dgamma, float* dbeta,
+                          int M, void* gdrop, float drop_p, unsigned int drop_seed, float* slab, void* stream);
+int tup_layernorm128_bwd_det(const void* gy, const float* x, const float* mean, const float* rstd,
+                             const float* gamma, const float* gres, float* dx, float* dgamma, float* dbeta,
+                             int M, void* gdrop, float drop_p, unsigned int drop_seed, float* slab, void* stream);
+
 /* Input gradient of Conv2d(3,3rr,k3)+PixelShuffle(r) on planar fp32 (final_upscale): w fp32 [3rr][3][3][3]. */
 int tup_conv3x3_planar_dgrad(const float* gpl, const float* w, float* gx, int B, int H, int W, int r, void* stream);
 

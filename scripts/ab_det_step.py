@@ -1,6 +1,9 @@
-"""Training-step time with the weight-gradient convs in their atomic forms (ops.deterministic = False) and in their deterministic
-forms (True): FastTransformer 2x 720p -> 1080p, batch 4 (config 3) and ResidualTransformer 6x 720p, batch 2 (config 5).
-Five alternating runs of 10 steps per arm after warm-up; median [range] in ms per step."""
+"""Training-step time in the default mode (ops.deterministic = False: atomic forms), in the default mode with branch A on the
+explicit stage convs (FastTransformer only: what that route-around of deterministic mode costs without the slab forms; the
+second route-around, patch_unembed.bias from one more column-sum pass, is NOT in this arm, so the split it gives is incomplete) and in
+deterministic mode (True): FastTransformer 2x 720p -> 1080p, batch 4 (config 3) and ResidualTransformer 6x 720p, batch 2
+(config 5).  Five alternating runs of 10 steps per arm after warm-up; median [range] in ms per step.  Run the same
+script from a checkout of an older commit for that commit's two arms (there True meant the convs only)."""
 import importlib
 import os
 import statistics
@@ -10,7 +13,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from transformerupscaler_amd import harness, ops  # noqa: E402
+from transformerupscaler_amd import fast_transformer, harness, ops  # noqa: E402
 from transformerupscaler_amd.autograd import l1_loss  # noqa: E402
 from transformerupscaler_amd.weights import deterministic_state_dict, rt_deterministic_state_dict  # noqa: E402
 
@@ -54,19 +57,25 @@ def timed(step):
     return (time.perf_counter() - t0) / STEPS * 1e3
 
 
-for name, make in (("FastTransformer x2 B=4", ft_case), ("ResidualTransformer x6 B=2", rt_case)):
+ARMS = {"default": (False, True), "default, explicit branch A": (False, False), "deterministic": (True, True)}
+
+
+def set_arm(arm):
+    ops.deterministic, fast_transformer.compose_branch_a_in_training = ARMS[arm]
+
+
+for name, make, arms in (("FastTransformer x2 B=4", ft_case, list(ARMS)), ("ResidualTransformer x6 B=2", rt_case, ["default", "deterministic"])):
     step = make()
-    res = {False: [], True: []}
-    for arm in (False, True):
-        ops.deterministic = arm
+    res = {arm: [] for arm in arms}
+    for arm in arms:
+        set_arm(arm)
         for _ in range(2):
             step()
     for _ in range(RUNS):
-        for arm in (False, True):
-            ops.deterministic = arm
+        for arm in arms:
+            set_arm(arm)
             res[arm].append(timed(step))
-    ops.deterministic = False
-    print(f"{name}: atomic {statistics.median(res[False]):.2f} ms [{min(res[False]):.2f}-{max(res[False]):.2f}], "
-          f"deterministic convs {statistics.median(res[True]):.2f} ms [{min(res[True]):.2f}-{max(res[True]):.2f}]", flush=True)
+    set_arm("default")
+    print(f"{name}: " + ", ".join(f"{arm} {statistics.median(v):.2f} ms [{min(v):.2f}-{max(v):.2f}]" for arm, v in res.items()), flush=True)
     del step
     torch.cuda.empty_cache()

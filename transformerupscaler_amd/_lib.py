@@ -112,6 +112,16 @@ SIGNATURES = {
     "tup_conv3x3_c64_wgrad_s2d_det": [P, P, P, P, I, I, I, I, I, P, P],
     "tup_conv3x3_thin_wgrad_det": [P, P, P, P, I, I, I, P, P],
     "tup_conv3x3_planar_wgrad_det": [P, P, P, P, I, I, I, I, P, P],
+    # ... and of the token path (csrc/gemm_wgrad.hip, csrc/attention_bwd.hip)
+    "tup_wgrad_slab": [I, c_longlong, I, I],
+    "tup_gemm_wgrad_bias_det": [P, I, I, P, I, I, P, I, P, I, I, I, P, P],
+    "tup_patch_wgrad_det": [P, P, P, I, I, I, I, P, P],
+    "tup_patch_wgrad_bf16_det": [P, P, P, I, I, I, I, P, P],
+    "tup_rt_patch_wgrad_det": [P, P, P, I, I, I, P, P],
+    "tup_wt_patch_wgrad_det": [P, P, P, I, I, I, I, P, P],
+    "tup_colsum_det": [P, I, I, P, I, I, P, P, P],
+    "tup_layernorm_bwd_det": [P, P, P, P, P, P, P, P, P, I, P, F, U, P, P],
+    "tup_layernorm128_bwd_det": [P, P, P, P, P, P, P, P, P, I, P, F, U, P, P],
 }
 
 
@@ -122,7 +132,7 @@ class TupscaleLibraryError(RuntimeError):
 _lib = None
 
 
-COUNT_RETURNING = {"tup_window_attn_bwd_scratch", "tup_conv_wgrad_slab"}      # return an element count, not a hipError_t
+COUNT_RETURNING = {"tup_window_attn_bwd_scratch", "tup_conv_wgrad_slab", "tup_wgrad_slab"}      # return an element count, not a hipError_t
 
 
 def load():

@@ -59,7 +59,10 @@ def forward_train(pk, frags_t, x, scale, res_out, require_ratio, drop_p=0.0, see
     ups = [feat]
     # the last Upsampler stage + up1_conv through their exact composition (csrc/branch_a_train.hip) when it is a x2 stage:
     # one 5x5 conv with 12 outputs instead of the 64 -> 256 conv, the 64-channel HR tensor and the 64 -> 3 conv
-    composed = "bra.comp" in pk and stages[-1][1] == 2 and min(H, W) * (scale // 2) >= 6
+    # Not in deterministic mode (ops.deterministic, set before the forward): the composed backward (tup_bra_backward) sums its weight
+    # gradients with float atomics and has no deterministic form, so branch A trains through the explicit stage convs, whose weight
+    # gradients have one.  The decision travels in sv["bra"]: a backward follows the forward that produced its sv.
+    composed = "bra.comp" in pk and stages[-1][1] == 2 and min(H, W) * (scale // 2) >= 6 and not ops.deterministic_enabled()
     for si, (_, r) in enumerate(stages[:-1] if composed else stages):
         ups.append(ops.conv_c64(ups[-1], pk[f"up1.{si}.w"], pk[f"up1.{si}.b"], r, relu=False))
     sv["ups"], sv["bra"] = ups, composed
@@ -151,7 +154,8 @@ def backward_train(pk, frags_t, frags_n, sv, scale, gout, reducer=None, want_inp
     # patch_unembed's bias gradient = the column sums of g_comb.  Without a gradient reducer they ride along in the kernel that reads
     # g_comb last (the merged patch_embed input gradient at the end of this function); with one, the bias has to be ready NOW so that
     # its bucket's all-reduce starts under the rest of the backward
-    late_pu_bias = reducer is None and pe_merge and H % 8 == 0 and W % 8 == 0
+    # (nor in deterministic mode: the merge kernel adds those sums with float atomics; ops.colsum has a deterministic form)
+    late_pu_bias = reducer is None and pe_merge and H % 8 == 0 and W % 8 == 0 and not ops.deterministic_enabled()
     if not late_pu_bias:
         g["patch_unembed.bias"] = ops.colsum(g_comb.view(-1, 64))
     g["patch_unembed.weight"] = ops.patch_wgrad(sv["xw_out"], g_comb, reflect=False).view(192, 8, 8, 64).permute(0, 3, 1, 2)

@@ -26,7 +26,9 @@ TUP_DEVICE bf16x8 join4(s16x4 lo, s16x4 hi) {
 
 constexpr int HD = 16, NTOK = 64;      // heads / width are template parameters (12 x 16 = 192, or 8 x 16 = 128)
 
-template <int NQ>
+// DET: the deterministic form -- workgroup blockIdx.x stores its column sums into slab slice blockIdx.x (dgamma = the slab:
+// [grid][2][LD], dgamma sums then dbeta sums; dbeta unused) instead of adding them; tup_slab_reduce adds the slices in order
+template <int NQ, bool DET>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(
     const bf16_t* __restrict__ gy, const float* __restrict__ x, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ gres,
@@ -111,8 +113,14 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(
         float a = 0.f, b = 0.f;
 #pragma unroll
         for (int s = 0; s < 16; ++s) { a += red[0][s][threadIdx.x]; b += red[1][s][threadIdx.x]; }
-        atomicAdd(dgamma + threadIdx.x, a);
-        atomicAdd(dbeta + threadIdx.x, b);
+        if constexpr (DET) {
+            float* o = dgamma + (size_t)blockIdx.x * (2 * LD);
+            o[threadIdx.x] = a;
+            o[LD + threadIdx.x] = b;
+        } else {
+            atomicAdd(dgamma + threadIdx.x, a);
+            atomicAdd(dbeta + threadIdx.x, b);
+        }
     }
 }
 
@@ -398,7 +406,7 @@ extern "C" int tup_layernorm_bwd(const void* gy, const float* x, const float* me
     if (M <= 0) return 0;
     if (gdrop && (drop_p <= 0.f || drop_p >= 1.f)) return (int)hipErrorInvalidValue;
     const int blocks = ln_bwd_blocks(M);
-    layernorm_bwd_kernel<3><<<dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    layernorm_bwd_kernel<3, false><<<dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
         (const bf16_t*)gy, x, mean, rstd, gamma, gres, dx, dgamma, dbeta, M, (bf16_t*)gdrop,
         gdrop ? (uint32_t)((double)drop_p * 4294967296.0) : 0u, gdrop ? 1.0f / (1.0f - drop_p) : 1.f, drop_seed);
     TUP_CHECK_LAUNCH();
@@ -413,11 +421,49 @@ extern "C" int tup_layernorm128_bwd(const void* gy, const float* x, const float*
     if (M <= 0) return 0;
     if (gdrop && (drop_p <= 0.f || drop_p >= 1.f)) return (int)hipErrorInvalidValue;
     const int blocks = ln_bwd_blocks(M);
-    layernorm_bwd_kernel<2><<<dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    layernorm_bwd_kernel<2, false><<<dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
         (const bf16_t*)gy, x, mean, rstd, gamma, gres, dx, dgamma, dbeta, M, (bf16_t*)gdrop,
         gdrop ? (uint32_t)((double)drop_p * 4294967296.0) : 0u, gdrop ? 1.0f / (1.0f - drop_p) : 1.f, drop_seed);
     TUP_CHECK_LAUNCH();
     return 0;
+}
+
+// Deterministic forms: `slab` = tup_wgrad_slab(3, M, 192 | 128, 0) floats (contents ignored); the grid is tup_ln_bwd_det_blocks(M)
+// workgroups, each with a slice of 2 x C sums, added in order onto dgamma and dbeta (which the caller zeroed).
+namespace {
+template <int NQ>
+int layernorm_bwd_det(const void* gy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* gres,
+                      float* dx, float* dgamma, float* dbeta, int M, void* gdrop, float drop_p, unsigned int drop_seed,
+                      float* slab, void* stream)
+{
+    constexpr int LD = NQ * 64;
+    if (M <= 0) return 0;
+    if ((gdrop && (drop_p <= 0.f || drop_p >= 1.f)) || slab == nullptr) return (int)hipErrorInvalidValue;
+    const int blocks = tup_ln_bwd_det_blocks(M);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    layernorm_bwd_kernel<NQ, true><<<dim3(blocks), dim3(256), 0, s>>>(
+        (const bf16_t*)gy, x, mean, rstd, gamma, gres, dx, slab, nullptr, M, (bf16_t*)gdrop,
+        gdrop ? (uint32_t)((double)drop_p * 4294967296.0) : 0u, gdrop ? 1.0f / (1.0f - drop_p) : 1.f, drop_seed);
+    TUP_CHECK_LAUNCH();
+    if (dbeta == dgamma + LD) return tup_slab_reduce(slab, 2 * LD, blocks, dgamma, 2 * LD, 1, s);      // adjacent: one reduce serves both
+    const int e = tup_slab_reduce(slab, 2 * LD, blocks, dgamma, LD, 1, s);
+    if (e != 0) return e;
+    return tup_slab_reduce(slab + LD, 2 * LD, blocks, dbeta, LD, 1, s);
+}
+}  // namespace
+
+extern "C" int tup_layernorm_bwd_det(const void* gy, const float* x, const float* mean, const float* rstd,
+                                     const float* gamma, const float* gres, float* dx, float* dgamma, float* dbeta,
+                                     int M, void* gdrop, float drop_p, unsigned int drop_seed, float* slab, void* stream)
+{
+    return layernorm_bwd_det<3>(gy, x, mean, rstd, gamma, gres, dx, dgamma, dbeta, M, gdrop, drop_p, drop_seed, slab, stream);
+}
+
+extern "C" int tup_layernorm128_bwd_det(const void* gy, const float* x, const float* mean, const float* rstd,
+                                        const float* gamma, const float* gres, float* dx, float* dgamma, float* dbeta,
+                                        int M, void* gdrop, float drop_p, unsigned int drop_seed, float* slab, void* stream)
+{
+    return layernorm_bwd_det<2>(gy, x, mean, rstd, gamma, gres, dx, dgamma, dbeta, M, gdrop, drop_p, drop_seed, slab, stream);
 }
 
 // Dense bias in the N-layout fragment order (backward only): fp32 [12][4 qt][4 kt][64][4].

@@ -33,6 +33,12 @@ GUARDED = [
     ("branch_a_train.hip", ["bra_wgrad_kernel"]),
     # counted vmcnt between its LDS-DMA stages, asm fragment reads with counted lgkmcnt
     ("gemm_wgrad.hip", ["gemm_wgrad_wide_kernel"]),
+    # the deterministic forms of the token-path reductions: no counted hand-off in these, guarded so that a DET epilogue that starts
+    # to spill (a slower twin of a kernel tuned to stay under its register budget) fails the build instead of shipping
+    # (the DET = true instantiations: mangled ...Lb1EEEv...; the wide kernel's is covered by its entry above)
+    ("gemm_wgrad.hip", ["gemm_wgrad_kernelILi0ELi0ELb1E", "gemm_wgrad_kernelILi0ELi1ELb1E", "gemm_wgrad_kernelILi1ELi0ELb1E",
+                        "gemm_wgrad_kernelILi1ELi1ELb1E", "gemm_wgrad_kernelILi1ELi2ELb1E", "colsum_kernelILb0ELb1E", "colsum_kernelILb1ELb1E"]),
+    ("attention_bwd.hip", ["layernorm_bwd_kernelILi2ELb1E", "layernorm_bwd_kernelILi3ELb1E"]),
 ]
 # diagnostic template instantiations, never launched by the product path: fused_qkv_attn_kernel<PROJ, MLP, STAMPS = true>, the
 # timing ablations fused_mlp_v2_kernel<ABL != 0>

@@ -306,3 +306,13 @@ inline void drop_pair_params(float p, uint32_t& thresh_hi, float& inv_keep) {
 // Ordered slab reduce of the deterministic weight-gradient forms (deterministic.hip): out[i] (accumulate ? += : =) sum over
 // s < nslab of slab[s * ld + i], in a fixed order that depends on nslab only.
 extern "C" int tup_slab_reduce(const float* slab, long long ld, int nslab, float* out, long long n, int accumulate, void* stream);
+
+// Workgroups of the deterministic LayerNorm backward (attention_bwd.hip) = slices of its slab (tup_wgrad_slab kind 3): 16 rows per
+// workgroup and sweep, at most 256 workgroups, every workgroup the same number of sweeps.  A function of M only: the diagnostic
+// build's TUP_LN_BWD_BLOCKS, which would change the slicing, is not read here.
+inline int tup_ln_bwd_det_blocks(int M)
+{
+    const int groups = (M + 15) / 16;
+    const int sweeps = (groups + 255) / 256;
+    return (groups + sweeps - 1) / sweeps;
+}

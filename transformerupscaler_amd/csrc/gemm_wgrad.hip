@@ -6,6 +6,12 @@
 // exactly the A / B fragment of v_mfma_f32_16x16x16_bf16.  M is split over gridDim.z; partial
 // results are added to the fp32 output with global float atomics (64-B segments).
 //
+// DET (the *_det entries): the deterministic forms.  Every static work item (an M slice blockIdx.z of a 64 x 64 tile, a wide-kernel
+// workgroup's M slice of its tile, a column-sum row chunk) stores its partial result with plain stores into its own slice of a
+// caller-provided fp32 slab (p.out = the slab, p.slice floats per M slice) and tup_slab_reduce adds the slices in a fixed order.
+// The split of M is a function of the shapes only, so the bits are the same on every run.  The kernels share their bodies through the DET
+// template flag; the <..., false> instantiations compile to the code they had without it.
+//
 // Autograd call sites replaced (reference train.py:138 backward through):
 //   nn.Linear weights     model.py:79,81,146-151   P = grad_out [M][N], Q = layer input [M][K]
 //   patch_embed weight    model.py:215,268          P = grad tokens, Q = 8x8 patches of feat (gather)
@@ -27,13 +33,14 @@ struct WgradParams {
     int H, W, Ht, Wt_, nWx, nWy, reflect;   // OP_PATCH geometry (token rows in window layout)
     int linear;                             // OP_PATCH: token rows are a plain [B][Ht][Wt] grid (ResidualTransformer)
     int xcd_remap;
+    long long slice;             // DET: floats per M slice of the slab (out / colsum_out point into slice 0)
 };
 
 TUP_DEVICE s16x4 lds_read_tr16(const char* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
 }
 
-template <int PMODE, int QMODE>
+template <int PMODE, int QMODE, bool DET>
 __global__ __launch_bounds__(256, 2) void gemm_wgrad_kernel(const WgradParams p)
 {
     __shared__ __attribute__((aligned(16))) char smem[2 * 2 * 64 * 128];   // [buf][P|Q][64 rows][128 B]
@@ -195,24 +202,39 @@ __global__ __launch_bounds__(256, 2) void gemm_wgrad_kernel(const WgradParams p)
     }
 
     // D[row = i 4g+e][col = j l16]
+    if constexpr (DET) {
+        // M slice bz owns slab slice bz: [NI][NJ] (p.ldo = NJ) and, behind it, the NI column sums
+        float* o = p.out + (size_t)bz * p.slice;
 #pragma unroll
-    for (int jt = 0; jt < 4; ++jt)
+        for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
+            for (int e = 0; e < 4; ++e) o[(size_t)(i0 + 16 * wave + 4 * g + e) * p.ldo + j0 + 16 * jt + l16] = acc[jt][e];
+        if (want_cs && l16 == 0) {
+            float* oc = p.colsum_out + (size_t)bz * p.slice;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) oc[i0 + 16 * wave + 4 * g + e] = accs[e];
+        }
+    } else {
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
 #ifndef TUP_EXP_NOATOMIC      // timing experiment (wrong results)
-            atomicAdd(p.out + (size_t)(i0 + 16 * wave + 4 * g + e) * p.ldo + j0 + 16 * jt + l16, acc[jt][e]);
+                atomicAdd(p.out + (size_t)(i0 + 16 * wave + 4 * g + e) * p.ldo + j0 + 16 * jt + l16, acc[jt][e]);
 #else
-            if (acc[jt][e] == 123.456f) p.out[0] = 1.f;
+                if (acc[jt][e] == 123.456f) p.out[0] = 1.f;
 #endif
-    if (want_cs && l16 == 0) {
+        if (want_cs && l16 == 0) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) atomicAdd(p.colsum_out + i0 + 16 * wave + 4 * g + e, accs[e]);
+            for (int e = 0; e < 4; ++e) atomicAdd(p.colsum_out + i0 + 16 * wave + 4 * g + e, accs[e]);
+        }
     }
 }
 
 // column sums: out[n] += sum_m G[m][n].  16-byte loads: LPR lanes cover a 64-column stripe of one row, the
 // block's other lanes take further rows; grid.x = column stripes, grid.y splits M.
-template <bool F32>
+// DET: row chunk blockIdx.y stores its 64 sums into slab row blockIdx.y (out = the slab, [gridDim.y][N]).
+template <bool F32, bool DET>
 __global__ __launch_bounds__(256) void colsum_kernel(const void* __restrict__ G, int ld, float* __restrict__ out, int M, int N, int mchunk,
                                                      const unsigned char* __restrict__ rowmask)
 {
@@ -265,7 +287,8 @@ __global__ __launch_bounds__(256) void colsum_kernel(const void* __restrict__ G,
     if (threadIdx.x < 64) {
         float s = 0.f;
         for (int r = 0; r < RPB; ++r) s += red[r][threadIdx.x];
-        atomicAdd(out + blockIdx.x * 64 + threadIdx.x, s);
+        if constexpr (DET) out[(size_t)blockIdx.y * N + blockIdx.x * 64 + threadIdx.x] = s;
+        else atomicAdd(out + blockIdx.x * 64 + threadIdx.x, s);
     }
 }
 
@@ -288,7 +311,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const void* __restrict__ G,
 // ------------------------------------------------------------------------------------------------
 __device__ __attribute__((aligned(16))) unsigned int tup_wg_zero_line[4] = {0u, 0u, 0u, 0u};
 
-template <int JP, int NST, bool PATCH, int NW>
+template <int JP, int NST, bool PATCH, int NW, bool DET>
 __global__ __launch_bounds__(64 * NW, 1) void gemm_wgrad_wide_kernel(const WgradParams p)
 {
     constexpr int IP = 3;                              // 64-column panels of P per workgroup
@@ -445,59 +468,213 @@ __global__ __launch_bounds__(64 * NW, 1) void gemm_wgrad_wide_kernel(const Wgrad
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the zero-line requests past the end
 
     // D[row = i 4g+e][col = j l16]
-#pragma unroll
-    for (int it = 0; it < IT; ++it)
-#pragma unroll
-        for (int jt = 0; jt < JT; ++jt)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                atomicAdd(p.out + (size_t)(i0 + 16 * IT * wi + 16 * it + 4 * g + e) * p.ldo + j0 + 32 * JP * wj + 16 * jt + l16, acc[it][jt][e]);
-    if (want_cs && l16 == 0) {
+    if constexpr (DET) {
+        // M slice mz owns slab slice mz: [NI][NJ] (p.ldo = NJ); the deterministic entries pass no colsum_out
+        float* o = p.out + (size_t)mz * p.slice;
 #pragma unroll
         for (int it = 0; it < IT; ++it)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) atomicAdd(p.colsum_out + i0 + 16 * IT * wi + 16 * it + 4 * g + e, accs[it][e]);
+            for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    o[(size_t)(i0 + 16 * IT * wi + 16 * it + 4 * g + e) * p.ldo + j0 + 32 * JP * wj + 16 * jt + l16] = acc[it][jt][e];
+    } else {
+#pragma unroll
+        for (int it = 0; it < IT; ++it)
+#pragma unroll
+            for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    atomicAdd(p.out + (size_t)(i0 + 16 * IT * wi + 16 * it + 4 * g + e) * p.ldo + j0 + 32 * JP * wj + 16 * jt + l16, acc[it][jt][e]);
+        if (want_cs && l16 == 0) {
+#pragma unroll
+            for (int it = 0; it < IT; ++it)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) atomicAdd(p.colsum_out + i0 + 16 * IT * wi + 16 * it + 4 * g + e, accs[it][e]);
+        }
     }
 }
 
-template <int JP, int NST, bool PATCH, int NW>
-int launch_wide(WgradParams p, hipStream_t s)
+// M splits.  They are functions of the shapes only (the product build has no tuning knobs; the diagnostic build's TUP_COLSUM_BLOCKS
+// and TUP_PATCH_WGRAD_FORM, which would change the slicing, are ignored by the deterministic forms, and TUP_WGRAD_NO_XCD only
+// renumbers the workgroups: slice bz holds the same rows either way).
+// wide kernel: one workgroup per CU (the LDS ring); M slices of whole 64-row stages
+int wide_split(int M, int nij, int* mchunk)
+{
+    int msplit = 256 / nij;
+    if (msplit < 1) msplit = 1;
+    *mchunk = (((M + msplit - 1) / msplit) + 63) / 64 * 64;
+    return (M + *mchunk - 1) / *mchunk;
+}
+
+// Five workgroups per CU are resident (32 KB of LDS each, 52 registers): any grid up to 1,280 workgroups is one round; the
+// split is rounded DOWN so that the M slices never come out shorter than the target (more slices = more fp32 atomics on the
+// same 64 x 64 output tiles, or more slab slices to write and add up in the deterministic form; the kernel is bound by L2 reads of its operands)
+int tile_split(int M, int blocks_ij, int* mchunk)
+{
+    int msplit = 1024 / blocks_ij;
+    const int maxsplit = (M + 63) / 64;
+    if (msplit > maxsplit) msplit = maxsplit;
+    if (msplit < 1) msplit = 1;
+    *mchunk = (((M + msplit - 1) / msplit) + 63) / 64 * 64;
+    return (M + *mchunk - 1) / *mchunk;
+}
+
+// every workgroup ends with 64 float atomics on the same addresses (they serialise in L2): a few hundred workgroups, not thousands
+// (the 64-column map sums: 2,048 workgroups 106 us, 512 95 us; three column stripes of token rows are flat from 512 to 2,048)
+int colsum_split(int M, int N, int forced, int* mchunk)
+{
+    const int target = forced > 0 ? forced : (N == 64 ? 512 : 2048);
+    int msplit = target / (N / 64);
+    if (msplit < 1) msplit = 1;
+    *mchunk = (M + msplit - 1) / msplit;
+    if (*mchunk < 256) *mchunk = 256;
+    return (M + *mchunk - 1) / *mchunk;
+}
+
+// DET: p.out is the caller's output; the kernel writes the slab (slices of NI x NJ) and the ordered reduce adds them onto it
+template <int JP, int NST, bool PATCH, int NW, bool DET = false>
+int launch_wide(WgradParams p, hipStream_t s, float* slab = nullptr)
 {
     if (p.M <= 0) return 0;
     if (p.NI % 192 || p.NJ % (64 * JP)) return (int)hipErrorInvalidValue;
     constexpr size_t lds = (size_t)NST * (3 + JP) * 8192;
-    TUP_SET_DYN_LDS((gemm_wgrad_wide_kernel<JP, NST, PATCH, NW>), lds);
     const int nij = (p.NI / 192) * (p.NJ / (64 * JP));
-    // one workgroup per CU (the LDS ring); M slices of whole 64-row stages
-    int msplit = 256 / nij;
-    if (msplit < 1) msplit = 1;
-    p.mchunk = (((p.M + msplit - 1) / msplit) + 63) / 64 * 64;
-    msplit = (p.M + p.mchunk - 1) / p.mchunk;
-    gemm_wgrad_wide_kernel<JP, NST, PATCH, NW><<<dim3(nij * msplit), dim3(64 * NW), lds, s>>>(p);
-    TUP_CHECK_LAUNCH();
-    return 0;
+    const int msplit = wide_split(p.M, nij, &p.mchunk);
+    if constexpr (DET) {
+        if (slab == nullptr || p.colsum_out != nullptr || p.ldo != p.NJ) return (int)hipErrorInvalidValue;
+        float* out = p.out;
+        p.out = slab; p.slice = (long long)p.NI * p.NJ;
+        TUP_SET_DYN_LDS((gemm_wgrad_wide_kernel<JP, NST, PATCH, NW, true>), lds);
+        gemm_wgrad_wide_kernel<JP, NST, PATCH, NW, true><<<dim3(nij * msplit), dim3(64 * NW), lds, s>>>(p);
+        TUP_CHECK_LAUNCH();
+        return tup_slab_reduce(slab, p.slice, msplit, out, p.slice, 1, s);
+    } else {
+        TUP_SET_DYN_LDS((gemm_wgrad_wide_kernel<JP, NST, PATCH, NW, false>), lds);
+        gemm_wgrad_wide_kernel<JP, NST, PATCH, NW, false><<<dim3(nij * msplit), dim3(64 * NW), lds, s>>>(p);
+        TUP_CHECK_LAUNCH();
+        return 0;
+    }
 }
 
-template <int PMODE, int QMODE>
-int launch(WgradParams p, hipStream_t s)
+// DET: a slab slice is the whole NI x NJ matrix with the NI column sums behind it, so when the caller's bias gradient lies right
+// behind its weight gradient one reduce launch serves both
+template <int PMODE, int QMODE, bool DET = false>
+int launch(WgradParams p, hipStream_t s, float* slab = nullptr)
 {
     if (p.M <= 0) return 0;
     if (p.NI % 64 || p.NJ % 64) return (int)hipErrorInvalidValue;
     const int blocks_ij = (p.NI / 64) * (p.NJ / 64);
-    // Five workgroups per CU are resident (32 KB of LDS each, 52 registers): any grid up to 1,280 workgroups is one round; the
-    // split is rounded DOWN so that the M slices never come out shorter than the target (more slices = more fp32 atomics on the
-    // same 64 x 64 output tiles; the kernel is bound by L2 reads of its operands)
-    int msplit = 1024 / blocks_ij;
-    const int maxsplit = (p.M + 63) / 64;
-    if (msplit > maxsplit) msplit = maxsplit;
-    if (msplit < 1) msplit = 1;
-    p.mchunk = (((p.M + msplit - 1) / msplit) + 63) / 64 * 64;
-    msplit = (p.M + p.mchunk - 1) / p.mchunk;
+    const int msplit = tile_split(p.M, blocks_ij, &p.mchunk);
     static const int remap = TUP_ENV_FLAG("TUP_WGRAD_NO_XCD") ? 0 : 1;            // A/B switch
     p.xcd_remap = remap;
-    gemm_wgrad_kernel<PMODE, QMODE><<<dim3(p.NI / 64, p.NJ / 64, msplit), dim3(256), 0, s>>>(p);
-    TUP_CHECK_LAUNCH();
-    return 0;
+    if constexpr (DET) {
+        if (slab == nullptr || p.ldo < p.NJ) return (int)hipErrorInvalidValue;
+        float* out = p.out;
+        float* cs = p.colsum_out;
+        const int ldo = p.ldo;
+        const long long nw = (long long)p.NI * p.NJ;
+        p.slice = nw + p.NI;
+        p.out = slab; p.ldo = p.NJ;
+        p.colsum_out = cs ? slab + nw : nullptr;
+        gemm_wgrad_kernel<PMODE, QMODE, true><<<dim3(p.NI / 64, p.NJ / 64, msplit), dim3(256), 0, s>>>(p);
+        TUP_CHECK_LAUNCH();
+        if (ldo == p.NJ) {
+            const bool joined = cs == out + nw;
+            const int e = tup_slab_reduce(slab, p.slice, msplit, out, joined ? p.slice : nw, 1, s);
+            if (e != 0 || joined || cs == nullptr) return e;
+        } else {
+            // a padded output (no caller in the package): one reduce per output row
+            for (int i = 0; i < p.NI; ++i) {
+                const int e = tup_slab_reduce(slab + (size_t)i * p.NJ, p.slice, msplit, out + (size_t)i * ldo, p.NJ, 1, s);
+                if (e != 0) return e;
+            }
+            if (cs == nullptr) return 0;
+        }
+        return tup_slab_reduce(slab + nw, p.slice, msplit, cs, p.NI, 1, s);
+    } else {
+        gemm_wgrad_kernel<PMODE, QMODE, false><<<dim3(p.NI / 64, p.NJ / 64, msplit), dim3(256), 0, s>>>(p);
+        TUP_CHECK_LAUNCH();
+        return 0;
+    }
+}
+
+void patch_params(WgradParams& p, const void* P, int NI, const void* map, float* out, int B, int H, int W, int reflect)
+{
+    p.H = H; p.W = W; p.Ht = (H + 7) / 8; p.Wt_ = (W + 7) / 8;
+    p.nWy = (p.Ht + 7) / 8; p.nWx = (p.Wt_ + 7) / 8; p.reflect = reflect;
+    p.P = P; p.ldp = NI; p.Q = map; p.out = out; p.ldo = 4096;
+    p.M = B * p.nWy * p.nWx * 64; p.NI = NI; p.NJ = 4096;
+}
+
+template <bool DET>
+int gemm_wgrad_any(const void* P, int p_dtype, int ldp, const void* Q, int q_dtype, int ldq,
+                   float* out, int ldo, float* colsum_out, int M, int NI, int NJ, float* slab, void* stream)
+{
+    WgradParams p{};
+    p.P = P; p.ldp = ldp; p.Q = Q; p.ldq = ldq; p.out = out; p.ldo = ldo; p.M = M; p.NI = NI; p.NJ = NJ;
+    p.colsum_out = colsum_out;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (p_dtype == 0 && q_dtype == 0) return launch<OP_BF16, OP_BF16, DET>(p, s, slab);
+    if (p_dtype == 1 && q_dtype == 0) return launch<OP_F32, OP_BF16, DET>(p, s, slab);
+    if (p_dtype == 0 && q_dtype == 1) return launch<OP_BF16, OP_F32, DET>(p, s, slab);
+    if (p_dtype == 1 && q_dtype == 1) return launch<OP_F32, OP_F32, DET>(p, s, slab);
+    return (int)hipErrorInvalidValue;
+}
+
+template <bool DET>
+int patch_wgrad_any(const float* P, const void* map, float* out, int B, int H, int W, int reflect, float* slab, void* stream)
+{
+    WgradParams p{};
+    patch_params(p, P, 192, map, out, B, H, W, reflect);
+    return launch<OP_F32, OP_PATCH, DET>(p, reinterpret_cast<hipStream_t>(stream), slab);
+}
+
+template <bool DET>
+int rt_patch_wgrad_any(const float* P, const void* map, float* out, int B, int H, int W, float* slab, void* stream)
+{
+    if (H % 8 || W % 8) return (int)hipErrorInvalidValue;
+    WgradParams p{};
+    p.H = H; p.W = W; p.Ht = H / 8; p.Wt_ = W / 8; p.linear = 1; p.reflect = 0;
+    p.P = P; p.ldp = 128; p.Q = map; p.out = out; p.ldo = 4096;
+    p.M = B * p.Ht * p.Wt_; p.NI = 128; p.NJ = 4096;
+    return launch<OP_F32, OP_PATCH, DET>(p, reinterpret_cast<hipStream_t>(stream), slab);
+}
+
+template <bool DET>
+int wt_patch_wgrad_any(const float* P, const void* map, float* out, int B, int H, int W, int NI, float* slab, void* stream)
+{
+    if (NI % 64 || H < 8 || W < 8) return (int)hipErrorInvalidValue;
+    WgradParams p{};
+    p.H = H; p.W = W; p.Ht = H / 8; p.Wt_ = W / 8;
+    p.nWy = (p.Ht + 7) / 8; p.nWx = (p.Wt_ + 7) / 8; p.reflect = 0;
+    p.P = P; p.ldp = NI; p.Q = map; p.out = out; p.ldo = 4096;
+    p.M = B * p.nWy * p.nWx * 64; p.NI = NI; p.NJ = 4096;
+    return launch<OP_F32, OP_PATCH, DET>(p, reinterpret_cast<hipStream_t>(stream), slab);
+}
+
+template <bool DET>
+int colsum_any(const void* G, int dtype, int ld, float* out, int M, int N, const void* rowmask, float* slab, void* stream)
+{
+    if (M <= 0 || N <= 0) return 0;
+    if (N % 64 != 0 || ld % 8 != 0) return (int)hipErrorInvalidValue;
+    static const int forced = TUP_ENV_INT("TUP_COLSUM_BLOCKS", 0);
+    int mchunk;
+    const int msplit = colsum_split(M, N, DET ? 0 : forced, &mchunk);          // DET: the knob would change the slicing
+    dim3 grid(N / 64, msplit);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if constexpr (DET) {
+        if (slab == nullptr) return (int)hipErrorInvalidValue;
+        if (dtype == 1) colsum_kernel<true, true><<<grid, dim3(256), 0, s>>>(G, ld, slab, M, N, mchunk, (const unsigned char*)rowmask);
+        else colsum_kernel<false, true><<<grid, dim3(256), 0, s>>>(G, ld, slab, M, N, mchunk, (const unsigned char*)rowmask);
+        TUP_CHECK_LAUNCH();
+        return tup_slab_reduce(slab, N, msplit, out, N, 1, s);
+    } else {
+        if (dtype == 1) colsum_kernel<true, false><<<grid, dim3(256), 0, s>>>(G, ld, out, M, N, mchunk, (const unsigned char*)rowmask);
+        else colsum_kernel<false, false><<<grid, dim3(256), 0, s>>>(G, ld, out, M, N, mchunk, (const unsigned char*)rowmask);
+        TUP_CHECK_LAUNCH();
+        return 0;
+    }
 }
 
 }  // namespace
@@ -505,27 +682,16 @@ int launch(WgradParams p, hipStream_t s)
 // out[NI][NJ] (fp32, ldo) += P^T Q and, when colsum_out != NULL, colsum_out[NI] += column sums of P (weight and bias
 // gradient of a Linear layer in one pass over grad_out).  p_dtype / q_dtype: 0 = bf16, 1 = fp32.  The caller zeroes both.
 extern "C" int tup_gemm_wgrad_bias(const void* P, int p_dtype, int ldp, const void* Q, int q_dtype, int ldq,
-                                   float* out, int ldo, float* colsum_out, int M, int NI, int NJ, void* stream);
+                                   float* out, int ldo, float* colsum_out, int M, int NI, int NJ, void* stream)
+{
+    return gemm_wgrad_any<false>(P, p_dtype, ldp, Q, q_dtype, ldq, out, ldo, colsum_out, M, NI, NJ, nullptr, stream);
+}
 
 // out[NI][NJ] (fp32, ldo) += P^T Q.  p_dtype / q_dtype: 0 = bf16, 1 = fp32.  The caller zeroes `out`.
 extern "C" int tup_gemm_wgrad(const void* P, int p_dtype, int ldp, const void* Q, int q_dtype, int ldq,
                               float* out, int ldo, int M, int NI, int NJ, void* stream)
 {
-    return tup_gemm_wgrad_bias(P, p_dtype, ldp, Q, q_dtype, ldq, out, ldo, nullptr, M, NI, NJ, stream);
-}
-
-extern "C" int tup_gemm_wgrad_bias(const void* P, int p_dtype, int ldp, const void* Q, int q_dtype, int ldq,
-                                   float* out, int ldo, float* colsum_out, int M, int NI, int NJ, void* stream)
-{
-    WgradParams p{};
-    p.P = P; p.ldp = ldp; p.Q = Q; p.ldq = ldq; p.out = out; p.ldo = ldo; p.M = M; p.NI = NI; p.NJ = NJ;
-    p.colsum_out = colsum_out;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (p_dtype == 0 && q_dtype == 0) return launch<OP_BF16, OP_BF16>(p, s);
-    if (p_dtype == 1 && q_dtype == 0) return launch<OP_F32, OP_BF16>(p, s);
-    if (p_dtype == 0 && q_dtype == 1) return launch<OP_BF16, OP_F32>(p, s);
-    if (p_dtype == 1 && q_dtype == 1) return launch<OP_F32, OP_F32>(p, s);
-    return (int)hipErrorInvalidValue;
+    return gemm_wgrad_any<false>(P, p_dtype, ldp, Q, q_dtype, ldq, out, ldo, nullptr, M, NI, NJ, nullptr, stream);
 }
 
 // out[192][4096] += P^T patches(map): P fp32 [M][192] token rows (window layout), map NHWC bf16
@@ -534,12 +700,7 @@ extern "C" int tup_gemm_wgrad_bias(const void* P, int p_dtype, int ldp, const vo
 extern "C" int tup_patch_wgrad(const float* P, const void* map, float* out, int B, int H, int W,
                                int reflect, void* stream)
 {
-    WgradParams p{};
-    p.H = H; p.W = W; p.Ht = (H + 7) / 8; p.Wt_ = (W + 7) / 8;
-    p.nWy = (p.Ht + 7) / 8; p.nWx = (p.Wt_ + 7) / 8; p.reflect = reflect;
-    p.P = P; p.ldp = 192; p.Q = map; p.out = out; p.ldo = 4096;
-    p.M = B * p.nWy * p.nWx * 64; p.NI = 192; p.NJ = 4096;
-    return launch<OP_F32, OP_PATCH>(p, reinterpret_cast<hipStream_t>(stream));
+    return patch_wgrad_any<false>(P, map, out, B, H, W, reflect, nullptr, stream);
 }
 
 // The same from bf16 token rows (P bf16 [M][192]: the rounding the fp32 form applies on load, done by the caller) on the wide-tile
@@ -547,10 +708,7 @@ extern "C" int tup_patch_wgrad(const float* P, const void* map, float* out, int 
 extern "C" int tup_patch_wgrad_bf16(const void* P, const void* map, float* out, int B, int H, int W, int reflect, void* stream)
 {
     WgradParams p{};
-    p.H = H; p.W = W; p.Ht = (H + 7) / 8; p.Wt_ = (W + 7) / 8;
-    p.nWy = (p.Ht + 7) / 8; p.nWx = (p.Wt_ + 7) / 8; p.reflect = reflect;
-    p.P = P; p.ldp = 192; p.Q = map; p.out = out; p.ldo = 4096;
-    p.M = B * p.nWy * p.nWx * 64; p.NI = 192; p.NJ = 4096;
+    patch_params(p, P, 192, map, out, B, H, W, reflect);
     if ((long long)B * H * W * 128 >= (1LL << 31)) return (int)hipErrorInvalidValue;          // 32-bit pixel offsets in the gather
     static const int form = TUP_ENV_INT("TUP_PATCH_WGRAD_FORM", 0);          // tuning knob (diagnostic build)
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -570,46 +728,83 @@ extern "C" int tup_patch_wgrad_bf16(const void* P, const void* map, float* out, 
 // on the plain token grid (H, W multiples of 8).
 extern "C" int tup_rt_patch_wgrad(const float* P, const void* map, float* out, int B, int H, int W, void* stream)
 {
-    if (H % 8 || W % 8) return (int)hipErrorInvalidValue;
-    WgradParams p{};
-    p.H = H; p.W = W; p.Ht = H / 8; p.Wt_ = W / 8; p.linear = 1; p.reflect = 0;
-    p.P = P; p.ldp = 128; p.Q = map; p.out = out; p.ldo = 4096;
-    p.M = B * p.Ht * p.Wt_; p.NI = 128; p.NJ = 4096;
-    return launch<OP_F32, OP_PATCH>(p, reinterpret_cast<hipStream_t>(stream));
+    return rt_patch_wgrad_any<false>(P, map, out, B, H, W, nullptr, stream);
 }
 
 // WindowTransformer's patch_embed / patch_unembed weights: out[NI][4096] += P^T patches(map), P fp32 [M][NI] token rows in
 // window layout over the floor(H/8) x floor(W/8) token grid (no reflect padding: pixels beyond the grid do not exist).
 extern "C" int tup_wt_patch_wgrad(const float* P, const void* map, float* out, int B, int H, int W, int NI, void* stream)
 {
-    if (NI % 64 || H < 8 || W < 8) return (int)hipErrorInvalidValue;
-    WgradParams p{};
-    p.H = H; p.W = W; p.Ht = H / 8; p.Wt_ = W / 8;
-    p.nWy = (p.Ht + 7) / 8; p.nWx = (p.Wt_ + 7) / 8; p.reflect = 0;
-    p.P = P; p.ldp = NI; p.Q = map; p.out = out; p.ldo = 4096;
-    p.M = B * p.nWy * p.nWx * 64; p.NI = NI; p.NJ = 4096;
-    return launch<OP_F32, OP_PATCH>(p, reinterpret_cast<hipStream_t>(stream));
+    return wt_patch_wgrad_any<false>(P, map, out, B, H, W, NI, nullptr, stream);
 }
 
 // out[N] += column sums of G [M][N] (bias gradients); rowmask (uint8 [M], may be NULL) selects the rows
 // that count (patch_embed's bias does not reach the zero-padded tokens).
 extern "C" int tup_colsum(const void* G, int dtype, int ld, float* out, int M, int N, const void* rowmask, void* stream)
 {
-    if (M <= 0 || N <= 0) return 0;
-    if (N % 64 != 0 || ld % 8 != 0) return (int)hipErrorInvalidValue;
-    // every workgroup ends with 64 float atomics on the same addresses (they serialise in L2): a few hundred workgroups, not thousands
-    // (the 64-column map sums: 2,048 workgroups 106 us, 512 95 us; three column stripes of token rows are flat from 512 to 2,048)
-    static const int forced = TUP_ENV_INT("TUP_COLSUM_BLOCKS", 0);
-    const int target = forced > 0 ? forced : (N == 64 ? 512 : 2048);
-    int msplit = target / (N / 64);
-    if (msplit < 1) msplit = 1;
-    int mchunk = (M + msplit - 1) / msplit;
-    if (mchunk < 256) mchunk = 256;
-    msplit = (M + mchunk - 1) / mchunk;
-    dim3 grid(N / 64, msplit);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == 1) colsum_kernel<true><<<grid, dim3(256), 0, s>>>(G, ld, out, M, N, mchunk, (const unsigned char*)rowmask);
-    else colsum_kernel<false><<<grid, dim3(256), 0, s>>>(G, ld, out, M, N, mchunk, (const unsigned char*)rowmask);
-    TUP_CHECK_LAUNCH();
+    return colsum_any<false>(G, dtype, ld, out, M, N, rowmask, nullptr, stream);
+}
+
+// ---- deterministic forms: the arguments of the atomic twin plus `slab`, an fp32 workspace of tup_wgrad_slab(...) floats (contents
+// ignored).  Every M slice stores its partial result into its own slab slice and tup_slab_reduce adds the slices in order onto the
+// outputs, which the caller zeroed as for the atomic forms. ----
+
+// Slab floats.  kind 0: the 64 x 64-tile GEMM (tup_gemm_wgrad_bias_det, tup_patch_wgrad_det, tup_rt_patch_wgrad_det,
+// tup_wt_patch_wgrad_det; M token rows, out NI x NJ), 1: the wide patch GEMM (tup_patch_wgrad_bf16_det), 2: tup_colsum_det (M rows,
+// N = NI columns, NJ ignored), 3: tup_layernorm_bwd_det / tup_layernorm128_bwd_det (M rows, NI = 192 / 128, NJ ignored).  Host
+// only; 0 for an invalid request.
+extern "C" long long tup_wgrad_slab(int kind, long long M, int NI, int NJ)
+{
+    if (M <= 0 || M > 0x7fffffffLL || NI <= 0) return 0;
+    int mchunk;
+    if (kind == 0) {
+        if (NJ <= 0 || NI % 64 || NJ % 64) return 0;
+        return (long long)tile_split((int)M, (NI / 64) * (NJ / 64), &mchunk) * ((long long)NI * NJ + NI);
+    }
+    if (kind == 1) {
+        if (NJ <= 0 || NI % 192 || NJ % 256) return 0;
+        return (long long)wide_split((int)M, (NI / 192) * (NJ / 256), &mchunk) * ((long long)NI * NJ);
+    }
+    if (kind == 2) {
+        if (NI % 64) return 0;
+        return (long long)colsum_split((int)M, NI, 0, &mchunk) * NI;
+    }
+    if (kind == 3) return (NI == 192 || NI == 128) ? (long long)tup_ln_bwd_det_blocks((int)M) * 2 * NI : 0;
     return 0;
+}
+
+// colsum_out == NULL gives the plain form (tup_gemm_wgrad)
+extern "C" int tup_gemm_wgrad_bias_det(const void* P, int p_dtype, int ldp, const void* Q, int q_dtype, int ldq,
+                                       float* out, int ldo, float* colsum_out, int M, int NI, int NJ, float* slab, void* stream)
+{
+    return gemm_wgrad_any<true>(P, p_dtype, ldp, Q, q_dtype, ldq, out, ldo, colsum_out, M, NI, NJ, slab, stream);
+}
+
+extern "C" int tup_patch_wgrad_det(const float* P, const void* map, float* out, int B, int H, int W, int reflect, float* slab, void* stream)
+{
+    return patch_wgrad_any<true>(P, map, out, B, H, W, reflect, slab, stream);
+}
+
+// always the product tile (192 x 256, 2 stages, 8 waves): TUP_PATCH_WGRAD_FORM would change the slicing
+extern "C" int tup_patch_wgrad_bf16_det(const void* P, const void* map, float* out, int B, int H, int W, int reflect, float* slab, void* stream)
+{
+    WgradParams p{};
+    patch_params(p, P, 192, map, out, B, H, W, reflect);
+    if ((long long)B * H * W * 128 >= (1LL << 31)) return (int)hipErrorInvalidValue;
+    return launch_wide<4, 2, true, 8, true>(p, reinterpret_cast<hipStream_t>(stream), slab);
+}
+
+extern "C" int tup_rt_patch_wgrad_det(const float* P, const void* map, float* out, int B, int H, int W, float* slab, void* stream)
+{
+    return rt_patch_wgrad_any<true>(P, map, out, B, H, W, slab, stream);
+}
+
+extern "C" int tup_wt_patch_wgrad_det(const float* P, const void* map, float* out, int B, int H, int W, int NI, float* slab, void* stream)
+{
+    return wt_patch_wgrad_any<true>(P, map, out, B, H, W, NI, slab, stream);
+}
+
+extern "C" int tup_colsum_det(const void* G, int dtype, int ld, float* out, int M, int N, const void* rowmask, float* slab, void* stream)
+{
+    return colsum_any<true>(G, dtype, ld, out, M, N, rowmask, slab, stream);
 }

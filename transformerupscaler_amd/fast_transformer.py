@@ -182,7 +182,8 @@ class TransformerModel(nn.Module):
             nb = len(self.window_blocks)
             frags_t = [ops.relpos_bias_expand(pk[f"b{i}.table"]) for i in range(nb)]
             frags_n = [ops.relpos_bias_expand_n(pk[f"b{i}.table"]) for i in range(nb)] if backward else None
-            if backward and compose_branch_a_in_training:
+            # (not in deterministic mode: forward_train takes the explicit branch A there and would not read the composition)
+            if backward and compose_branch_a_in_training and not ops.deterministic_enabled():
                 from .weights import upsampler_layout as _layout
                 idx, r = _layout(scale)[-1]
                 if r == 2:         # training: last Upsampler stage + up1_conv as one composed conv (csrc/branch_a_train.hip)

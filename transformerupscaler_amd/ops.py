@@ -6,6 +6,7 @@ on the caller's current HIP stream.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import numpy as np
@@ -525,6 +526,12 @@ def gemm_wgrad(p, q, out=None):
     assert q.shape[0] == M and NI % 64 == 0 and NJ % 64 == 0
     if out is None:
         out = _zeros((NI, NJ), p.device)
+    if deterministic_enabled():
+        slab = _det_slab(wgrad_slab_floats(0, M, NI, NJ), p.device)
+        _lib.call("tup_gemm_wgrad_bias_det", _chk(p, p.dtype, None, "p"), {BF16: 0, F32: 1}[p.dtype], NI,
+                  _chk(q, q.dtype, None, "q"), {BF16: 0, F32: 1}[q.dtype], NJ, _chk(out, F32, (NI, NJ), "out"), NJ, None,
+                  M, NI, NJ, slab.data_ptr(), _stream())
+        return out
     _lib.call("tup_gemm_wgrad", _chk(p, p.dtype, None, "p"), {BF16: 0, F32: 1}[p.dtype], NI,
               _chk(q, q.dtype, None, "q"), {BF16: 0, F32: 1}[q.dtype], NJ, _chk(out, F32, (NI, NJ), "out"), NJ,
               M, NI, NJ, _stream())
@@ -538,6 +545,13 @@ def gemm_wgrad_bias(p, q):
     assert q.shape[0] == M and NI % 64 == 0 and NJ % 64 == 0
     out = _zeros((NI, NJ), p.device)
     db = _zeros((NI,), p.device)
+    if deterministic_enabled():
+        # (out and db are neighbours in the zero pool: the entry then adds weight and bias slices in one reduce launch)
+        slab = _det_slab(wgrad_slab_floats(0, M, NI, NJ), p.device)
+        _lib.call("tup_gemm_wgrad_bias_det", _chk(p, p.dtype, None, "p"), {BF16: 0, F32: 1}[p.dtype], NI,
+                  _chk(q, q.dtype, None, "q"), {BF16: 0, F32: 1}[q.dtype], NJ, out.data_ptr(), NJ, db.data_ptr(),
+                  M, NI, NJ, slab.data_ptr(), _stream())
+        return out, db
     _lib.call("tup_gemm_wgrad_bias", _chk(p, p.dtype, None, "p"), {BF16: 0, F32: 1}[p.dtype], NI,
               _chk(q, q.dtype, None, "q"), {BF16: 0, F32: 1}[q.dtype], NJ, out.data_ptr(), NJ, db.data_ptr(),
               M, NI, NJ, _stream())
@@ -551,11 +565,23 @@ def patch_wgrad(p, fmap, reflect):
     B, H, W, C = fmap.shape
     _, _, nwy, nwx = window_geometry(H, W)
     out = _zeros((192, 4096), p.device)
+    M = B * nwy * nwx * 64
+    det = deterministic_enabled()
     if PATCH_WGRAD_WIDE and B * H * W * 128 < 2 ** 31:
         # bf16 token rows (the rounding the fp32 entry applies on load): the wide kernel fetches its operands by DMA
         _chk(p, F32, (B * nwy * nwx * 64, 192), "p")
         pb = p.to(BF16)
+        if det:
+            slab = _det_slab(wgrad_slab_floats(1, M, 192, 4096), p.device)
+            _lib.call("tup_patch_wgrad_bf16_det", pb.data_ptr(), _chk(fmap, BF16, None, "map"), out.data_ptr(), B, H, W, int(reflect),
+                      slab.data_ptr(), _stream())
+            return out
         _lib.call("tup_patch_wgrad_bf16", pb.data_ptr(), _chk(fmap, BF16, None, "map"), out.data_ptr(), B, H, W, int(reflect), _stream())
+        return out
+    if det:
+        slab = _det_slab(wgrad_slab_floats(0, M, 192, 4096), p.device)
+        _lib.call("tup_patch_wgrad_det", _chk(p, F32, (M, 192), "p"), _chk(fmap, BF16, None, "map"),
+                  out.data_ptr(), B, H, W, int(reflect), slab.data_ptr(), _stream())
         return out
     _lib.call("tup_patch_wgrad", _chk(p, F32, (B * nwy * nwx * 64, 192), "p"), _chk(fmap, BF16, None, "map"),
               out.data_ptr(), B, H, W, int(reflect), _stream())
@@ -566,6 +592,11 @@ def colsum(g, out=None, rowmask=None):
     M, N = g.shape
     if out is None:
         out = _zeros((N,), g.device)
+    if deterministic_enabled():
+        slab = _det_slab(wgrad_slab_floats(2, M, N), g.device)
+        _lib.call("tup_colsum_det", _chk(g, g.dtype, None, "g"), {BF16: 0, F32: 1}[g.dtype], N, _chk(out, F32, (N,), "out"),
+                  M, N, _opt(rowmask, torch.uint8, (M,), "rowmask"), slab.data_ptr(), _stream())
+        return out
     _lib.call("tup_colsum", _chk(g, g.dtype, None, "g"), {BF16: 0, F32: 1}[g.dtype], N, _chk(out, F32, (N,), "out"),
               M, N, _opt(rowmask, torch.uint8, (M,), "rowmask"), _stream())
     return out
@@ -578,6 +609,13 @@ def layernorm_bwd(gy, x, mean, rstd, gamma, gres=None, drop=None):
     dg = _zeros((192,), x.device)
     db = _zeros((192,), x.device)
     gd = torch.empty((M, 192), dtype=BF16, device=x.device) if drop else None
+    if deterministic_enabled():
+        slab = _det_slab(wgrad_slab_floats(3, M, 192), x.device)
+        _lib.call("tup_layernorm_bwd_det", _chk(gy, BF16, (M, 192), "gy"), _chk(x, F32, (M, 192), "x"), _chk(mean, F32, (M,), "mean"),
+                  _chk(rstd, F32, (M,), "rstd"), _chk(gamma, F32, (192,), "gamma"), _opt(gres, F32, (M, 192), "gres"),
+                  dx.data_ptr(), dg.data_ptr(), db.data_ptr(), M, gd.data_ptr() if drop else None,
+                  float(drop[0]) if drop else 0.0, (int(drop[1]) & 0xFFFFFFFF) if drop else 0, slab.data_ptr(), _stream())
+        return (dx, dg, db, gd) if drop else (dx, dg, db)
     _lib.call("tup_layernorm_bwd", _chk(gy, BF16, (M, 192), "gy"), _chk(x, F32, (M, 192), "x"), _chk(mean, F32, (M,), "mean"),
               _chk(rstd, F32, (M,), "rstd"), _chk(gamma, F32, (192,), "gamma"), _opt(gres, F32, (M, 192), "gres"),
               dx.data_ptr(), dg.data_ptr(), db.data_ptr(), M, gd.data_ptr() if drop else None,
@@ -650,16 +688,63 @@ def patch_embed_bwd_merge(gx, wt, add1, add2, relu_src, want_add1_colsum=False):
     return (out, cs.sum(0)) if want_add1_colsum else out
 
 
-# ---- deterministic forms: the weight-gradient convs below have *_det forms without float atomics (a slab of per-workgroup partial
-# sums, added in a fixed order), bitwise reproducible from run to run.  The other weight-gradient reductions of the backward still
-# use atomics, so a training step is not reproducible yet: the mode is explicit-only and does not follow
-# torch.use_deterministic_algorithms until every site has a deterministic form. ----
-deterministic = False            # A/B attribute: True routes the weight-gradient convs to their deterministic forms
+# ---- deterministic mode: every order-dependent reduction of the three plugins' backward has a *_det form without float atomics
+# (a slab of per-work-item partial sums, added in a fixed order: the weight-gradient convs below, the weight-gradient GEMMs, the
+# column sums and the LayerNorm backward above) or is routed around (the composed branch A and the patch_unembed bias sums riding
+# in patch_embed_bwd_merge have no such form: autograd.py takes the explicit stage convs and ops.colsum instead).  With the
+# switch on, a training step is bitwise reproducible from run to run (INTEGRATION.md states the guarantee).  The switch is
+# explicit: it does not follow torch.use_deterministic_algorithms.  Set it BEFORE the forward of a step: the branch-A route is
+# chosen in forward_train and the backward follows the forward that produced its saved state. ----
+deterministic = False            # True routes the reductions of the backward to their deterministic forms
 
 
 def deterministic_enabled():
     """Whether the wrappers take the deterministic forms now (read at call time)."""
     return bool(deterministic)
+
+
+@contextlib.contextmanager
+def deterministic_mode(enabled=True):
+    """Sets ops.deterministic for the duration of the block (forward AND backward of the steps inside it) and restores the
+    previous value afterwards, also when the block raises."""
+    global deterministic
+    previous = deterministic
+    deterministic = bool(enabled)
+    try:
+        yield
+    finally:
+        deterministic = previous
+
+
+def wgrad_slab_floats(kind, M, NI, NJ=0):
+    """fp32 slab size of the deterministic token-path reductions (kind 0 = 64 x 64-tile GEMM, 1 = wide patch GEMM, 2 = column sums
+    over NI columns, 3 = LayerNorm backward of NI-wide rows).  Host only (tup_wgrad_slab returns the count, not an error code)."""
+    n = int(_lib.load().tup_wgrad_slab(int(kind), int(M), int(NI), int(NJ)))
+    if n <= 0:
+        raise ValueError(f"tup_wgrad_slab({kind}, {M}, {NI}, {NJ}): invalid request")
+    return n
+
+
+# One slab per device and stream, grown to the largest request and reused: the kernels of a backward run in stream order, and a
+# deterministic entry is done with its slab when its reduce launch has run.  (A slab per call would be ~40 allocations of up to
+# 50 MB per step.)  Replacing a slab by a larger one while kernels that use the old one are still queued is safe only because the
+# slab is allocated on, and used on, the same (current) stream: the caching allocator hands the old block out again in stream
+# order.  The cache never shrinks; release_det_slabs() returns the memory (call it also before destroying a side stream that ran
+# deterministic steps, so that a later stream with a recycled handle does not inherit its slab).
+_det_slabs = {}
+
+
+def _det_slab(n, device):
+    key = (_cur_dev(), _stream())
+    slab = _det_slabs.get(key)
+    if slab is None or slab.numel() < n:
+        _det_slabs.pop(key, None)
+        slab = _det_slabs[key] = torch.empty((n,), dtype=F32, device=device)
+    return slab
+
+
+def release_det_slabs():
+    _det_slabs.clear()
 
 
 def conv_wgrad_slab_floats(kind, B, H, W, r=1):
@@ -867,6 +952,13 @@ def layernorm128_bwd(gy, x, mean, rstd, gamma, gres=None, drop=None):
     dg = _zeros((128,), x.device)
     db = _zeros((128,), x.device)
     gd = torch.empty((M, 128), dtype=BF16, device=x.device) if drop else None
+    if deterministic_enabled():
+        slab = _det_slab(wgrad_slab_floats(3, M, 128), x.device)
+        _lib.call("tup_layernorm128_bwd_det", _chk(gy, BF16, (M, 128), "gy"), _chk(x, F32, (M, 128), "x"), _chk(mean, F32, (M,), "mean"),
+                  _chk(rstd, F32, (M,), "rstd"), _chk(gamma, F32, (128,), "gamma"), _opt(gres, F32, (M, 128), "gres"),
+                  dx.data_ptr(), dg.data_ptr(), db.data_ptr(), M, gd.data_ptr() if drop else None,
+                  float(drop[0]) if drop else 0.0, (int(drop[1]) & 0xFFFFFFFF) if drop else 0, slab.data_ptr(), _stream())
+        return (dx, dg, db, gd) if drop else (dx, dg, db)
     _lib.call("tup_layernorm128_bwd", _chk(gy, BF16, (M, 128), "gy"), _chk(x, F32, (M, 128), "x"), _chk(mean, F32, (M,), "mean"),
               _chk(rstd, F32, (M,), "rstd"), _chk(gamma, F32, (128,), "gamma"), _opt(gres, F32, (M, 128), "gres"),
               dx.data_ptr(), dg.data_ptr(), db.data_ptr(), M, gd.data_ptr() if drop else None,
@@ -878,6 +970,12 @@ def rt_patch_wgrad(p, fmap):
     """fp32 [128][4096] = p^T patches(fmap); p fp32 [B*T][128] (plain token grid), fmap NHWC bf16."""
     B, H, W, C = fmap.shape
     out = _zeros((128, 4096), p.device)
+    if deterministic_enabled():
+        M = B * (H // 8) * (W // 8)
+        slab = _det_slab(wgrad_slab_floats(0, M, 128, 4096), p.device)
+        _lib.call("tup_rt_patch_wgrad_det", _chk(p, F32, (M, 128), "p"), _chk(fmap, BF16, None, "map"),
+                  out.data_ptr(), B, H, W, slab.data_ptr(), _stream())
+        return out
     _lib.call("tup_rt_patch_wgrad", _chk(p, F32, (B * (H // 8) * (W // 8), 128), "p"), _chk(fmap, BF16, None, "map"),
               out.data_ptr(), B, H, W, _stream())
     return out
@@ -1222,6 +1320,12 @@ def wt_patch_wgrad(p, fmap):
     B, H, W, C = fmap.shape
     NI = p.shape[1]
     out = _zeros((NI, 4096), p.device)
+    if deterministic_enabled():
+        M = B * ((H // 8 + 7) // 8) * ((W // 8 + 7) // 8) * 64
+        slab = _det_slab(wgrad_slab_floats(0, M, NI, 4096), p.device)
+        _lib.call("tup_wt_patch_wgrad_det", _chk(p, F32, (M, NI), "p"), _chk(fmap, BF16, None, "map"), out.data_ptr(), B, H, W, NI,
+                  slab.data_ptr(), _stream())
+        return out
     _lib.call("tup_wt_patch_wgrad", _chk(p, F32, None, "p"), _chk(fmap, BF16, None, "map"), out.data_ptr(), B, H, W, NI, _stream())
     return out
 
