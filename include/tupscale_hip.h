@@ -507,6 +507,21 @@ int tup_quality_u8hwc_partial(const void* a, const void* b, double* partial, int
  * image's result does not depend on the run or on the other images of the batch. */
 int tup_quality_reduce(const double* partial, double* out, int B, int H, int W, int nparts, float data_range, void* stream);
 
+/* ---- training loss on the scored quantities (transformerupscaler_amd/losses.py; csrc/quality_loss.hip) ----
+ * loss = w_l1 * mean|x - y| + w_mse * mean (x - y)^2 + w_ssim * (1 - mean_b SSIM(x[b], y[b])), x, y fp32 planar [B][3][H][W],
+ * SSIM as tup_quality_f32_partial defines it. */
+
+/* out[0] (fp32, device) = the loss, from qpartial = the partials of tup_quality_f32_partial (read when w_mse or w_ssim != 0, else
+ * may be NULL) and l1partial = the nl1 partials of tup_l1_loss_partial over the whole batch (read when w_l1 != 0, else may be NULL).
+ * One workgroup: an image's slots are added as tup_quality_reduce adds them, then the images in index order, in fp64; no atomics. */
+int tup_quality_loss_reduce(const double* qpartial, const float* l1partial, float* out, int B, int H, int W, int nparts, int nl1,
+                            float w_l1, float w_mse, float w_ssim, void* stream);
+/* grad (fp32 [B][3][H][W]) = gscalar[0] * d loss / d x  (gscalar: the upstream scalar gradient, on the device).  One streaming
+ * pass (x and y read ~1.18 times, grad written once), no workspace, no atomics: a pixel's gradient depends on its own plane only.
+ * With w_ssim == 0 an elementwise kernel runs instead.  H, W >= 7. */
+int tup_quality_loss_f32_bwd(const float* x, const float* y, const float* gscalar, float* grad, int B, int H, int W,
+                             float w_l1, float w_mse, float w_ssim, float data_range, void* stream);
+
 /* nblk (<= 8) consecutive WindowTransformerBlocks in ONE launch (the loop `for block in self.window_blocks`, model.py:288-289), with
  * the default kernel's geometry (two waves per window, two workgroups per CU): between blocks the residual stream passes through
  * memory as each wave's own stores followed by its own loads (L2), so the launch boundaries and their chip-wide load / store bursts

@@ -82,6 +82,9 @@ SIGNATURES = {
     "tup_quality_f32_partial": [P, P, P, I, I, I, I, F, P],
     "tup_quality_u8hwc_partial": [P, P, P, I, I, I, I, F, P],
     "tup_quality_reduce": [P, P, I, I, I, I, F, P],
+    # training loss on the scored quantities (csrc/quality_loss.hip)
+    "tup_quality_loss_reduce": [P, P, P, I, I, I, I, I, F, F, F, P],
+    "tup_quality_loss_f32_bwd": [P, P, P, P, I, I, I, F, F, F, F, P],
     # backward
     "tup_gemm_wgrad": [P, I, I, P, I, I, P, I, I, I, I, P],
     "tup_gemm_wgrad_bias": [P, I, I, P, I, I, P, I, P, I, I, I, P],

@@ -39,6 +39,9 @@ GUARDED = [
     ("gemm_wgrad.hip", ["gemm_wgrad_kernelILi0ELi0ELb1E", "gemm_wgrad_kernelILi0ELi1ELb1E", "gemm_wgrad_kernelILi1ELi0ELb1E",
                         "gemm_wgrad_kernelILi1ELi1ELb1E", "gemm_wgrad_kernelILi1ELi2ELb1E", "colsum_kernelILb0ELb1E", "colsum_kernelILb1ELb1E"]),
     ("attention_bwd.hip", ["layernorm_bwd_kernelILi2ELb1E", "layernorm_bwd_kernelILi3ELb1E"]),
+    # no counted hand-off: four register rings (7 rows of 5 moment sums, of 3 coefficient sums, of x and y) indexed by the unrolled
+    # row loop; a build that indexes them dynamically puts them in scratch
+    ("quality_loss.hip", ["quality_loss_bwd_kernel"]),
 ]
 # diagnostic template instantiations, never launched by the product path: fused_qkv_attn_kernel<PROJ, MLP, STAMPS = true>, the
 # timing ablations fused_mlp_v2_kernel<ABL != 0>

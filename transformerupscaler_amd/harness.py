@@ -1,7 +1,8 @@
 """Training-step harness with the semantics of the reference loop (train.py:110-146): zero_grad,
 forward with ``res_out = HR size, require_ratio=False``, antialiased Resize to the HR size when shapes
 differ, L1 loss, backward, Adam step.  Equal-shaped samples are batched (the reference loops over
-samples at B=1; mean of per-sample L1 means == batch L1 mean for equal shapes)."""
+samples at B=1; mean of per-sample L1 means == batch L1 mean for equal shapes).
+``train_step(..., loss=losses.QualityLoss(...))`` trains on another criterion (L1 / MSE / SSIM mix) in the L1 loss's place."""
 from __future__ import annotations
 
 import os
@@ -23,12 +24,16 @@ def make_optimizer(model, lr: float = 1e-4):
     return Adam(model.parameters(), lr=lr)
 
 
-def train_step(model, optimizer, lr_batch: torch.Tensor, hr_batch: torch.Tensor) -> torch.Tensor:
+def train_step(model, optimizer, lr_batch: torch.Tensor, hr_batch: torch.Tensor, loss=None) -> torch.Tensor:
+    """`loss`: None = the reference's nn.L1Loss; or a callable ``loss(out, target) -> scalar`` (losses.QualityLoss) used in its place."""
     optimizer.zero_grad(set_to_none=True)                                    # train.py:113
     out = model(lr_batch, res_out=tuple(hr_batch.shape[2:]), require_ratio=False)      # train.py:124
     if tuple(out.shape[2:]) != tuple(hr_batch.shape[2:]):
         out = resize_aa(out, tuple(hr_batch.shape[2:]))                      # train.py:127-130
-    loss = l1_loss(out, hr_batch, fuse_into_model_backward=True)             # train.py:103,132,136 (HIP forward + backward; `out` feeds nothing else)
+    if loss is None:
+        loss = l1_loss(out, hr_batch, fuse_into_model_backward=True)         # train.py:103,132,136 (HIP forward + backward; `out` feeds nothing else)
+    else:
+        loss = loss(out, hr_batch)
     loss.backward()                                                          # train.py:138 (bf16 needs no GradScaler)
     optimizer.step()                                                         # train.py:139
     return loss.detach()
