@@ -550,6 +550,13 @@ int tup_pack_gather(const void* src, const int* offs, int nparam, const int* map
  * (segment index, first element), one workgroup per 4096 elements.  p, m, v are updated in place. */
 int tup_adam_step(const void* segs, const int* chunks, int nchunks, void* stream);
 
+/* Gradient accumulation of a mixed-scale step (reference train.py:119-138: several samples, one optimizer step) for all parameters of
+ * one backward in one launch.  segs: device array [nseg] of 32-byte records {float* dst; const float* src; long long n; float alpha;
+ * int mode}; mode 0: dst = alpha * src, 1: dst = dst + alpha * src (alpha * src rounded first: with alpha == 1 a plain fp32 add),
+ * 2: dst = 0 (src ignored, may be NULL); chunks: device int [nchunks][2] = (segment index, first element), one workgroup per 4096
+ * elements.  16-byte accesses where dst and src are 16-byte aligned, scalar otherwise.  Segments must not overlap; no atomics. */
+int tup_grad_accumulate(const void* segs, const int* chunks, int nchunks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,195 @@
+#!/usr/bin/env python
+"""Training driver with the reference's train.py surface (train.py:41-194): the model plugin ``models/<model>/model.py`` is
+trained on the samples of ``--data_dir`` with L1 loss and Adam, resumed from and checkpointed to
+``models/<model>/checkpoints/model_epoch_<N>.pth``.
+
+    python train.py --data_dir images/training_set --model FastTransformer --epochs 10
+    torchrun --nproc_per_node 8 train.py --data_dir images/training_set            # data parallel, one process per GPU
+
+A step is the reference's (train.py:110-146): a batch is a list of (lr, hr) samples of different sizes and scales
+(``transformerupscaler_amd.data.PairDataset``: ten scale pairs per image resolving to x2, x3, x4 and x6), each sample counts
+equally in the loss, and one optimizer step follows.  It runs as ``harness.train_step_samples``: equal-shaped samples of a batch
+are batched (``--no_group`` runs them one by one as the reference does), each group's backward runs at once, and the gradients
+are accumulated in one launch per backward.
+
+What differs from the reference driver:
+
+* ``--data_dir`` is required.  The reference's online dataset is not built; nothing here touches a network.
+* ``--model`` defaults to ``FastTransformer`` (the reference's default names a model its own tree does not have).
+* Images are decoded once on the host and resized on the GPU: no DataLoader worker processes.  The path computes in bf16 inside
+  with fp32 parameters: no autocast, no GradScaler.
+* The loss is read back only when a line is printed and at the end of an epoch.
+* ``--l1 / --mse / --ssim`` weights train on ``losses.QualityLoss`` instead of pure L1; ``--deterministic`` makes the run
+  bit-reproducible (``ops.deterministic_mode``); ``--seed`` seeds the shuffle and dropout; ``--max_steps`` ends the run early (a
+  checkpoint of the unfinished epoch is still written); ``--pairs "96x96:192x192,..."`` replaces the scale-pair table;
+  ``--cache_gb`` bounds the decoded-image cache; ``--save_optimizer`` writes Adam's state beside the weights and resumes from
+  it; ``--json PATH`` writes a record of the run.
+* ``--traceback`` is accepted; the reference's traceback window is not available here.
+* With ``WORLD_SIZE > 1`` in the environment (torchrun) the run is data parallel: every rank shuffles with the same seed and
+  trains ``batch[rank::world]``; the gradients of a step are all-reduced once.
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Train the TransformerModel for image upscaling")
+    p.add_argument("--data_dir", type=str, default=None, help="Directory containing the training images (.png); required")
+    p.add_argument("--batch_size", type=int, default=6, help="Samples per optimizer step")
+    p.add_argument("--epochs", type=int, default=10, help="Number of training epochs")
+    p.add_argument("--lr", type=float, default=1e-4, help="Learning rate of Adam")
+    p.add_argument("--log_interval", type=int, default=1, help="Log the loss every N steps")
+    p.add_argument("--checkpoint_interval", type=int, default=1, help="Save a checkpoint every N epochs")
+    p.add_argument("--model", type=str, default="FastTransformer", help="Model name (models/{model}/model.py)")
+    p.add_argument("--checkpoint_dir", type=str, default=None, help="Checkpoint directory (default: models/{model}/checkpoints/)")
+    p.add_argument("--traceback", action="store_true", help="Accepted for compatibility; the traceback window is not available")
+    p.add_argument("--l1", type=float, default=1.0, help="Weight of the L1 term of the loss")
+    p.add_argument("--mse", type=float, default=0.0, help="Weight of the MSE term of the loss")
+    p.add_argument("--ssim", type=float, default=0.0, help="Weight of the (1 - SSIM) term of the loss")
+    p.add_argument("--deterministic", action="store_true", help="Bit-reproducible training (ops.deterministic_mode)")
+    p.add_argument("--seed", type=int, default=0, help="Seed of the shuffle and of dropout")
+    p.add_argument("--max_steps", type=int, default=None, help="Stop after this many optimizer steps of this invocation")
+    p.add_argument("--pairs", type=str, default=None, help='Scale pairs "LRHxLRW:HRHxHRW,..." in place of the dataset\'s ten')
+    p.add_argument("--cache_gb", type=float, default=2.0, help="Bound of the decoded-image cache on the GPU, in GiB")
+    p.add_argument("--save_optimizer", action="store_true", help="Write / resume Adam's state beside the weights")
+    p.add_argument("--no_group", action="store_true", help="Run every sample at batch 1, as the reference does")
+    p.add_argument("--json", type=str, default=None, help="Write a record of the run to this path")
+    return p
+
+
+def pure_l1(args):
+    return args.l1 == 1.0 and args.mse == 0.0 and args.ssim == 0.0
+
+
+def epoch_batches(n_samples, batch_size, generator):
+    """The shuffled batches of one epoch (index lists); a last partial batch is kept (DataLoader's drop_last=False)."""
+    import torch
+    order = torch.randperm(n_samples, generator=generator).tolist()
+    return [order[i:i + batch_size] for i in range(0, n_samples, batch_size)]
+
+
+def run(args):
+    if not args.data_dir:
+        sys.exit("train.py: --data_dir is required (a directory of .png images); the reference's online dataset is not built")
+    if args.batch_size < 1:
+        sys.exit("train.py: --batch_size must be >= 1")
+    import torch
+
+    from transformerupscaler_amd import harness, ops
+    from transformerupscaler_amd.data import SCALE_PAIRS, PairDataset, parse_pairs
+
+    if args.checkpoint_dir is None:
+        args.checkpoint_dir = os.path.join("models", args.model, "checkpoints")
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = 0
+    if world > 1:
+        import torch.distributed as dist
+        torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
+        dist.init_process_group("nccl")
+        rank = dist.get_rank()
+    device = torch.device("cuda", torch.cuda.current_device())
+    say = print if rank == 0 else (lambda *a, **k: None)
+    say(f"Training on device: {device}" + (f" ({world} ranks)" if world > 1 else ""))
+    if args.traceback:
+        say("--traceback: the traceback window is not available in this build; continuing without it")
+
+    torch.manual_seed(args.seed)
+    model = importlib.import_module(f"models.{args.model}.model").TransformerModel()
+    if not any(p.requires_grad for p in model.parameters()):
+        sys.exit(f"train.py: model {args.model} has no trainable parameter; there is nothing to train")
+    model = model.to(device)
+    optimizer = harness.make_optimizer(model, lr=args.lr)
+    epochs_trained = harness.load_latest_checkpoint(model, args.checkpoint_dir, optimizer if args.save_optimizer else None,
+                                                    map_location=device)
+    if epochs_trained:
+        say(f"Resuming from epoch {epochs_trained} of {args.checkpoint_dir}")
+        if epochs_trained >= args.epochs:
+            sys.exit(f"train.py: the latest checkpoint in {args.checkpoint_dir} is of epoch {epochs_trained}, "
+                     f"which is not below --epochs {args.epochs}")
+    else:
+        say(f"No checkpoint in {args.checkpoint_dir}: starting from the initial weights")
+
+    dp = None
+    if world > 1:
+        from transformerupscaler_amd.dp import DataParallel
+        from transformerupscaler_amd.weights import VALID_SCALES
+        if args.model == "FastTransformer":
+            dp = DataParallel(model, scales=tuple(VALID_SCALES))          # (2, 3, 4, 6): a step may use any of them
+        else:
+            dp = DataParallel(model)                                      # every parameter is active in every step
+
+    pairs = parse_pairs(args.pairs) if args.pairs else SCALE_PAIRS
+    dataset = PairDataset(args.data_dir, pairs, cache_bytes=int(args.cache_gb * (1 << 30)), device=device)
+    criterion = None
+    if not pure_l1(args):
+        from transformerupscaler_amd.losses import QualityLoss
+        criterion = QualityLoss(l1=args.l1, mse=args.mse, ssim=args.ssim)
+    say(f"{len(dataset)} samples from {len(dataset.files)} images, {len(pairs)} scale pairs; loss "
+        f"{'L1' if criterion is None else criterion}")
+
+    shuffle = torch.Generator().manual_seed(args.seed)
+    for _ in range(epochs_trained):                                       # a resumed run continues the shuffle sequence
+        torch.randperm(len(dataset), generator=shuffle)
+    record = {"model": args.model, "world": world, "samples": len(dataset), "resumed_from_epoch": epochs_trained,
+              "steps": [], "epochs": [], "checkpoints": []}
+    steps_done = 0
+    stop = False
+    model.train()
+    with ops.deterministic_mode(args.deterministic):
+        for epoch in range(epochs_trained, args.epochs):
+            batches = epoch_batches(len(dataset), args.batch_size, shuffle)
+            losses = []                                                   # device scalars: read back when printed / at epoch end
+            for step, batch in enumerate(batches):
+                mine = batch[rank::world]
+                samples = [dataset[i] for i in mine]
+                loss = harness.train_step_samples(model, optimizer, [s[0] for s in samples], [s[1] for s in samples],
+                                                  loss=criterion, group=not args.no_group, b_global=len(batch))
+                if world > 1:                                             # ranks hold their share / world of the step's mean loss
+                    loss = loss.clone()
+                    torch.distributed.all_reduce(loss)
+                    loss = loss / world
+                losses.append(loss)
+                steps_done += 1
+                if step % args.log_interval == 0:
+                    value = loss.item()
+                    say(f"Epoch [{epoch + 1}/{args.epochs}] Step [{step + 1}/{len(batches)}] Loss: {value:.6f}")
+                    record["steps"].append({"epoch": epoch + 1, "step": step + 1, "loss": value})
+                if args.max_steps is not None and steps_done >= args.max_steps:
+                    stop = True
+                    break
+            avg = torch.stack(losses).mean().item()
+            say(f"Epoch [{epoch + 1}/{args.epochs}] completed. Average Loss: {avg:.6f}")
+            record["epochs"].append({"epoch": epoch + 1, "steps": len(losses), "average_loss": avg})
+            if (epoch + 1) % args.checkpoint_interval == 0 or stop:
+                if rank == 0:
+                    path = harness.save_checkpoint(model, args.checkpoint_dir, epoch + 1, optimizer if args.save_optimizer else None)
+                    say(f"Saved checkpoint: {path}")
+                    record["checkpoints"].append(path)
+            if stop:
+                break
+    say("Training complete!" if not stop else f"Stopped after {steps_done} steps (--max_steps).")
+    if dp is not None:
+        dp.detach()
+        torch.distributed.barrier()
+        torch.distributed.destroy_process_group()
+    return record
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    record = run(args)
+    if args.json and int(os.environ.get("RANK", "0")) == 0:
+        with open(args.json, "w") as f:
+            json.dump(record, f, indent=1)
+    return record
+
+
+if __name__ == "__main__":
+    main()

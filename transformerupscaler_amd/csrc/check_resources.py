@@ -42,6 +42,8 @@ GUARDED = [
     # no counted hand-off: four register rings (7 rows of 5 moment sums, of 3 coefficient sums, of x and y) indexed by the unrolled
     # row loop; a build that indexes them dynamically puts them in scratch
     ("quality_loss.hip", ["quality_loss_bwd_kernel"]),
+    # no counted hand-off: a streaming kernel at 12 B per element; scratch traffic would be a large share of what it moves
+    ("grad_accumulate.hip", ["grad_accumulate_kernel"]),
 ]
 # diagnostic template instantiations, never launched by the product path: fused_qkv_attn_kernel<PROJ, MLP, STAMPS = true>, the
 # timing ablations fused_mlp_v2_kernel<ABL != 0>

@@ -24,6 +24,9 @@ Two layouts:
 One backward node = one begin() / on_ready()... / finish() episode; with train.py's per-sample loop
 (several forwards, one ``loss.backward()``) every sample's node runs its own episode, so all ranks must
 run the same number of forward calls per step.
+
+``harness.train_step_samples`` does not use the episodes: it accumulates the gradients of a whole step in one arena
+(accumulate.GradAccumulator) and reduces it ONCE through ``reduce_flat``, so ranks may run different numbers of forwards.
 """
 from __future__ import annotations
 
@@ -249,6 +252,57 @@ class GradReducer:
         out = {n: self.flat[self.offset[n]:self.offset[n] + self.numel[n]].view(self.shapes[n]) for n in have}
         self._in_step, self._active = False, None
         return out
+
+    # ---- per-step reduction of a gradient arena (accumulate.GradAccumulator); independent of the episode API above ----
+    def reduce_flat(self, flat: torch.Tensor, touched: Iterable[str]) -> List[str]:
+        """All-reduce `flat` (fp32, this reducer's layout, segments this rank did not produce zeroed) ONCE: the buckets in index
+        order on the comm stream, the ranks' touched-parameter masks ORed on the host, the sum scaled by 1 / world.  Returns the
+        names some rank touched, in layout order.  Collective: every rank calls it once per step, whatever it ran before."""
+        if self._in_step:
+            raise RuntimeError("GradReducer.reduce_flat() called while a backward episode is open")
+        if flat.dtype != torch.float32 or flat.numel() < self.total_floats or flat.device != self.device or not flat.is_contiguous():
+            raise ValueError(f"reduce_flat: expected a contiguous fp32 buffer of >= {self.total_floats} floats on {self.device}")
+        words = [0] * self._mask_words
+        for n in touched:
+            if n not in self.index:
+                raise RuntimeError(f"gradient {n} is not in this reducer's layout")
+            words[self.index[n] // 62] |= 1 << (self.index[n] % 62)
+        mask = torch.tensor(words, dtype=torch.int64)
+        distributed = dist.is_initialized()
+        mask_work = None
+        if distributed and self.world > 1:
+            if self._host_group is None:          # layouts built without the host group (not mixed): made at the first step, on all ranks
+                if dist.get_backend(self.group) == "gloo":
+                    self._host_group = self.group if self.group is not None else dist.group.WORLD
+                else:
+                    ranks = dist.get_process_group_ranks(self.group if self.group is not None else dist.group.WORLD)
+                    self._host_group = dist.new_group(ranks=ranks, backend="gloo")
+            mask_work = dist.all_reduce(mask, op=dist.ReduceOp.BOR, group=self._host_group, async_op=True)
+        self.launched_order = []
+        works = []
+        for k, (a, b) in enumerate(self.bucket_ranges):
+            self.launched_order.append(k)
+            if b <= a or not distributed:
+                continue
+            view = flat[a:b]
+            if self.comm_stream is not None:
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(self.device))
+                with torch.cuda.stream(self.comm_stream):
+                    self.comm_stream.wait_event(ev)
+                    works.append(dist.all_reduce(view, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
+            else:
+                works.append(dist.all_reduce(view, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
+        for w in works:
+            w.wait()
+        if self.comm_stream is not None and distributed:
+            torch.cuda.current_stream(self.device).wait_stream(self.comm_stream)
+        if self.world > 1:
+            flat[:self.total_floats].mul_(1.0 / self.world)
+        if mask_work is not None:
+            mask_work.wait()
+        words = mask.tolist()
+        return [n for n in self.names if (words[self.index[n] // 62] >> (self.index[n] % 62)) & 1]
 
     def _abort(self):
         for w in self._works:

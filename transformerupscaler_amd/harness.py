@@ -39,6 +39,95 @@ def train_step(model, optimizer, lr_batch: torch.Tensor, hr_batch: torch.Tensor,
     return loss.detach()
 
 
+def plan_groups(shapes, group: bool = True, world: int = 1, b_global: int = None):
+    """How `train_step_samples` runs a list of samples: ``[(sample indices, loss weight)]`` in execution order.  shapes: one hashable
+    key per sample (its LR and HR shapes).  group=True: samples with equal keys form one batched group, groups in order of first
+    occurrence; group=False: every sample is its own group, in list order.  The weight of a group of n samples is
+    ``n * world / b_global`` (b_global = the sum of the ranks' list lengths, default ``len(shapes) * world``): the group's batch-mean
+    loss times its share of the step's mean over all samples, times `world` because the reducer divides the sum over ranks by it."""
+    shapes = list(shapes)
+    world = int(world)
+    if world < 1:
+        raise ValueError("world must be >= 1")
+    if b_global is None:
+        b_global = len(shapes) * world
+    if shapes and b_global < len(shapes):
+        raise ValueError(f"b_global = {b_global} is smaller than this rank's {len(shapes)} samples")
+    if not shapes:
+        return []          # a rank without samples (world > 1) still takes part in the step's reduction
+    if group:
+        members = {}
+        for i, key in enumerate(shapes):
+            members.setdefault(key, []).append(i)          # dicts keep insertion order: first occurrence
+        groups = list(members.values())
+    else:
+        groups = [[i] for i in range(len(shapes))]
+    return [(idx, len(idx) * world / b_global) for idx in groups]
+
+
+def _accumulator_for(model):
+    """The model's cached GradAccumulator, rebuilt when its reducer (DataParallel attached / detached) changed."""
+    from .accumulate import GradAccumulator
+    reducer = getattr(model, "_grad_reducer", None)
+    acc = model.__dict__.get("_grad_accumulator")
+    if acc is None or acc.reducer is not reducer:
+        acc = GradAccumulator(model, reducer)
+        model.__dict__["_grad_accumulator"] = acc
+    return acc
+
+
+def train_step_samples(model, optimizer, lr_list, hr_list, loss=None, group=True, accumulator=None, b_global=None) -> torch.Tensor:
+    """One optimizer step on a list of (lr, hr) samples of different sizes and scales: the reference's step (train.py:113-140), which
+    runs every sample at B = 1, averages the losses and steps once.  Samples are ``[3][h][w]`` or ``[1][3][h][w]`` GPU tensors.
+    Equal-shaped samples are batched (`group`, see `plan_groups`); each group's backward runs at once, so its activations are freed
+    before the next group's forward (the reference holds every graph until its single backward; the gradient is the same by
+    linearity), and its gradients go to `accumulator` (accumulate.GradAccumulator, by default the model's own, built on first use)
+    in one launch.  Under DataParallel the step's gradients are all-reduced once, in `accumulator.finish()`; ranks may hold different
+    numbers of samples (also none) when `b_global`, the sum of the ranks' list lengths, is passed.  Returns this rank's weighted loss
+    sum as a device scalar (no host synchronisation): the step's mean loss in a single process, and its sum over ranks / world
+    otherwise."""
+    if len(lr_list) != len(hr_list):
+        raise ValueError(f"{len(lr_list)} LR samples but {len(hr_list)} HR samples")
+    acc = accumulator if accumulator is not None else _accumulator_for(model)
+    world = acc.reducer.world if acc.reducer is not None else 1
+    lrs = [t.unsqueeze(0) if t.dim() == 3 else t for t in lr_list]
+    hrs = [t.unsqueeze(0) if t.dim() == 3 else t for t in hr_list]
+    plan = plan_groups([(tuple(a.shape), tuple(b.shape)) for a, b in zip(lrs, hrs)], group, world, b_global)
+    names = list(acc.params)
+    params = [acc.params[n] for n in names]
+    optimizer.zero_grad(set_to_none=True)                                    # train.py:113
+    total = torch.zeros((), dtype=torch.float32, device=acc.device)
+    suspended = getattr(model, "_grad_reducer", None)                        # the accumulator reduces once per step: the model's
+    model._grad_reducer = None                                               # backward opens no reducer episode of its own
+    acc.begin()
+    try:
+        for idx, weight in plan:
+            lr_b = lrs[idx[0]] if len(idx) == 1 else torch.cat([lrs[i] for i in idx])
+            hr_b = hrs[idx[0]] if len(idx) == 1 else torch.cat([hrs[i] for i in idx])
+            hw = tuple(hr_b.shape[2:])
+            out = model(lr_b, res_out=hw, require_ratio=False)               # train.py:124
+            if tuple(out.shape[2:]) != hw:
+                out = resize_aa(out, hw)                                     # train.py:127-130
+            if loss is None:
+                value = l1_loss(out, hr_b, fuse_into_model_backward=True)    # train.py:103,132
+            else:
+                value = loss(out, hr_b)
+            value = value * weight                                           # train.py:136, this group's share
+            del out
+            grads = torch.autograd.grad(value, params, allow_unused=True)    # train.py:138, for this group alone
+            acc.add(dict(zip(names, grads)))
+            total = total + value.detach()
+            del grads, value
+        acc.finish()
+    except BaseException:
+        acc._touched = None
+        raise
+    finally:
+        model._grad_reducer = suspended
+    optimizer.step()                                                         # train.py:139
+    return total
+
+
 def save_checkpoint(model, checkpoint_dir: str, epoch: int, optimizer=None) -> str:
     """train.py:152-156: weights only, ``model_epoch_{n}.pth`` -- the file the reference's drivers load
     (``model.load_state_dict(torch.load(path))``, train.py:90, inference.py:97, speed_test.py:45), in both directions.
