@@ -557,6 +557,28 @@ int tup_adam_step(const void* segs, const int* chunks, int nchunks, void* stream
  * elements.  16-byte accesses where dst and src are 16-byte aligned, scalar otherwise.  Segments must not overlap; no atomics. */
 int tup_grad_accumulate(const void* segs, const int* chunks, int nchunks, void* stream);
 
+/* The guarded optimizer step (csrc/step_guard.hip): GradScaler's skipping of steps with non-finite gradients (reference
+ * train.py:136-139) and torch.nn.utils.clip_grad_norm_, decided on the device; at most three launches, no host synchronisation.
+ *
+ * tup_grad_sumsq_partial: segs: device array [nseg] of 16-byte records {const float* g; long long n}; chunks: device int [nchunks][2] =
+ * (segment index, first element), one workgroup per 4096 elements; partials: device double [nchunks], partials[w] = the sum of
+ * (double)g * (double)g over workgroup w's elements.  16-byte loads where g is 16-byte aligned, scalar otherwise.
+ *
+ * tup_grad_guard_finish: one workgroup sums partials[0 .. npartials) in a fixed order and writes the 64-byte guard record
+ * {double sumsq, norm; float coef; int apply; float norm_f32; int clipped; unsigned long long steps, applied, clipped, skipped}:
+ * coef = min(1, max_norm / (norm + 1e-6)) computed in double and rounded (1 when max_norm < 0: no clipping), apply = isfinite(sumsq)
+ * || !skip_nonfinite, clipped = apply && coef < 1; the four running counters are incremented in place (zero the record once).
+ * No floating-point atomics: the record is bitwise reproducible.
+ *
+ * tup_adam_step_guarded: tup_adam_step with weight decay, reading the guard record (NULL: apply, coef = 1).  segs: device array [nseg]
+ * of 72-byte records {float* p; const float* g; float* m; float* v; long long n; float step_size (= lr / bias_correction1), bc2_sqrt
+ * (= sqrt(bias_correction2)), beta2, 1 - beta1, 1 - beta2, eps, wd_l2 (g += wd_l2 * p, torch.optim.Adam; 0: none), decay (p *= decay,
+ * = 1 - lr * weight_decay, torch.optim.AdamW; 1: none)}; chunks as for tup_adam_step.  apply == 0: p, m, v are not written; otherwise
+ * the gradient is coef * g.  g itself is never written. */
+int tup_grad_sumsq_partial(const void* segs, const int* chunks, int nchunks, double* partials, void* stream);
+int tup_grad_guard_finish(const double* partials, int npartials, double max_norm, int skip_nonfinite, void* guard, void* stream);
+int tup_adam_step_guarded(const void* segs, const int* chunks, int nchunks, const void* guard, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,12 @@ What differs from the reference driver:
   checkpoint of the unfinished epoch is still written); ``--pairs "96x96:192x192,..."`` replaces the scale-pair table;
   ``--cache_gb`` bounds the decoded-image cache; ``--save_optimizer`` writes Adam's state beside the weights and resumes from
   it; ``--json PATH`` writes a record of the run.
+* ``--weight_decay W`` decays the weights inside the fused step (Adam's L2 form; ``--adamw``: AdamW's decoupled form).
+  ``--clip_grad_norm C`` clips the step's global gradient norm to C and ``--skip_nonfinite`` skips a step whose gradients hold an
+  inf or a NaN (what the reference's GradScaler does), both decided on the GPU without a host synchronisation; ``p.grad`` keeps
+  the unclipped gradient.  ``--warmup_steps N`` / ``--lr_schedule cosine`` / ``--lr_min`` set the learning rate per optimizer
+  step (`lr_at`).  With any of these a step line and its ``--json`` entry also carry ``lr`` and ``grad_norm``, and the record
+  ``guard: {applied, clipped, skipped}``.
 * ``--traceback`` is accepted; the reference's traceback window is not available here.
 * With ``WORLD_SIZE > 1`` in the environment (torchrun) the run is data parallel: every rank shuffles with the same seed and
   trains ``batch[rank::world]``; the gradients of a step are all-reduced once.
@@ -31,6 +37,7 @@ What differs from the reference driver:
 import argparse
 import importlib
 import json
+import math
 import os
 import sys
 
@@ -61,7 +68,38 @@ def build_parser():
     p.add_argument("--save_optimizer", action="store_true", help="Write / resume Adam's state beside the weights")
     p.add_argument("--no_group", action="store_true", help="Run every sample at batch 1, as the reference does")
     p.add_argument("--json", type=str, default=None, help="Write a record of the run to this path")
+    p.add_argument("--weight_decay", type=float, default=0.0, help="Weight decay, inside the fused optimizer step")
+    p.add_argument("--adamw", action="store_true", help="AdamW: decoupled weight decay (p *= 1 - lr * wd) instead of Adam's L2 form")
+    p.add_argument("--clip_grad_norm", type=float, default=None, help="Clip the global gradient norm of a step to this value")
+    p.add_argument("--skip_nonfinite", action="store_true", help="Skip an optimizer step whose gradients hold an inf or a NaN")
+    p.add_argument("--warmup_steps", type=int, default=0, help="Linear learning-rate warm-up over this many optimizer steps")
+    p.add_argument("--lr_schedule", choices=("constant", "cosine"), default="constant", help="Learning rate after the warm-up")
+    p.add_argument("--lr_min", type=float, default=0.0, help="Final learning rate of the cosine schedule")
     return p
+
+
+def lr_at(k, base, warmup=0, schedule="constant", total=None, lr_min=0.0):
+    """The learning rate of global optimizer step k (0-based; a resumed run continues at epochs_trained * steps_per_epoch).
+    k < warmup: linear warm-up ``base * (k + 1) / warmup`` (step warmup - 1 runs at `base`).  Afterwards "constant" stays at `base`
+    and "cosine" runs from `base` (step `warmup`) to `lr_min` (step total - 1) over the remaining steps of the run."""
+    if k < warmup:
+        return base * (k + 1) / warmup
+    if schedule == "constant":
+        return base
+    if schedule != "cosine":
+        raise ValueError(f"unknown lr schedule {schedule!r}")
+    if total is None:
+        raise ValueError("the cosine schedule needs the run's total number of optimizer steps")
+    span = total - 1 - warmup
+    if span <= 0 or k >= total - 1:
+        return lr_min
+    return lr_min + 0.5 * (base - lr_min) * (1.0 + math.cos(math.pi * (k - warmup) / span))
+
+
+def guard_options(args):
+    """True if any optimizer option beyond the reference's plain Adam at a constant rate is set: the output gains lr / grad_norm."""
+    return (args.weight_decay != 0.0 or args.adamw or args.clip_grad_norm is not None or args.skip_nonfinite
+            or args.warmup_steps > 0 or args.lr_schedule != "constant")
 
 
 def pure_l1(args):
@@ -105,7 +143,8 @@ def run(args):
     if not any(p.requires_grad for p in model.parameters()):
         sys.exit(f"train.py: model {args.model} has no trainable parameter; there is nothing to train")
     model = model.to(device)
-    optimizer = harness.make_optimizer(model, lr=args.lr)
+    optimizer = harness.make_optimizer(model, lr=args.lr, weight_decay=args.weight_decay, decoupled=args.adamw,
+                                       max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
     epochs_trained = harness.load_latest_checkpoint(model, args.checkpoint_dir, optimizer if args.save_optimizer else None,
                                                     map_location=device)
     if epochs_trained:
@@ -141,6 +180,10 @@ def run(args):
               "steps": [], "epochs": [], "checkpoints": []}
     steps_done = 0
     stop = False
+    extras = guard_options(args)
+    guarded = args.clip_grad_norm is not None or args.skip_nonfinite
+    scheduled = args.warmup_steps > 0 or args.lr_schedule != "constant"
+    steps_per_epoch = -(-len(dataset) // args.batch_size)
     model.train()
     with ops.deterministic_mode(args.deterministic):
         for epoch in range(epochs_trained, args.epochs):
@@ -149,6 +192,12 @@ def run(args):
             for step, batch in enumerate(batches):
                 mine = batch[rank::world]
                 samples = [dataset[i] for i in mine]
+                lr_now = args.lr
+                if scheduled:                                             # the kernel reads lr from the group at every step
+                    lr_now = lr_at(epoch * steps_per_epoch + step, args.lr, args.warmup_steps, args.lr_schedule,
+                                   args.epochs * steps_per_epoch, args.lr_min)
+                    for group in optimizer.param_groups:
+                        group["lr"] = lr_now
                 loss = harness.train_step_samples(model, optimizer, [s[0] for s in samples], [s[1] for s in samples],
                                                   loss=criterion, group=not args.no_group, b_global=len(batch))
                 if world > 1:                                             # ranks hold their share / world of the step's mean loss
@@ -159,8 +208,14 @@ def run(args):
                 steps_done += 1
                 if step % args.log_interval == 0:
                     value = loss.item()
-                    say(f"Epoch [{epoch + 1}/{args.epochs}] Step [{step + 1}/{len(batches)}] Loss: {value:.6f}")
-                    record["steps"].append({"epoch": epoch + 1, "step": step + 1, "loss": value})
+                    entry = {"epoch": epoch + 1, "step": step + 1, "loss": value}
+                    tail = ""
+                    if extras:                                            # read back only here, where the loss already is
+                        entry["lr"] = lr_now
+                        entry["grad_norm"] = optimizer.grad_norm.item() if guarded and optimizer.grad_norm is not None else None
+                        tail = f" LR: {lr_now:.3e}" + ("" if entry["grad_norm"] is None else f" GradNorm: {entry['grad_norm']:.4f}")
+                    say(f"Epoch [{epoch + 1}/{args.epochs}] Step [{step + 1}/{len(batches)}] Loss: {value:.6f}{tail}")
+                    record["steps"].append(entry)
                 if args.max_steps is not None and steps_done >= args.max_steps:
                     stop = True
                     break
@@ -174,6 +229,11 @@ def run(args):
                     record["checkpoints"].append(path)
             if stop:
                 break
+    if extras:
+        stats = optimizer.guard_stats() if guarded else {"applied": steps_done, "clipped": 0, "skipped": 0}
+        record["guard"] = {k: stats[k] for k in ("applied", "clipped", "skipped")}
+        if guarded:
+            say(f"Optimizer steps applied: {stats['applied']}, clipped: {stats['clipped']}, skipped: {stats['skipped']}")
     say("Training complete!" if not stop else f"Stopped after {steps_done} steps (--max_steps).")
     if dp is not None:
         dp.detach()

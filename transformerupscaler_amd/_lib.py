@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_float, c_int, c_longlong, c_uint, c_void_p
+from ctypes import c_double, c_float, c_int, c_longlong, c_uint, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TUP_LIB_PATH") or os.path.join(_HERE, "libtupscale_hip.so")      # override: A/B of two builds
@@ -69,6 +69,10 @@ SIGNATURES = {
     "tup_pack_gather": [P, P, I, P, P, c_longlong, I, P],
     "tup_adam_step": [P, P, I, P],
     "tup_grad_accumulate": [P, P, I, P],
+    # guarded optimizer step (csrc/step_guard.hip)
+    "tup_grad_sumsq_partial": [P, P, I, P, P],
+    "tup_grad_guard_finish": [P, I, c_double, I, P, P],
+    "tup_adam_step_guarded": [P, P, I, P, P],
     "tup_l1_loss_partial": [P, P, P, c_longlong, I, P],
     "tup_l1_loss_bwd": [P, P, P, P, c_longlong, P],
     "tup_u8hwc_to_f32chw": [P, P, I, I, I, I, P],

@@ -44,6 +44,8 @@ GUARDED = [
     ("quality_loss.hip", ["quality_loss_bwd_kernel"]),
     # no counted hand-off: a streaming kernel at 12 B per element; scratch traffic would be a large share of what it moves
     ("grad_accumulate.hip", ["grad_accumulate_kernel"]),
+    # no counted hand-off: streaming kernels at 4 B (norm pass) and 28 B (step) per element, same reasoning
+    ("step_guard.hip", ["grad_sumsq_kernel", "guard_finish_kernel", "adam_guarded_kernel"]),
 ]
 # diagnostic template instantiations, never launched by the product path: fused_qkv_attn_kernel<PROJ, MLP, STAMPS = true>, the
 # timing ablations fused_mlp_v2_kernel<ABL != 0>

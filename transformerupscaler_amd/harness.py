@@ -5,6 +5,7 @@ samples at B=1; mean of per-sample L1 means == batch L1 mean for equal shapes, S
 ``train_step(..., loss=losses.QualityLoss(...))`` trains on another criterion (L1 / MSE / SSIM mix) in the L1 loss's place."""
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -15,13 +16,66 @@ from .autograd import l1_loss, resize_aa
 use_torch_adam = False          # A/B attribute
 
 
-def make_optimizer(model, lr: float = 1e-4):
+class _TorchGuardedStep:
+    """The A/B arm of optim.Adam / optim.AdamW's guard options on stock torch: clip_grad_norm_'s arithmetic on the parameters with a
+    gradient, a synchronised finite check (`.item()`), then torch's own step.  Unlike the fused step it scales ``p.grad`` in place."""
+
+    def __init__(self, params, *args, max_grad_norm=None, skip_nonfinite=False, **kwargs):
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f"max_grad_norm must be >= 0 or None, got {max_grad_norm}")
+        super().__init__(params, *args, **kwargs)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.grad_norm = None
+        self._counts = {"steps": 0, "applied": 0, "clipped": 0, "skipped": 0}
+
+    def guard_stats(self) -> dict:
+        return dict(self._counts)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if self.max_grad_norm is None and not self.skip_nonfinite:
+            return super().step(closure)
+        grads = [p.grad for g in self.param_groups for p in g["params"] if p.grad is not None]
+        if not grads:
+            return super().step(closure)
+        norm = torch.linalg.vector_norm(torch.stack(torch._foreach_norm(grads)).double())
+        self.grad_norm = norm.float()
+        self._counts["steps"] += 1
+        value = norm.item()                                   # the host synchronisation the fused step does without
+        if self.skip_nonfinite and not math.isfinite(value):
+            self._counts["skipped"] += 1
+            return None
+        if self.max_grad_norm is not None:
+            torch._foreach_mul_(grads, torch.clamp(self.max_grad_norm / (norm + 1e-6), max=1.0).float())
+            self._counts["clipped"] += int(self.max_grad_norm / (value + 1e-6) < 1.0)
+        self._counts["applied"] += 1
+        return super().step(closure)
+
+
+class _TorchAdam(_TorchGuardedStep, torch.optim.Adam):
+    pass
+
+
+class _TorchAdamW(_TorchGuardedStep, torch.optim.AdamW):
+    pass
+
+
+def make_optimizer(model, lr: float = 1e-4, weight_decay: float = 0.0, decoupled: bool = False, max_grad_norm=None,
+                   skip_nonfinite: bool = False):
     """train.py:104 -- Adam, default betas/eps, no weight decay (parameters without grad are skipped).  `optim.Adam` is
-    torch.optim.Adam with the whole update in one HIP launch; harness.use_torch_adam = True selects torch's own step (A/B)."""
+    torch.optim.Adam with the whole update in one HIP launch; harness.use_torch_adam = True selects torch's own step (A/B).
+    `weight_decay` with `decoupled` selects AdamW's form (``p *= 1 - lr * wd``) instead of Adam's (``g += wd * p``);
+    `max_grad_norm` / `skip_nonfinite` are optim.Adam's guard options (global-norm clipping, GradScaler's skipping of a step whose
+    gradients are not finite), which the torch arm runs as clip_grad_norm_'s arithmetic plus a synchronised finite check."""
+    kw = dict(lr=lr, weight_decay=weight_decay)
+    guard = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
     if use_torch_adam:
-        return torch.optim.Adam(model.parameters(), lr=lr)
-    from .optim import Adam
-    return Adam(model.parameters(), lr=lr)
+        if max_grad_norm is None and not skip_nonfinite:
+            return (torch.optim.AdamW if decoupled else torch.optim.Adam)(model.parameters(), **kw)
+        return (_TorchAdamW if decoupled else _TorchAdam)(model.parameters(), **kw, **guard)
+    from .optim import Adam, AdamW
+    return (AdamW if decoupled else Adam)(model.parameters(), **kw, **guard)
 
 
 def train_step(model, optimizer, lr_batch: torch.Tensor, hr_batch: torch.Tensor, loss=None) -> torch.Tensor:
@@ -34,7 +88,7 @@ def train_step(model, optimizer, lr_batch: torch.Tensor, hr_batch: torch.Tensor,
         loss = l1_loss(out, hr_batch, fuse_into_model_backward=True)         # train.py:103,132,136 (HIP forward + backward; `out` feeds nothing else)
     else:
         loss = loss(out, hr_batch)
-    loss.backward()                                                          # train.py:138 (bf16 needs no GradScaler)
+    loss.backward()                                                          # train.py:138 (bf16 needs no loss scaling; GradScaler's step skipping is make_optimizer(skip_nonfinite=True))
     optimizer.step()                                                         # train.py:139
     return loss.detach()
 
