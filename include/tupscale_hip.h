@@ -579,6 +579,19 @@ int tup_grad_sumsq_partial(const void* segs, const int* chunks, int nchunks, dou
 int tup_grad_guard_finish(const double* partials, int npartials, double max_norm, int skip_nonfinite, void* guard, void* stream);
 int tup_adam_step_guarded(const void* segs, const int* chunks, int nchunks, const void* guard, void* stream);
 
+/* Patch training samples of a whole batch in one launch (data.PatchSampler; csrc/patch_pairs.hip).  recs: device array [B] of 32-byte
+ * records {const uint8_t* frame; int H; int W; int y0; int x0; int op; int reserved}, frame a contiguous uint8 [H][W][3] RGB image.
+ * Per record, bit-exact: t = frame[y0:y0+P, x0:x0+P]; op & 1: t = t[:, ::-1]; op & 2: t = t[::-1]; op & 4: t = t.transpose(1, 0, 2)
+ * (in that order); hr = ToTensor(t) = (float)v / 255.0f; lr = ToTensor(Image.resize((p, p), BILINEAR)(t)), Pillow's 8-bit two-pass
+ * resampler as tup_resize_u8_rows / _cols state it, the horizontal pass over the TRANSFORMED image rounded to uint8 first.
+ * P = p * s is the HR and p the LR patch side; xmin / xsize int32 [p], k int32 [p][ksize] = resize_taps.pil_bilinear_coeffs(P, p)
+ * serve both passes; hr fp32 [B][3][P][P], lr fp32 [B][3][p][p], both in [0, 1].  One workgroup per 16 x 16 LR tile and sample; the
+ * uint8 intermediate stays in LDS; one writer per output element, no atomics, no workspace.  A record whose box leaves its frame
+ * or whose op is outside [0, 8) is skipped (its outputs are not written): validate on the host.  B <= 0: no-op.  B > 65535,
+ * ksize < 1, P < p, p < 1, P not a multiple of p, or a window beyond 64 KiB of LDS (s > 8): hipErrorInvalidValue. */
+int tup_patch_pairs(const void* recs, int B, int P, int p, const int* xmin, const int* xsize, const int* k, int ksize,
+                    float* hr, float* lr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

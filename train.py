@@ -30,6 +30,12 @@ What differs from the reference driver:
   the unclipped gradient.  ``--warmup_steps N`` / ``--lr_schedule cosine`` / ``--lr_min`` set the learning rate per optimizer
   step (`lr_at`).  With any of these a step line and its ``--json`` entry also carry ``lr`` and ``grad_norm``, and the record
   ``guard: {applied, clipped, skipped}``.
+* ``--patch_size N`` trains on random patches instead of whole frames (``transformerupscaler_amd.data.PatchSampler``): every
+  sample is an ``N x N`` LR patch and its ``N*s x N*s`` HR crop, s drawn from ``--patch_scales`` (default 2,3,4,6), with one of the
+  8 flip / rotate variants (``--no_augment``: none); a step's samples are built in one launch per distinct scale.
+  ``--patches_per_epoch`` sets the epoch length (default: the whole-frame dataset's).  Sample g of a run is a function of
+  ``(--seed, g)`` alone, so resumed runs and ranks need no generator state.  ``--pairs`` does not apply; ResidualTransformer (fixed
+  720x1280 input) cannot train on patches.  The ``--json`` record gains ``patch``.
 * ``--traceback`` is accepted; the reference's traceback window is not available here.
 * With ``WORLD_SIZE > 1`` in the environment (torchrun) the run is data parallel: every rank shuffles with the same seed and
   trains ``batch[rank::world]``; the gradients of a step are all-reduced once.
@@ -75,6 +81,10 @@ def build_parser():
     p.add_argument("--warmup_steps", type=int, default=0, help="Linear learning-rate warm-up over this many optimizer steps")
     p.add_argument("--lr_schedule", choices=("constant", "cosine"), default="constant", help="Learning rate after the warm-up")
     p.add_argument("--lr_min", type=float, default=0.0, help="Final learning rate of the cosine schedule")
+    p.add_argument("--patch_size", type=int, default=None, help="Train on random patches: the LR patch side (HR side = this x scale)")
+    p.add_argument("--patch_scales", type=str, default="2,3,4,6", help="Scales the patches are drawn from (with --patch_size)")
+    p.add_argument("--no_augment", action="store_true", help="No flip / rotate variants of the patches (with --patch_size)")
+    p.add_argument("--patches_per_epoch", type=int, default=None, help="Samples per epoch with --patch_size (default: the dataset's)")
     return p
 
 
@@ -106,6 +116,34 @@ def pure_l1(args):
     return args.l1 == 1.0 and args.mse == 0.0 and args.ssim == 0.0
 
 
+def patch_options(args):
+    """The patch-mode options, checked before anything touches the GPU: None without ``--patch_size``, else (patch, scales)."""
+    if args.patch_size is None:
+        if args.no_augment or args.patches_per_epoch is not None or args.patch_scales != "2,3,4,6":
+            sys.exit("train.py: --patch_scales, --no_augment and --patches_per_epoch need --patch_size")
+        return None
+    if args.pairs:
+        sys.exit("train.py: --pairs does not apply with --patch_size (patches are square: use --patch_scales)")
+    if args.patch_size < 1:
+        sys.exit("train.py: --patch_size must be >= 1")
+    if args.patches_per_epoch is not None and args.patches_per_epoch < 1:
+        sys.exit("train.py: --patches_per_epoch must be >= 1")
+    try:
+        scales = tuple(int(v) for v in args.patch_scales.split(","))
+    except ValueError:
+        sys.exit(f"train.py: --patch_scales {args.patch_scales!r}: expected integers separated by commas, e.g. 2,3,4,6")
+    if args.model == "ResidualTransformer":
+        sys.exit("train.py: --model ResidualTransformer takes only 720x1280 input (its position embedding fixes the token count); "
+                 "it cannot train with --patch_size")
+    if args.model == "WindowTransformer" and (args.patch_size + 1) // 2 < 8:
+        sys.exit("train.py: --model WindowTransformer needs --patch_size >= 15 (one 8x8 patch after its stride-2 conv)")
+    valid = (2, 3, 4, 6) if args.model == "FastTransformer" else tuple(range(1, 9))          # weights.VALID_SCALES; the sampler's range
+    bad = [v for v in scales if v not in valid]
+    if bad or not scales or len(set(scales)) != len(scales):
+        sys.exit(f"train.py: --patch_scales {args.patch_scales!r}: --model {args.model} trains on distinct scales out of {list(valid)}")
+    return args.patch_size, scales
+
+
 def epoch_batches(n_samples, batch_size, generator):
     """The shuffled batches of one epoch (index lists); a last partial batch is kept (DataLoader's drop_last=False)."""
     import torch
@@ -118,10 +156,11 @@ def run(args):
         sys.exit("train.py: --data_dir is required (a directory of .png images); the reference's online dataset is not built")
     if args.batch_size < 1:
         sys.exit("train.py: --batch_size must be >= 1")
+    patch = patch_options(args)
     import torch
 
     from transformerupscaler_amd import harness, ops
-    from transformerupscaler_amd.data import SCALE_PAIRS, PairDataset, parse_pairs
+    from transformerupscaler_amd.data import SCALE_PAIRS, PairDataset, PatchSampler, parse_pairs
 
     if args.checkpoint_dir is None:
         args.checkpoint_dir = os.path.join("models", args.model, "checkpoints")
@@ -164,20 +203,33 @@ def run(args):
         else:
             dp = DataParallel(model)                                      # every parameter is active in every step
 
-    pairs = parse_pairs(args.pairs) if args.pairs else SCALE_PAIRS
-    dataset = PairDataset(args.data_dir, pairs, cache_bytes=int(args.cache_gb * (1 << 30)), device=device)
+    if patch is not None:
+        pairs = None
+        try:
+            dataset = PatchSampler(args.data_dir, patch=patch[0], scales=patch[1], augment=not args.no_augment, seed=args.seed,
+                                   samples_per_epoch=args.patches_per_epoch, cache_bytes=int(args.cache_gb * (1 << 30)), device=device)
+        except ValueError as e:
+            sys.exit(f"train.py: {e}")
+    else:
+        pairs = parse_pairs(args.pairs) if args.pairs else SCALE_PAIRS
+        dataset = PairDataset(args.data_dir, pairs, cache_bytes=int(args.cache_gb * (1 << 30)), device=device)
     criterion = None
     if not pure_l1(args):
         from transformerupscaler_amd.losses import QualityLoss
         criterion = QualityLoss(l1=args.l1, mse=args.mse, ssim=args.ssim)
-    say(f"{len(dataset)} samples from {len(dataset.files)} images, {len(pairs)} scale pairs; loss "
-        f"{'L1' if criterion is None else criterion}")
+    what = (f"{len(pairs)} scale pairs" if patch is None else
+            f"{patch[0]}x{patch[0]} patches at scales {list(patch[1])}" + ("" if dataset.augment else ", no augmentation"))
+    say(f"{len(dataset)} samples from {len(dataset.files)} images, {what}; loss {'L1' if criterion is None else criterion}")
 
     shuffle = torch.Generator().manual_seed(args.seed)
     for _ in range(epochs_trained):                                       # a resumed run continues the shuffle sequence
         torch.randperm(len(dataset), generator=shuffle)
     record = {"model": args.model, "world": world, "samples": len(dataset), "resumed_from_epoch": epochs_trained,
               "steps": [], "epochs": [], "checkpoints": []}
+    if patch is not None:
+        record["patch"] = {"size": patch[0], "scales": list(patch[1]), "augment": dataset.augment,
+                           "samples_per_epoch": dataset.samples_per_epoch}
+    timed = []                                                            # patch mode: (start, sampler done, step done) events
     steps_done = 0
     stop = False
     extras = guard_options(args)
@@ -191,15 +243,27 @@ def run(args):
             losses = []                                                   # device scalars: read back when printed / at epoch end
             for step, batch in enumerate(batches):
                 mine = batch[rank::world]
-                samples = [dataset[i] for i in mine]
+                if patch is not None:                                     # global sample index: a function of (seed, g) alone
+                    if len(timed) < 256:
+                        marks = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                        marks[0].record()
+                    lr_list, hr_list = dataset.batch([epoch * len(dataset) + i for i in mine])
+                    if len(timed) < 256:
+                        marks[1].record()
+                else:
+                    samples = [dataset[i] for i in mine]
+                    lr_list, hr_list = [s[0] for s in samples], [s[1] for s in samples]
                 lr_now = args.lr
                 if scheduled:                                             # the kernel reads lr from the group at every step
                     lr_now = lr_at(epoch * steps_per_epoch + step, args.lr, args.warmup_steps, args.lr_schedule,
                                    args.epochs * steps_per_epoch, args.lr_min)
                     for group in optimizer.param_groups:
                         group["lr"] = lr_now
-                loss = harness.train_step_samples(model, optimizer, [s[0] for s in samples], [s[1] for s in samples],
+                loss = harness.train_step_samples(model, optimizer, lr_list, hr_list,
                                                   loss=criterion, group=not args.no_group, b_global=len(batch))
+                if patch is not None and len(timed) < 256:
+                    marks[2].record()
+                    timed.append(marks)
                 if world > 1:                                             # ranks hold their share / world of the step's mean loss
                     loss = loss.clone()
                     torch.distributed.all_reduce(loss)
@@ -234,6 +298,12 @@ def run(args):
         record["guard"] = {k: stats[k] for k in ("applied", "clipped", "skipped")}
         if guarded:
             say(f"Optimizer steps applied: {stats['applied']}, clipped: {stats['clipped']}, skipped: {stats['skipped']}")
+    if len(timed) > 1:                                                    # GPU time between stream events, first step (warm-up) left out
+        torch.cuda.synchronize()
+        sampler_ms = sum(m[0].elapsed_time(m[1]) for m in timed[1:]) / (len(timed) - 1)
+        step_ms = sum(m[0].elapsed_time(m[2]) for m in timed[1:]) / (len(timed) - 1)
+        record["patch"]["timing"] = {"steps": len(timed) - 1, "step_ms": step_ms, "sampler_ms": sampler_ms}
+        say(f"Patch sampler: {sampler_ms:.3f} ms of {step_ms:.3f} ms per step ({len(timed) - 1} steps after the first)")
     say("Training complete!" if not stop else f"Stopped after {steps_done} steps (--max_steps).")
     if dp is not None:
         dp.detach()

@@ -46,6 +46,9 @@ GUARDED = [
     ("grad_accumulate.hip", ["grad_accumulate_kernel"]),
     # no counted hand-off: streaming kernels at 4 B (norm pass) and 28 B (step) per element, same reasoning
     ("step_guard.hip", ["grad_sumsq_kernel", "guard_finish_kernel", "adam_guarded_kernel"]),
+    # no counted hand-off: byte work at ~15 B of memory traffic per HR pixel whose tap loops index small LDS tiles; scratch would add
+    # memory traffic to a kernel that exists to remove it
+    ("patch_pairs.hip", ["patch_pairs_kernel"]),
 ]
 # diagnostic template instantiations, never launched by the product path: fused_qkv_attn_kernel<PROJ, MLP, STAMPS = true>, the
 # timing ablations fused_mlp_v2_kernel<ABL != 0>

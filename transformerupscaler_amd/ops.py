@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import os
+import struct
 
 import numpy as np
 import torch
@@ -1237,6 +1238,101 @@ def resize_frames(frames_u8, size, to_tensor=False, bgr=False):
                   None if out_f is None else out_f.data_ptr(), lo.data_ptr(), n.data_ptr(), k.data_ptr(), ks, B, H, w, h, int(bgr), _stream())
         return out_f if to_tensor else out_u8
     return frames_to_tensor(cur, bgr=bgr) if to_tensor else (cur if cur is not frames_u8 else cur.clone())
+
+
+# ---- patch training samples: crops, flip / rotate variants and their LR counterparts in one launch (csrc/patch_pairs.hip) ----
+_PATCH_REC = struct.Struct("<Qiiiiii")          # PatchRec: frame, H, W, y0, x0, op, reserved
+
+
+class _RecordStager:
+    """The record table of a `tup_patch_pairs` launch changes with every launch, so it goes up through one of two pinned staging
+    buffers in one non-blocking copy (the pattern of accumulate.SegmentLauncher)."""
+
+    def __init__(self, device):
+        self.device = device
+        self._stage = [None, None]
+        self._events = [None, None]
+        self._slot = 0
+
+    def upload(self, raw: bytes) -> torch.Tensor:
+        slot = self._slot = self._slot ^ 1
+        # the host may run ahead of the GPU: a staging slot is rewritten only after the upload that last read it has executed
+        if self._events[slot] is not None:
+            self._events[slot].synchronize()
+        words = len(raw) // 8
+        if self._stage[slot] is None or self._stage[slot].numel() < words:
+            self._stage[slot] = torch.empty(max(words, 1024), dtype=torch.int64).pin_memory()
+        host = self._stage[slot][:words]
+        host.copy_(torch.frombuffer(bytearray(raw), dtype=torch.int64))
+        table = host.to(self.device, non_blocking=True)
+        if self._events[slot] is None:
+            self._events[slot] = torch.cuda.Event()
+        self._events[slot].record()
+        return table
+
+
+_PATCH_STAGERS = {}
+
+
+def patch_pairs(frames, boxes, p, scale, out=None):
+    """Training patches of a batch in ONE launch.  frames: B uint8 [H][W][3] GPU tensors (RGB, contiguous; the same tensor may appear
+    several times); boxes: B tuples (y0, x0, op); p: LR patch side; scale: HR side = p * scale.  Per sample, bit-exact:
+    t = frame[y0:y0+P, x0:x0+P]; op & 1: t[:, ::-1]; op & 2: t[::-1]; op & 4: t.transpose(1, 0, 2), in that order; hr = ToTensor(t),
+    lr = ToTensor(Image.resize((p, p), BILINEAR)(t)).  Returns (lr fp32 [B][3][p][p], hr fp32 [B][3][P][P]); out=(lr, hr) supplies
+    them.  Everything is validated on the host before anything is uploaded: a crop that leaves its frame never reaches the device."""
+    p, scale = int(p), int(scale)
+    if p < 1 or scale < 1:
+        raise ValueError(f"patch_pairs: p = {p} and scale = {scale} must be >= 1")
+    if scale > 8:
+        raise ValueError(f"patch_pairs: scale {scale} is beyond the kernel's LDS window (scales up to 8)")
+    P = p * scale
+    frames, boxes = list(frames), list(boxes)
+    B = len(frames)
+    if len(boxes) != B:
+        raise ValueError(f"patch_pairs: {B} frames but {len(boxes)} boxes")
+    if B > 65535:
+        raise ValueError(f"patch_pairs: {B} samples in one launch (at most 65535)")
+    recs = []
+    for i, (f, box) in enumerate(zip(frames, boxes)):
+        if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8:
+            raise TypeError(f"patch_pairs: sample {i}: the frame must be a uint8 tensor, got {getattr(f, 'dtype', type(f))}")
+        if f.dim() != 3 or f.shape[2] != 3 or not f.is_contiguous():
+            raise ValueError(f"patch_pairs: sample {i}: the frame must be contiguous [H][W][3], got {tuple(f.shape)}")
+        H, W = int(f.shape[0]), int(f.shape[1])
+        if len(box) != 3 or any(int(v) != v for v in box):
+            raise ValueError(f"patch_pairs: sample {i}: box {box!r} is not (y0, x0, op) in integers")
+        y0, x0, op = (int(v) for v in box)
+        if y0 < 0 or x0 < 0 or y0 + P > H or x0 + P > W:
+            raise ValueError(f"patch_pairs: sample {i}: the {P} x {P} crop at (y0, x0) = ({y0}, {x0}) leaves its {H} x {W} frame")
+        if not 0 <= op < 8:
+            raise ValueError(f"patch_pairs: sample {i}: op {op} is outside [0, 8)")
+        recs.append((f, H, W, y0, x0, op))
+    if B == 0:
+        dev = out[0].device if out is not None else torch.device("cuda", _cur_dev())
+    else:
+        dev = frames[0].device
+        for i, f in enumerate(frames):
+            if not f.is_cuda or f.device != dev or f.device.index != _cur_dev():
+                raise RuntimeError(f"patch_pairs: sample {i}: the frame lives on {f.device}; every frame must be on the current GPU "
+                                   f"cuda:{_cur_dev() if torch.cuda.is_available() else '?'} (no CPU fallback)")
+    if out is None:
+        lr = torch.empty((B, 3, p, p), dtype=F32, device=dev)
+        hr = torch.empty((B, 3, P, P), dtype=F32, device=dev)
+    else:
+        lr, hr = out
+        _chk(lr, F32, (B, 3, p, p), "out lr")
+        _chk(hr, F32, (B, 3, P, P), "out hr")
+    if B == 0:
+        return lr, hr
+    lo, n, k, ks = _pil_taps_on(dev, P, p)
+    raw = b"".join(_PATCH_REC.pack(f.data_ptr(), H, W, y0, x0, op, 0) for f, H, W, y0, x0, op in recs)
+    stager = _PATCH_STAGERS.get(dev)
+    if stager is None:
+        stager = _PATCH_STAGERS[dev] = _RecordStager(dev)
+    table = stager.upload(raw)
+    _lib.call("tup_patch_pairs", table.data_ptr(), B, P, p, lo.data_ptr(), n.data_ptr(), k.data_ptr(), ks,
+              hr.data_ptr(), lr.data_ptr(), _stream())
+    return lr, hr
 
 
 # ---- WindowTransformer (SURVEY 8(f) rank 2): window block at width 128 / 8 heads ----
