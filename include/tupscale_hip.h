@@ -58,6 +58,13 @@ int tup_conv3x3_c64_fwd(const void* x, const void* wp, const float* bias, const 
 int tup_decoder_fused_fwd(const void* x, const void* w1, const float* b1, const void* wz, const float* b2,
                           float* seamv, float* cseam, float* out, int B, int H, int W, void* stream);
 
+/* The same without the finishing launch: part and seamv fp32 [B][3][H][W] and cseam fp32 [B][H][ceil(W/32)][32] are left unfinished
+ * (the wave's own sums, the row-seam terms, the raw tile-edge columns; the rows of seamv without a seam partner and cseam's pad
+ * words are not written).  The finished plane is b2 + part [+ seamv] [+ three cseam terms], in that order
+ * (decoder_finish_kernel): tup_tail_stream_r2_parts_fwd / tup_tail_stream_r2_resize_parts_fwd form it where they read it. */
+int tup_decoder_fused_parts_fwd(const void* x, const void* w1, const float* b1, const void* wz,
+                                float* part, float* seamv, float* cseam, int B, int H, int W, void* stream);
+
 /* Inference conv1 + conv2 (model.py:202-204,251-252: Conv2d(3,64)+ReLU, Conv2d(64,64)+ReLU) without the 64-channel map between
  * them in HBM (csrc/conv12_fused.hip).  tup_conv1_compact_fwd: x fp32 [B][3][H][W] -> xc bf16 [B][Hp][Wp][4], Hp = 8 ceil(H/8) + 4,
  * Wp = 32 ceil(W/32) + 4 (image at (+2, +2), zero border, channel 3 = 0).  tup_conv12_fused_fwd: xc -> out bf16 NHWC [B][H][W][64]
@@ -109,6 +116,19 @@ int tup_tail_stream_r2_resize_fwd(const float* x, const float* wfu_t, const floa
                                   const float* ui, float* out, const int* ymin, const int* ysize, const float* yw, int KY,
                                   const int* xmin, const int* xsize, const float* xw, int KX, const int* oxb, const int* oyb,
                                   int B, int H, int W, int Ho, int Wo, int sc, int band_h, int ext, int clamp01, void* stream);
+
+/* The two entries above on the unfinished output of tup_decoder_fused_parts_fwd in place of x (part, seamv, cseam as left by it,
+ * b2 fp32 [3] = decoder_conv2's bias, tilesX = ceil(W / 32)): every LR value is formed in decoder_finish_kernel's order of fp32
+ * additions where the kernel would have loaded it, so out equals, bit for bit, what the finished plane gives.
+ * Requires B*H*tilesX*32 < 2^29 beside the limits of the entries above. */
+int tup_tail_stream_r2_parts_fwd(const float* part, const float* seamv, const float* cseam, const float* b2, int tilesX,
+                                 const float* wfu_t, const float* bfu, const float* wfc_t, const float* bfc,
+                                 const float* ui, float* out, int B, int H, int W, int clamp01, void* stream);
+int tup_tail_stream_r2_resize_parts_fwd(const float* part, const float* seamv, const float* cseam, const float* b2, int tilesX,
+                                        const float* wfu_t, const float* bfu, const float* wfc_t, const float* bfc,
+                                        const float* ui, float* out, const int* ymin, const int* ysize, const float* yw, int KY,
+                                        const int* xmin, const int* xsize, const float* xw, int KX, const int* oxb, const int* oyb,
+                                        int B, int H, int W, int Ho, int Wo, int sc, int band_h, int ext, int clamp01, void* stream);
 
 /* Inference fusion of the output tail (model.py:316-327): last final_upscale stage (Conv2d(3,3rr,3)+PixelShuffle),
  * final_upscale_conv, "+ upscaled_input", Resize (tap tables; identity tables when sizes match) and clamp.

@@ -25,6 +25,7 @@ SIGNATURES = {
     "tup_conv3x3_c64_fwd": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],
     "tup_conv5x5_c64_planar_fwd": [P, P, P, P, P, P, I, I, I, I, I, P],
     "tup_decoder_fused_fwd": [P, P, P, P, P, P, P, P, I, I, I, P],
+    "tup_decoder_fused_parts_fwd": [P, P, P, P, P, P, P, I, I, I, P],
     "tup_conv1_compact_fwd": [P, P, I, I, I, P],
     "tup_conv12_fused_fwd": [P, P, P, P, P, P, I, I, I, P],
     "tup_conv3x3_planar_fwd": [P, P, P, P, P, I, I, I, I, I, P],
@@ -32,6 +33,8 @@ SIGNATURES = {
     "tup_tail_fused_fwd": [P, P, P, P, P, P, P, P, P, P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
     "tup_tail_stream_r2_fwd": [P, P, P, P, P, P, P, I, I, I, I, P],
     "tup_tail_stream_r2_resize_fwd": [P] * 7 + [P, P, P, I, P, P, P, I, P, P] + [I] * 9 + [P],
+    "tup_tail_stream_r2_parts_fwd": [P, P, P, P, I] + [P] * 6 + [I, I, I, I, P],
+    "tup_tail_stream_r2_resize_parts_fwd": [P, P, P, P, I] + [P] * 6 + [P, P, P, I, P, P, P, I, P, P] + [I] * 9 + [P],
     "tup_clamp01_fwd": [P, P, c_longlong, P],
     "tup_layernorm_fwd": [P, P, P, P, P, P, I, P],
     "tup_relpos_bias_expand": [P, P, P],

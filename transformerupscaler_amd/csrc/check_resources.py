@@ -49,6 +49,9 @@ GUARDED = [
     # no counted hand-off: byte work at ~15 B of memory traffic per HR pixel whose tap loops index small LDS tiles; scratch would add
     # memory traffic to a kernel that exists to remove it
     ("patch_pairs.hip", ["patch_pairs_kernel"]),
+    # no counted vmcnt here, but the kernel lives on three waves per SIMD with every row's loads requested a row ahead: scratch reloads
+    # queue behind those loads (seen in round 3).  All four instances (RESIZE x PARTS) sit at 133-152 registers of 168
+    ("tail_stream.hip", ["tail_stream_r2_kernel"]),
 ]
 # diagnostic template instantiations, never launched by the product path: fused_qkv_attn_kernel<PROJ, MLP, STAMPS = true>, the
 # timing ablations fused_mlp_v2_kernel<ABL != 0>

@@ -21,6 +21,8 @@
 //   cseam  [B][H][tilesX][2][4][4]  raw Z of the tile's first (side 0: dx = 2, to column x-1) and last (side 1: dx = 0,
 //                        to column x+1) dec column: [c][dy]
 // dec pixels outside the image hold ReLU(bias), not conv2's zero padding, so edge tiles zero them before the second GEMM.
+// At scale 2 the only reader of residual is the streaming output tail, which adds the pieces itself in the same order as it reads
+// them (tup_decoder_fused_parts_fwd here, tail_stream.hip PARTS): the finishing kernel then does not run.
 #include "common.h"
 
 namespace {
@@ -362,13 +364,11 @@ __global__ __launch_bounds__(256) void decoder_finish_kernel(
 
 }  // namespace
 
-// combined bf16 NHWC [B][H][W][64]; w1 bf16 [1][1][9][64][64] + b1 fp32 [64] (tup_conv3x3_c64_fwd's out_mode 0 packing);
-// wz bf16 [48][64] (decoder_conv2 in scatter form, packing.pack_dec2_scatter); b2 fp32 [3];
-// seamv fp32 [B][3][H][W], cseam fp32 [B][H][ceil(W/32)][32] workspaces; out fp32 [B][3][H][W].
-extern "C" int tup_decoder_fused_fwd(const void* x, const void* w1, const float* b1, const void* wz, const float* b2,
-                                     float* seamv, float* cseam, float* out, int B, int H, int W, void* stream)
+namespace {
+// decoder_fused_kernel alone: part, seamv and cseam are left in HBM as the header of this file describes them
+int launch_decoder_parts(const void* x, const void* w1, const float* b1, const void* wz, float* part, float* seamv, float* cseam,
+                         int B, int H, int W, void* stream)
 {
-    if (B <= 0 || H <= 0 || W <= 0) return 0;
     const int tilesX = (W + TW - 1) / TW, tilesY = (H + TH - 1) / TH;
     const long long nt = (long long)tilesX * tilesY * B;
     // buffer-resource byte offsets are 32-bit and per image
@@ -377,9 +377,23 @@ extern "C" int tup_decoder_fused_fwd(const void* x, const void* w1, const float*
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     TUP_SET_DYN_LDS(decoder_fused_kernel, DEC_LDS);
     const int grid = (int)(nt < 256 ? nt : 256);                 // one workgroup per CU
-    decoder_fused_kernel<<<dim3(grid), dim3(512), DEC_LDS, s>>>((const bf16_t*)x, (const bf16_t*)w1, b1, (const bf16_t*)wz, out,
+    decoder_fused_kernel<<<dim3(grid), dim3(512), DEC_LDS, s>>>((const bf16_t*)x, (const bf16_t*)w1, b1, (const bf16_t*)wz, part,
                                                                  seamv, cseam, B, H, W, tilesX, tilesY);
     TUP_CHECK_LAUNCH();
+    return 0;
+}
+}  // namespace
+
+// combined bf16 NHWC [B][H][W][64]; w1 bf16 [1][1][9][64][64] + b1 fp32 [64] (tup_conv3x3_c64_fwd's out_mode 0 packing);
+// wz bf16 [48][64] (decoder_conv2 in scatter form, packing.pack_dec2_scatter); b2 fp32 [3];
+// seamv fp32 [B][3][H][W], cseam fp32 [B][H][ceil(W/32)][32] workspaces; out fp32 [B][3][H][W].
+extern "C" int tup_decoder_fused_fwd(const void* x, const void* w1, const float* b1, const void* wz, const float* b2,
+                                     float* seamv, float* cseam, float* out, int B, int H, int W, void* stream)
+{
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    const int tilesX = (W + TW - 1) / TW;
+    if (const int err = launch_decoder_parts(x, w1, b1, wz, out, seamv, cseam, B, H, W, stream)) return err;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if ((long long)B * H > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     if (W % 4 == 0)
         decoder_finish_kernel<4><<<dim3((unsigned)((W / 4 + 255) / 256), (unsigned)(B * H)), dim3(256), 0, s>>>(out, seamv, cseam, b2, H, W, tilesX);
@@ -387,4 +401,14 @@ extern "C" int tup_decoder_fused_fwd(const void* x, const void* w1, const float*
         decoder_finish_kernel<1><<<dim3((unsigned)((W + 255) / 256), (unsigned)(B * H)), dim3(256), 0, s>>>(out, seamv, cseam, b2, H, W, tilesX);
     TUP_CHECK_LAUNCH();
     return 0;
+}
+
+// The fused kernel without the finishing launch: part, seamv fp32 [B][3][H][W] and cseam fp32 [B][H][ceil(W/32)][32] stay unfinished
+// (rows of seamv without a seam partner and the pad words of cseam are not written).  tup_tail_stream_r2_parts_fwd /
+// tup_tail_stream_r2_resize_parts_fwd (tail_stream.hip) add them, with decoder_conv2's bias, where they read the plane.
+extern "C" int tup_decoder_fused_parts_fwd(const void* x, const void* w1, const float* b1, const void* wz,
+                                           float* part, float* seamv, float* cseam, int B, int H, int W, void* stream)
+{
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return launch_decoder_parts(x, w1, b1, wz, part, seamv, cseam, B, H, W, stream);
 }

@@ -15,6 +15,11 @@
 // DPP wave shifts (v_mov_b32_dpp wave_shr:1 / wave_shl:1) and the 405 wave-uniform weights as scalar operands; per LR row and
 // lane 324 + 324 FMAs, 3 + 6 loads (requested one row ahead) and 6 stores; nothing is recomputed except two t1 rows per band.
 // HBM sees x, upscaled_input and out once each: bound = HBM / VALU issue, about equal.
+//
+// PARTS = true: x is not in HBM as a finished plane.  The kernel takes the pieces that decoder_fused_kernel (decoder_fused.hip) leaves
+// there -- part, seamv, cseam and decoder_conv2's bias -- and forms every LR value where it would have loaded it, in
+// decoder_finish_kernel's order of additions (so the value is the one that kernel would have written, bit for bit): the 0.27 GB
+// finishing pass between the two kernels does not run.
 #include "common.h"
 
 namespace {
@@ -37,6 +42,9 @@ struct TailStreamParams {
     const int* xmin; const int* xsize; const float* xw; int KX;
     const int* oxb; const int* oyb;
     int Ho, Wo, sc, ext;
+    // PARTS: x = part [B][3][H][W]; seamv [B][3][H][W], cseam [B][H][tilesX][2][4][4], b2 [3] as decoder_fused.hip describes them
+    const float* seamv; const float* cseam; const float* b2;
+    int tilesX;
 };
 
 // Neighbour exchange by DPP wave shifts, as volatile asm: the values are fetched where they are used (a handful of transient
@@ -59,7 +67,7 @@ TUP_DEVICE float from_right(float v) {    // lane l <- lane l + 1 (0 into lane 6
 
 // (the pointers are separate __restrict__ parameters: the weight reads inside the row loop stay scalar loads only while hipcc can
 // prove that the kernel's own stores do not alias them)
-template <bool RESIZE>
+template <bool RESIZE, bool PARTS>
 __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
     const float* __restrict__ x_arg, const float* __restrict__ wfu_arg, const float* __restrict__ bfu_arg,
     const float* __restrict__ wfc_arg, const float* __restrict__ bfc_arg, const float* __restrict__ ui_arg, float* __restrict__ out_arg,
@@ -102,6 +110,25 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ui_arg), 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(out_arg, 0, 0x7fffffff, 0x00020000);
     const unsigned vx = xc * 4u, vu = xc * 8u;
+    // PARTS: seamv is addressed as part is (same shape).  A lane's column is fixed, so is its role at a 32-column tile edge of the
+    // decoder: column 31 of a tile takes the next tile's column 0 (side 0), column 0 the previous tile's column 31 (side 1); the
+    // lane's cseam offset is that [tile][side] record (derived from xcol: with RESIZE the strips advance by sc < 60, so the edge
+    // lanes differ from strip to strip).  Other lanes read record 0 and drop the value.
+    __amdgpu_buffer_rsrc_t rsv = rx, rcs = rx;
+    unsigned vcs = 0u;
+    bool edge = false;
+    float b2v[3] = {0.f, 0.f, 0.f};
+    if constexpr (PARTS) {
+        rsv = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.seamv), 0, 0x7fffffff, 0x00020000);
+        rcs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.cseam), 0, 0x7fffffff, 0x00020000);
+        int ctile = -1, side = 0;
+        if ((xcol & 31) == 31 && xcol + 1 < W) ctile = (xcol >> 5) + 1;
+        else if ((xcol & 31) == 0 && xcol > 0) { ctile = (xcol >> 5) - 1; side = 1; }
+        edge = colok && ctile >= 0;
+        vcs = edge ? (unsigned)(ctile * 2 + side) * 64u : 0u;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) b2v[c] = p.b2[c];
+    }
 
     // ---- register windows, indexed by (LR row + 3) % 3 ----
     float X[3][3];                  // [slot][channel] LR values of this lane's column (neighbours by DPP at use)
@@ -110,7 +137,8 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
                                     // kernel into scratch, whose reloads wait on vmcnt behind the prefetched rows)
     // Loads in flight land in register PAIRS of their own: hipcc pairs neighbouring VGPRs into v_pk_fma_f32 operands, and a pair
     // with a pending load in its other half makes the instruction wait for that load (vmcnt(0) in the middle of stage B).
-    f32x2 xn[3];                    // [0] = LR row r + 2 of channel c, requested at the top of iteration r
+    f32x2 xn[3];                    // [0] = LR row r + 2 of channel c, requested at the top of iteration r (PARTS: [1] = its seamv)
+    float cn[3][3];                 // PARTS: [channel][dy] the column terms of LR row r + 2 (dec rows r + 1 .. r + 3), requested with xn
     f32x2 un[1][3][2];              // upscaled_input (HR rows 2q, 2q+1): requested at the end of iteration q (stage C of q - 1 has read the previous rows), used in q + 1
 
     // RESIZE state: the lane's output columns of the two gather passes with their first tap (as an index into the wave's LDS line),
@@ -148,18 +176,46 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
     };
     if constexpr (RESIZE) { if (oy < oy_end) fetch_row_taps(oy); }
 
-    auto load_x_row = [&](int row, f32x2 (&dst)[3]) __attribute__((always_inline)) {
+    auto load_x_row = [&](int row, f32x2 (&dst)[3], float (&cd)[3][3]) __attribute__((always_inline)) {
         const bool rok = row >= 0 && row < H;                     // wave-uniform
         const int rr = rok ? row : 0;
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
+        for (int c = 0; c < 3; ++c) {
             dst[c][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, vx, (((b * 3 + c) * H + rr) * W) * 4, 0));
+            if constexpr (PARTS)
+                dst[c][1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsv, vx, (((b * 3 + c) * H + rr) * W) * 4, 0));
+        }
+        if constexpr (PARTS) {
+            // dec row row + dy - 1 holds the dy term of this row (a row outside the image: any row, the value is dropped)
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy) {
+                const int yy = min(max(row + dy - 1, 0), H - 1);
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    cd[c][dy] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+                        rcs, vcs, ((b * H + yy) * p.tilesX * 32 + c * 4 + dy) * 4, 0));
+            }
+        }
     };
-    auto place_x_row = [&](int row, int slot, const f32x2 (&src)[3]) __attribute__((always_inline)) {
+    auto place_x_row = [&](int row, int slot, const f32x2 (&src)[3], const float (&cd)[3][3]) __attribute__((always_inline)) {
         const bool ok = colok && row >= 0 && row < H;
+        // PARTS: bias + part [+ seamv] [+ the three column terms], decoder_finish_kernel's order; an absent term is skipped, never
+        // added as +0 (a -0 sum stays -0)
+        const int ys = (row & 1) ? row + 1 : row - 1;             // the dec row whose wave wrote seamv for this row
+        const bool has_seam = ys >= 0 && ys < H;                  // wave-uniform
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            X[slot][c] = ok ? src[c][0] : 0.f;
+            float t = src[c][0];
+            if constexpr (PARTS) {
+                t = b2v[c] + t;
+                t = has_seam ? t + src[c][1] : t;
+#pragma unroll
+                for (int dy = 0; dy < 3; ++dy) {
+                    const bool cok = edge && row + dy - 1 >= 0 && row + dy - 1 < H;
+                    t = cok ? t + cd[c][dy] : t;
+                }
+            }
+            X[slot][c] = ok ? t : 0.f;
             asm volatile("" : "+v"(X[slot][c]));        // materialised HERE: see from_left
         }
     };
@@ -346,19 +402,20 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
     // requested an iteration ago); request the upscaled_input rows of LR row r; finally LR row r + 2 takes the slot of row r - 1
     auto iteration = [&](int r, int S) __attribute__((always_inline)) {
         const int SM = (S + 2) % 3, SP = (S + 1) % 3;
-        load_x_row(r + 2, xn);
+        load_x_row(r + 2, xn, cn);
         stages(r, SM, S, SP, r - 1 >= y0, 0);                  // T(r-2) lives in slot (r - 2 + 3) % 3 = SP, T(r-1) in SM, T(r) in S
         load_ui_rows(r, 0);
-        place_x_row(r + 2, SM, xn);
+        place_x_row(r + 2, SM, xn, cn);
     };
 
     // ---- prologue: LR rows y0-2, y0-1, y0 (for T(y0-1)); y0 % 3 == 0 (band_h is a multiple of 3), so the first iteration
     //      r = y0 - 1 has S = 2 ----
     {
         f32x2 t[3];
-        load_x_row(y0 - 2, t); place_x_row(y0 - 2, 1, t);       // (y0 - 2 + 3) % 3 = 1
-        load_x_row(y0 - 1, t); place_x_row(y0 - 1, 2, t);
-        load_x_row(y0, t);     place_x_row(y0, 0, t);
+        float tc[3][3];
+        load_x_row(y0 - 2, t, tc); place_x_row(y0 - 2, 1, t, tc);       // (y0 - 2 + 3) % 3 = 1
+        load_x_row(y0 - 1, t, tc); place_x_row(y0 - 1, 2, t, tc);
+        load_x_row(y0, t, tc);     place_x_row(y0, 0, t, tc);
 #pragma unroll
         for (int s = 0; s < 3; ++s)
 #pragma unroll
@@ -380,24 +437,32 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
 }  // namespace
 
 namespace {
-int launch_tail_stream(TailStreamParams& p, const float* x, const float* wfu_t, const float* bfu, const float* wfc_t, const float* bfc,
-                       const float* ui, float* out, bool resize, void* stream)
+// the unfinished decoder output (PARTS) in place of x: what tup_decoder_fused_parts_fwd left in HBM
+struct TailParts { const float* part; const float* seamv; const float* cseam; const float* b2; int tilesX; };
+
+int launch_tail_stream(TailStreamParams& p, const float* x, const TailParts* parts, const float* wfu_t, const float* bfu,
+                       const float* wfc_t, const float* bfc, const float* ui, float* out, bool resize, void* stream)
 {
     const long long waves = (long long)p.B * p.nstrip * p.nband;
     if (waves > (1ll << 30) || (long long)p.B * 3 * 4 * p.H * p.W >= (1ll << 29)) return (int)hipErrorInvalidValue;     // 32-bit byte offsets
+    if (parts) {
+        // seamv has part's shape (covered above); cseam is [B][H][tilesX][32] floats behind 32-bit byte offsets as well
+        if (parts->tilesX != (p.W + 31) / 32 || (long long)p.B * p.H * parts->tilesX * 32 >= (1ll << 29)) return (int)hipErrorInvalidValue;
+        x = parts->part;
+        p.seamv = parts->seamv; p.cseam = parts->cseam; p.b2 = parts->b2; p.tilesX = parts->tilesX;
+    }
     const dim3 grid((unsigned)((waves + 3) / 4));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (resize) tail_stream_r2_kernel<true><<<grid, dim3(256), 0, s>>>(x, wfu_t, bfu, wfc_t, bfc, ui, out, p);
-    else tail_stream_r2_kernel<false><<<grid, dim3(256), 0, s>>>(x, wfu_t, bfu, wfc_t, bfc, ui, out, p);
+    if (resize && parts) tail_stream_r2_kernel<true, true><<<grid, dim3(256), 0, s>>>(x, wfu_t, bfu, wfc_t, bfc, ui, out, p);
+    else if (resize) tail_stream_r2_kernel<true, false><<<grid, dim3(256), 0, s>>>(x, wfu_t, bfu, wfc_t, bfc, ui, out, p);
+    else if (parts) tail_stream_r2_kernel<false, true><<<grid, dim3(256), 0, s>>>(x, wfu_t, bfu, wfc_t, bfc, ui, out, p);
+    else tail_stream_r2_kernel<false, false><<<grid, dim3(256), 0, s>>>(x, wfu_t, bfu, wfc_t, bfc, ui, out, p);
     TUP_CHECK_LAUNCH();
     return 0;
 }
-}  // namespace
 
-// x fp32 [B][3][H][W]; wfu_t fp32 [27][12], bfu [12]; wfc_t fp32 [27][4], bfc [3] (packing.pack_planar_t);
-// ui / out fp32 [B][3][2H][2W].  r = 2 only; any H, W >= 1.
-extern "C" int tup_tail_stream_r2_fwd(const float* x, const float* wfu_t, const float* bfu, const float* wfc_t, const float* bfc,
-                                      const float* ui, float* out, int B, int H, int W, int clamp01, void* stream)
+int tail_stream_plain(const float* x, const TailParts* parts, const float* wfu_t, const float* bfu, const float* wfc_t, const float* bfc,
+                      const float* ui, float* out, int B, int H, int W, int clamp01, void* stream)
 {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
     TailStreamParams p{};
@@ -415,7 +480,35 @@ extern "C" int tup_tail_stream_r2_fwd(const float* x, const float* wfu_t, const 
         p.band_h = bh;
         p.nband = (H + bh - 1) / bh;
     }
-    return launch_tail_stream(p, x, wfu_t, bfu, wfc_t, bfc, ui, out, false, stream);
+    return launch_tail_stream(p, x, parts, wfu_t, bfu, wfc_t, bfc, ui, out, false, stream);
+}
+
+int tail_stream_resize(const float* x, const TailParts* parts, const float* wfu_t, const float* bfu, const float* wfc_t, const float* bfc,
+                       const float* ui, float* out, const int* ymin, const int* ysize, const float* yw, int KY,
+                       const int* xmin, const int* xsize, const float* xw, int KX, const int* oxb, const int* oyb,
+                       int B, int H, int W, int Ho, int Wo, int sc, int band_h, int ext, int clamp01, void* stream)
+{
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    if (sc < 1 || sc > TS_COLS || band_h < 3 || band_h % 3 != 0 || ext < 0 || ext > 2 || Ho < 1 || Wo < 1 || KX < 1 || KY < 1)
+        return (int)hipErrorInvalidValue;
+    if ((long long)B * 3 * Ho * Wo >= (1ll << 29)) return (int)hipErrorInvalidValue;
+    TailStreamParams p{};
+    p.B = B; p.H = H; p.W = W; p.clamp01 = clamp01;
+    p.nstrip = (W + sc - 1) / sc;
+    p.band_h = band_h;
+    p.nband = (H + band_h - 1) / band_h;
+    p.ymin = ymin; p.ysize = ysize; p.yw = yw; p.KY = KY; p.xmin = xmin; p.xsize = xsize; p.xw = xw; p.KX = KX;
+    p.oxb = oxb; p.oyb = oyb; p.Ho = Ho; p.Wo = Wo; p.sc = sc; p.ext = ext;
+    return launch_tail_stream(p, x, parts, wfu_t, bfu, wfc_t, bfc, ui, out, true, stream);
+}
+}  // namespace
+
+// x fp32 [B][3][H][W]; wfu_t fp32 [27][12], bfu [12]; wfc_t fp32 [27][4], bfc [3] (packing.pack_planar_t);
+// ui / out fp32 [B][3][2H][2W].  r = 2 only; any H, W >= 1.
+extern "C" int tup_tail_stream_r2_fwd(const float* x, const float* wfu_t, const float* bfu, const float* wfc_t, const float* bfc,
+                                      const float* ui, float* out, int B, int H, int W, int clamp01, void* stream)
+{
+    return tail_stream_plain(x, nullptr, wfu_t, bfu, wfc_t, bfc, ui, out, B, H, W, clamp01, stream);
 }
 
 // The same followed by the antialiased Resize to Ho x Wo (model.py:323-325) and the clamp: out fp32 [B][3][Ho][Wo].
@@ -429,16 +522,29 @@ extern "C" int tup_tail_stream_r2_resize_fwd(const float* x, const float* wfu_t,
                                              const int* xmin, const int* xsize, const float* xw, int KX, const int* oxb, const int* oyb,
                                              int B, int H, int W, int Ho, int Wo, int sc, int band_h, int ext, int clamp01, void* stream)
 {
-    if (B <= 0 || H <= 0 || W <= 0) return 0;
-    if (sc < 1 || sc > TS_COLS || band_h < 3 || band_h % 3 != 0 || ext < 0 || ext > 2 || Ho < 1 || Wo < 1 || KX < 1 || KY < 1)
-        return (int)hipErrorInvalidValue;
-    if ((long long)B * 3 * Ho * Wo >= (1ll << 29)) return (int)hipErrorInvalidValue;
-    TailStreamParams p{};
-    p.B = B; p.H = H; p.W = W; p.clamp01 = clamp01;
-    p.nstrip = (W + sc - 1) / sc;
-    p.band_h = band_h;
-    p.nband = (H + band_h - 1) / band_h;
-    p.ymin = ymin; p.ysize = ysize; p.yw = yw; p.KY = KY; p.xmin = xmin; p.xsize = xsize; p.xw = xw; p.KX = KX;
-    p.oxb = oxb; p.oyb = oyb; p.Ho = Ho; p.Wo = Wo; p.sc = sc; p.ext = ext;
-    return launch_tail_stream(p, x, wfu_t, bfu, wfc_t, bfc, ui, out, true, stream);
+    return tail_stream_resize(x, nullptr, wfu_t, bfu, wfc_t, bfc, ui, out, ymin, ysize, yw, KY, xmin, xsize, xw, KX, oxb, oyb,
+                              B, H, W, Ho, Wo, sc, band_h, ext, clamp01, stream);
+}
+
+// The two entries above with the decoder's unfinished output in place of x (tup_decoder_fused_parts_fwd: part, seamv fp32
+// [B][3][H][W], cseam fp32 [B][H][tilesX][32], tilesX = ceil(W / 32)) and decoder_conv2's bias b2 fp32 [3]: the kernel adds the pieces
+// in decoder_finish_kernel's order where it would have loaded x, so the result equals that of the finished plane bit for bit.
+extern "C" int tup_tail_stream_r2_parts_fwd(const float* part, const float* seamv, const float* cseam, const float* b2, int tilesX,
+                                            const float* wfu_t, const float* bfu, const float* wfc_t, const float* bfc,
+                                            const float* ui, float* out, int B, int H, int W, int clamp01, void* stream)
+{
+    const TailParts parts{part, seamv, cseam, b2, tilesX};
+    return tail_stream_plain(nullptr, &parts, wfu_t, bfu, wfc_t, bfc, ui, out, B, H, W, clamp01, stream);
+}
+
+extern "C" int tup_tail_stream_r2_resize_parts_fwd(const float* part, const float* seamv, const float* cseam, const float* b2, int tilesX,
+                                                   const float* wfu_t, const float* bfu, const float* wfc_t, const float* bfc,
+                                                   const float* ui, float* out, const int* ymin, const int* ysize, const float* yw, int KY,
+                                                   const int* xmin, const int* xsize, const float* xw, int KX, const int* oxb,
+                                                   const int* oyb, int B, int H, int W, int Ho, int Wo, int sc, int band_h, int ext,
+                                                   int clamp01, void* stream)
+{
+    const TailParts parts{part, seamv, cseam, b2, tilesX};
+    return tail_stream_resize(nullptr, &parts, wfu_t, bfu, wfc_t, bfc, ui, out, ymin, ysize, yw, KY, xmin, xsize, xw, KX, oxb, oyb,
+                              B, H, W, Ho, Wo, sc, band_h, ext, clamp01, stream);
 }

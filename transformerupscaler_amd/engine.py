@@ -65,6 +65,9 @@ fuse_decoder = True
 # inference (A/B attribute): conv1 recomputed per conv2 tile inside conv2's idle wave group from a compact bf16 copy of the input
 # (csrc/conv12_fused.hip); the 64-channel conv1 map never reaches HBM
 fuse_conv12 = True
+# inference (A/B attribute): at scale 2 the streaming tail reads `residual` straight from the fused decoder, so the decoder's finishing
+# launch does not run and the tail adds the unfinished pieces where it reads them (csrc/tail_stream.hip, PARTS).  Bit-identical.
+fuse_decoder_finish = True
 
 
 def _block_operands(pk, i, bias_frags):
@@ -172,9 +175,21 @@ def forward(pk: Dict[str, torch.Tensor], bias_frags, x: torch.Tensor, scale: int
         xw = transformer_blocks(pk, xw, bias_frags, cap, bf16_out=cap is None)
     with _stage("unembed"):
         combined = ops.patch_unembed(xw, pk["pu.w"], pk["pu.b"], feat)
+    hs, ws = H * scale, W * scale
+    # model.py:323: `res_out != (out.shape[2], out.shape[2])` -- the (H, H) quirk is kept; Resize to an
+    # identical size is the identity.
+    needs_resize = bool(require_ratio) and tuple(res_out) != (hs, hs) and tuple(res_out) != (hs, ws)
+    fu = upsampler_layout(scale)
+    tail_out_hw = tuple(res_out) if needs_resize else None
+    parts = None
     if fuse_decoder and fuse_tail and cap is None and "dec2.wz" in pk:
+        # the streaming tail is the decoder's only reader (one final_upscale stage of x2): it takes the unfinished pieces
+        unfinished = (fuse_decoder_finish and stream_tail and len(fu) == 1 and fu[0][1] == 2 and "tail.wfu_t" in pk
+                      and ops.tail_stream_fits(B, H, W, tail_out_hw))
         with _stage("decoder"):
-            residual = ops.decoder_fused(combined, pk["dec1.w"], pk["dec1.b"], pk["dec2.wz"], pk["dec2.b"])
+            residual = ops.decoder_fused(combined, pk["dec1.w"], pk["dec1.b"], pk["dec2.wz"], pk["dec2.b"], finish=not unfinished)
+        if unfinished:
+            parts, residual = residual, residual[0]
     else:
         with _stage("dec1"):
             dec = ops.conv_c64(combined, pk["dec1.w"], pk["dec1.b"], 1, relu=True)
@@ -183,24 +198,23 @@ def forward(pk: Dict[str, torch.Tensor], bias_frags, x: torch.Tensor, scale: int
     if cap is not None:
         cap["combined"] = combined; cap["dec"] = dec; cap["residual"] = residual
     t = residual
-    hs, ws = H * scale, W * scale
-    # model.py:323: `res_out != (out.shape[2], out.shape[2])` -- the (H, H) quirk is kept; Resize to an
-    # identical size is the identity.
-    needs_resize = bool(require_ratio) and tuple(res_out) != (hs, hs) and tuple(res_out) != (hs, ws)
-    fu = upsampler_layout(scale)
     if fuse_tail and cap is None:
         for si, (_, r) in enumerate(fu[:-1]):
             t = ops.conv_planar(t, pk[f"fu.{si}.w"], pk[f"fu.{si}.b"], r)
         li = len(fu) - 1
         if (stream_tail and fu[li][1] == 2 and "tail.wfu_t" in pk
-                and ops.tail_stream_fits(t.shape[0], t.shape[2], t.shape[3], tuple(res_out) if needs_resize else None)):
+                and ops.tail_stream_fits(t.shape[0], t.shape[2], t.shape[3], tail_out_hw)):
+            # (parts: `t` is then the unfinished `part` plane, which the kernel reads with the other pieces; they stay referenced
+            # by `parts` until the tail is enqueued)
             with _stage("tail"):
                 out = ops.tail_stream_r2(t, pk["tail.wfu_t"], pk[f"fu.{li}.b"], pk["tail.wfc_t"], pk["fuc.b"], upscaled_input,
-                                         clamp=True, out_hw=tuple(res_out) if needs_resize else None)
+                                         clamp=True, out_hw=tail_out_hw, parts=parts)
                 if out is None:        # a Resize with more than 4 taps per output: pre-resize sums, then the separable Resize kernel
-                    out = ops.tail_stream_r2(t, pk["tail.wfu_t"], pk[f"fu.{li}.b"], pk["tail.wfc_t"], pk["fuc.b"], upscaled_input, clamp=False)
+                    out = ops.tail_stream_r2(t, pk["tail.wfu_t"], pk[f"fu.{li}.b"], pk["tail.wfc_t"], pk["fuc.b"], upscaled_input,
+                                             clamp=False, parts=parts)
                     out = ops.resize_aa(out, tuple(res_out), clamp=True)
             return out
+        assert parts is None       # the unfinished pieces go to the streaming tail only
         with _stage("tail"):
             out = ops.tail_fused(t, pk[f"fu.{li}.w"], pk[f"fu.{li}.b"], pk["fuc.w"], pk["fuc.b"], upscaled_input, fu[li][1],
                                  tuple(res_out) if needs_resize else (hs, ws), clamp=True)

@@ -144,14 +144,22 @@ def conv_c64_thin(x, wp, bias, cout, relu=False, out=None):
     return out
 
 
-def decoder_fused(x, w1, b1, wz, b2):
+def decoder_fused(x, w1, b1, wz, b2, finish=True):
     """decoder_conv1 (64->64, +bias, ReLU) + decoder_conv2 (64->3, +bias) without the 64-channel map in HBM:
-    NHWC bf16 [B][H][W][64] -> fp32 planar [B][3][H][W] (csrc/decoder_fused.hip)."""
+    NHWC bf16 [B][H][W][64] -> fp32 planar [B][3][H][W] (csrc/decoder_fused.hip).
+    finish=False: the finishing launch does not run; returns the unfinished pieces (part, seamv, cseam, b2) that
+    tail_stream_r2(parts=...) adds up where it reads the plane."""
     B, H, W, C = x.shape
     assert C == 64
     out = torch.empty((B, 3, H, W), dtype=F32, device=x.device)
     seamv = torch.empty((B, 3, H, W), dtype=F32, device=x.device)
     cseam = torch.empty((B, H, (W + 31) // 32, 32), dtype=F32, device=x.device)
+    if not finish:
+        _chk(b2, F32, (3,), "b2")
+        _lib.call("tup_decoder_fused_parts_fwd", _chk(x, BF16, None, "x"), _chk(w1, BF16, (1, 1, 9, 64, 64), "w1"),
+                  _chk(b1, F32, (1, 64), "b1"), _chk(wz, BF16, (48, 64), "wz"), out.data_ptr(), seamv.data_ptr(), cseam.data_ptr(),
+                  B, H, W, _stream())
+        return out, seamv, cseam, b2
     _lib.call("tup_decoder_fused_fwd", _chk(x, BF16, None, "x"), _chk(w1, BF16, (1, 1, 9, 64, 64), "w1"), _chk(b1, F32, (1, 64), "b1"),
               _chk(wz, BF16, (48, 64), "wz"), _chk(b2, F32, (3,), "b2"), seamv.data_ptr(), cseam.data_ptr(), out.data_ptr(),
               B, H, W, _stream())
@@ -236,7 +244,7 @@ def tail_fused(x, wfu, bfu, wfc, bfc, ui, r, out_hw, clamp=True):
     return out
 
 
-TAIL_STREAM_WAVES_PER_SIMD = 3      # csrc/tail_stream.hip: 150 registers, 52 KB of LDS per four-wave workgroup
+TAIL_STREAM_WAVES_PER_SIMD = 3      # csrc/tail_stream.hip: 150 registers (152 on unfinished decoder pieces), 52 KB of LDS per four-wave workgroup
 
 
 def _tail_stream_plan(device, B, H, W, Ho, Wo):
@@ -285,23 +293,36 @@ def tail_stream_fits(B, H, W, out_hw=None):
     return True
 
 
-def tail_stream_r2(x, wfu_t, bfu, wfc_t, bfc, ui, clamp=True, out_hw=None):
+def tail_stream_r2(x, wfu_t, bfu, wfc_t, bfc, ui, clamp=True, out_hw=None, parts=None):
     """Last final_upscale stage (r = 2) + final_upscale_conv + "+ upscaled_input" [+ antialiased Resize to out_hw] [+ clamp],
-    streaming kernel.  Returns None when out_hw needs a Resize whose tap tables the fused kernel does not take (> 4 taps)."""
-    B, C, H, W = x.shape
-    args = (_chk(x, F32, (B, 3, H, W), "x"), _chk(wfu_t, F32, (27, 12), "wfu_t"), _chk(bfu, F32, (12,), "bfu"),
-            _chk(wfc_t, F32, (27, 4), "wfc_t"), _chk(bfc, F32, (3,), "bfc"), _chk(ui, F32, (B, 3, 2 * H, 2 * W), "ui"))
+    streaming kernel.  Returns None when out_hw needs a Resize whose tap tables the fused kernel does not take (> 4 taps).
+    parts = decoder_fused(..., finish=False): the kernel forms x from the unfinished pieces as it reads them (x may be None); the
+    result equals that of the finished plane bit for bit."""
+    if parts is not None:
+        part, seamv, cseam, b2 = parts
+        B, C, H, W = part.shape
+        dev, tiles_x = part.device, (W + 31) // 32
+        head = (_chk(part, F32, (B, 3, H, W), "part"), _chk(seamv, F32, (B, 3, H, W), "seamv"),
+                _chk(cseam, F32, (B, H, tiles_x, 32), "cseam"), _chk(b2, F32, (3,), "b2"), tiles_x)
+        suffix = "_parts_fwd"
+    else:
+        B, C, H, W = x.shape
+        dev = x.device
+        head = (_chk(x, F32, (B, 3, H, W), "x"),)
+        suffix = "_fwd"
+    args = head + (_chk(wfu_t, F32, (27, 12), "wfu_t"), _chk(bfu, F32, (12,), "bfu"),
+                   _chk(wfc_t, F32, (27, 4), "wfc_t"), _chk(bfc, F32, (3,), "bfc"), _chk(ui, F32, (B, 3, 2 * H, 2 * W), "ui"))
     if out_hw is None or tuple(out_hw) == (2 * H, 2 * W):
-        out = torch.empty((B, 3, 2 * H, 2 * W), dtype=F32, device=x.device)
-        _lib.call("tup_tail_stream_r2_fwd", *args, out.data_ptr(), B, H, W, int(clamp), _stream())
+        out = torch.empty((B, 3, 2 * H, 2 * W), dtype=F32, device=dev)
+        _lib.call("tup_tail_stream_r2" + suffix, *args, out.data_ptr(), B, H, W, int(clamp), _stream())
         return out
     Ho, Wo = int(out_hw[0]), int(out_hw[1])
-    plan = _tail_stream_plan(x.device, B, H, W, Ho, Wo)
+    plan = _tail_stream_plan(dev, B, H, W, Ho, Wo)
     if plan is None:
         return None
     ylo, yn, yw, ky, xlo, xn, xw, kx, oxb, oyb, sc, bh, ext = plan
-    out = torch.empty((B, 3, Ho, Wo), dtype=F32, device=x.device)
-    _lib.call("tup_tail_stream_r2_resize_fwd", *args, out.data_ptr(), ylo.data_ptr(), yn.data_ptr(), yw.data_ptr(), ky,
+    out = torch.empty((B, 3, Ho, Wo), dtype=F32, device=dev)
+    _lib.call("tup_tail_stream_r2_resize" + suffix, *args, out.data_ptr(), ylo.data_ptr(), yn.data_ptr(), yw.data_ptr(), ky,
               xlo.data_ptr(), xn.data_ptr(), xw.data_ptr(), kx, oxb.data_ptr(), oyb.data_ptr(), B, H, W, Ho, Wo, sc, bh, ext,
               int(clamp), _stream())
     return out
