@@ -599,6 +599,16 @@ int tup_grad_sumsq_partial(const void* segs, const int* chunks, int nchunks, dou
 int tup_grad_guard_finish(const double* partials, int npartials, double max_norm, int skip_nonfinite, void* guard, void* stream);
 int tup_adam_step_guarded(const void* segs, const int* chunks, int nchunks, const void* guard, void* stream);
 
+/* The optimizer step with an exponential moving average of the weights in the same launch (csrc/step_guard.hip).  segs: device array
+ * [nseg] of 88-byte records {float* p; const float* g; float* m; float* v; long long n; float step_size, bc2, beta2, 1 - beta1,
+ * 1 - beta2, eps, wd_l2, decay; float* e; float ema_w; int form}.  form 0: p, m, v are updated with tup_adam_step's arithmetic (bc2 =
+ * 1 / sqrt(bias_correction2); wd_l2 and decay are not read), form 1: with tup_adam_step_guarded's (bc2 = sqrt(bias_correction2)); in
+ * both they come out bit-equal to that entry's.  Then e = e + ema_w * (p - e) on the new p, as three separately rounded fp32
+ * operations (sub, mul, add).  g == NULL: the parameter has no gradient in this step; e alone is updated, p is only read, m and v
+ * are not touched.  chunks as for tup_adam_step; guard as for tup_adam_step_guarded (NULL: apply, coef = 1); apply == 0: p, m, v
+ * and e are not written.  e must not overlap p, g, m or v. */
+int tup_adam_step_ema(const void* segs, const int* chunks, int nchunks, const void* guard, void* stream);
+
 /* Patch training samples of a whole batch in one launch (data.PatchSampler; csrc/patch_pairs.hip).  recs: device array [B] of 32-byte
  * records {const uint8_t* frame; int H; int W; int y0; int x0; int op; int reserved}, frame a contiguous uint8 [H][W][3] RGB image.
  * Per record, bit-exact: t = frame[y0:y0+P, x0:x0+P]; op & 1: t = t[:, ::-1]; op & 2: t = t[::-1]; op & 4: t = t.transpose(1, 0, 2)

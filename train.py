@@ -36,6 +36,18 @@ What differs from the reference driver:
   ``--patches_per_epoch`` sets the epoch length (default: the whole-frame dataset's).  Sample g of a run is a function of
   ``(--seed, g)`` alone, so resumed runs and ranks need no generator state.  ``--pairs`` does not apply; ResidualTransformer (fixed
   720x1280 input) cannot train on patches.  The ``--json`` record gains ``patch``.
+* ``--ema_decay D`` keeps an exponential moving average of the weights inside the fused optimizer step (``--ema_warmup``: timm's
+  warm-up of the decay); a step skipped by ``--skip_nonfinite`` does not move it.  Every checkpoint then also writes
+  ``<checkpoint_dir>/ema/model_epoch_<N>.pth`` (the weight file's format: ``ab_test.py --checkpoint_dir_a .../ema`` loads it) and a
+  sidecar ``ema/ema_epoch_<N>.pt``; a resumed run loads both, or restarts the average from the loaded weights and says so.
+  The sidecar also holds the model's dropout call count, so that with ``--save_optimizer`` a resumed single-process run continues
+  bit for bit where the saved one stood.
+* ``--val_dir DIR`` scores a held-out directory after every ``--val_interval`` epochs (``harness.evaluate``: the training step's
+  forward on full images under the pairs of ``--val_pairs``, default ``--pairs`` or the dataset's ten; ``--val_images K``: the
+  first K files): L1, MSE, PSNR, SSIM in one printed line and a ``val`` entry of the ``--json`` record.  With ``--ema_decay`` the
+  averaged weights are scored (``--val_both``: the raw ones too).  ``--keep_best {psnr,ssim,l1}`` keeps
+  ``<checkpoint_dir>/best/model_epoch_<N>.pth`` of the best validated weights so far (record ``best``).  The validation set takes
+  half of the ``--cache_gb`` budget.
 * ``--traceback`` is accepted; the reference's traceback window is not available here.
 * With ``WORLD_SIZE > 1`` in the environment (torchrun) the run is data parallel: every rank shuffles with the same seed and
   trains ``batch[rank::world]``; the gradients of a step are all-reduced once.
@@ -46,6 +58,7 @@ import json
 import math
 import os
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -85,6 +98,14 @@ def build_parser():
     p.add_argument("--patch_scales", type=str, default="2,3,4,6", help="Scales the patches are drawn from (with --patch_size)")
     p.add_argument("--no_augment", action="store_true", help="No flip / rotate variants of the patches (with --patch_size)")
     p.add_argument("--patches_per_epoch", type=int, default=None, help="Samples per epoch with --patch_size (default: the dataset's)")
+    p.add_argument("--ema_decay", type=float, default=None, help="Keep an exponential moving average of the weights with this decay")
+    p.add_argument("--ema_warmup", action="store_true", help="Warm the EMA decay up: min(decay, (1 + n) / (10 + n)) (with --ema_decay)")
+    p.add_argument("--val_dir", type=str, default=None, help="Directory of held-out images (.png) scored after an epoch")
+    p.add_argument("--val_interval", type=int, default=1, help="Validate every N epochs (with --val_dir)")
+    p.add_argument("--val_pairs", type=str, default=None, help='Scale pairs of the validation set (default: --pairs, else the ten)')
+    p.add_argument("--val_images", type=int, default=None, help="Validate on the first K files of --val_dir in sorted order")
+    p.add_argument("--val_both", action="store_true", help="With --ema_decay: score the raw weights as well as the averaged ones")
+    p.add_argument("--keep_best", choices=("psnr", "ssim", "l1"), default=None, help="Keep best/model_epoch_<N>.pth by this validation metric")
     return p
 
 
@@ -144,6 +165,25 @@ def patch_options(args):
     return args.patch_size, scales
 
 
+def val_options(args):
+    """The EMA and validation options, checked before anything touches the GPU; True if the run validates."""
+    if args.val_dir is None:
+        if (args.val_interval != 1 or args.val_pairs is not None or args.val_images is not None or args.val_both
+                or args.keep_best is not None):
+            sys.exit("train.py: --val_interval, --val_pairs, --val_images, --val_both and --keep_best need --val_dir")
+    if args.ema_decay is None and (args.val_both or args.ema_warmup):
+        sys.exit("train.py: --val_both and --ema_warmup need --ema_decay")
+    if args.ema_decay is not None and not 0.0 <= args.ema_decay < 1.0:
+        sys.exit(f"train.py: --ema_decay {args.ema_decay} must be in [0, 1)")
+    if args.val_interval < 1:
+        sys.exit("train.py: --val_interval must be >= 1")
+    if args.val_images is not None and args.val_images < 1:
+        sys.exit("train.py: --val_images must be >= 1")
+    if args.val_dir is not None and not os.path.isdir(args.val_dir):
+        sys.exit(f"train.py: --val_dir {args.val_dir!r} is not a directory")
+    return args.val_dir is not None
+
+
 def epoch_batches(n_samples, batch_size, generator):
     """The shuffled batches of one epoch (index lists); a last partial batch is kept (DataLoader's drop_last=False)."""
     import torch
@@ -157,11 +197,19 @@ def run(args):
     if args.batch_size < 1:
         sys.exit("train.py: --batch_size must be >= 1")
     patch = patch_options(args)
+    validating = val_options(args)
+    ema = args.ema_decay is not None
     import torch
 
     from transformerupscaler_amd import harness, ops
-    from transformerupscaler_amd.data import SCALE_PAIRS, PairDataset, PatchSampler, parse_pairs
+    from transformerupscaler_amd.data import SCALE_PAIRS, PairDataset, PatchSampler, parse_pairs, sample_plan
 
+    val_pairs = None
+    if validating:
+        try:
+            val_pairs = parse_pairs(args.val_pairs) if args.val_pairs else (parse_pairs(args.pairs) if args.pairs else SCALE_PAIRS)
+        except ValueError as e:
+            sys.exit(f"train.py: {e}")
     if args.checkpoint_dir is None:
         args.checkpoint_dir = os.path.join("models", args.model, "checkpoints")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -169,7 +217,8 @@ def run(args):
     if world > 1:
         import torch.distributed as dist
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
-        dist.init_process_group("nccl")
+        if not dist.is_initialized():                                     # a caller may have set a group up (two ranks on one GPU: gloo)
+            dist.init_process_group("nccl")
         rank = dist.get_rank()
     device = torch.device("cuda", torch.cuda.current_device())
     say = print if rank == 0 else (lambda *a, **k: None)
@@ -182,12 +231,21 @@ def run(args):
     if not any(p.requires_grad for p in model.parameters()):
         sys.exit(f"train.py: model {args.model} has no trainable parameter; there is nothing to train")
     model = model.to(device)
-    optimizer = harness.make_optimizer(model, lr=args.lr, weight_decay=args.weight_decay, decoupled=args.adamw,
-                                       max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
+    options = dict(lr=args.lr, weight_decay=args.weight_decay, decoupled=args.adamw, max_grad_norm=args.clip_grad_norm,
+                   skip_nonfinite=args.skip_nonfinite)
+    optimizer = harness.make_ema_optimizer(model, args.ema_decay, args.ema_warmup, **options) if ema \
+        else harness.make_optimizer(model, **options)
     epochs_trained = harness.load_latest_checkpoint(model, args.checkpoint_dir, optimizer if args.save_optimizer else None,
                                                     map_location=device)
     if epochs_trained:
         say(f"Resuming from epoch {epochs_trained} of {args.checkpoint_dir}")
+        if ema:
+            side = harness.load_ema_checkpoint(model, args.checkpoint_dir, epochs_trained, optimizer, map_location=device)
+            if side is None:
+                say(f"No averaged weights of epoch {epochs_trained} in {os.path.join(args.checkpoint_dir, 'ema')}: "
+                    "the average restarts from the loaded weights")
+            elif side.get("dropout_calls") is not None and hasattr(model, "_dropout_calls"):
+                model._dropout_calls = side["dropout_calls"]              # the dropout masks continue where the saved run stood
         if epochs_trained >= args.epochs:
             sys.exit(f"train.py: the latest checkpoint in {args.checkpoint_dir} is of epoch {epochs_trained}, "
                      f"which is not below --epochs {args.epochs}")
@@ -203,16 +261,27 @@ def run(args):
         else:
             dp = DataParallel(model)                                      # every parameter is active in every step
 
+    cache_bytes = int(args.cache_gb * (1 << 30))
+    val_set = None
+    if validating:                                                        # full images, also in patch mode; half of the cache budget
+        cache_bytes //= 2
+        try:
+            val_set = PairDataset(args.val_dir, val_pairs, cache_bytes=cache_bytes, device=device)
+        except FileNotFoundError as e:
+            sys.exit(f"train.py: {e}")
+        if args.val_images is not None:                                   # the first K files in sorted order
+            val_set.files = val_set.files[:args.val_images]
+            val_set.plan = sample_plan(len(val_set.files), len(val_set.scale_pairs))
     if patch is not None:
         pairs = None
         try:
             dataset = PatchSampler(args.data_dir, patch=patch[0], scales=patch[1], augment=not args.no_augment, seed=args.seed,
-                                   samples_per_epoch=args.patches_per_epoch, cache_bytes=int(args.cache_gb * (1 << 30)), device=device)
+                                   samples_per_epoch=args.patches_per_epoch, cache_bytes=cache_bytes, device=device)
         except ValueError as e:
             sys.exit(f"train.py: {e}")
     else:
         pairs = parse_pairs(args.pairs) if args.pairs else SCALE_PAIRS
-        dataset = PairDataset(args.data_dir, pairs, cache_bytes=int(args.cache_gb * (1 << 30)), device=device)
+        dataset = PairDataset(args.data_dir, pairs, cache_bytes=cache_bytes, device=device)
     criterion = None
     if not pure_l1(args):
         from transformerupscaler_amd.losses import QualityLoss
@@ -220,6 +289,9 @@ def run(args):
     what = (f"{len(pairs)} scale pairs" if patch is None else
             f"{patch[0]}x{patch[0]} patches at scales {list(patch[1])}" + ("" if dataset.augment else ", no augmentation"))
     say(f"{len(dataset)} samples from {len(dataset.files)} images, {what}; loss {'L1' if criterion is None else criterion}")
+    if validating:
+        say(f"Validation: {len(val_set)} samples from {len(val_set.files)} images of {args.val_dir}, {len(val_pairs)} scale pairs, "
+            f"{'averaged' if ema else 'raw'} weights" + (" and raw weights" if args.val_both else ""))
 
     shuffle = torch.Generator().manual_seed(args.seed)
     for _ in range(epochs_trained):                                       # a resumed run continues the shuffle sequence
@@ -229,6 +301,43 @@ def run(args):
     if patch is not None:
         record["patch"] = {"size": patch[0], "scales": list(patch[1]), "augment": dataset.augment,
                            "samples_per_epoch": dataset.samples_per_epoch}
+    if validating:
+        record["val"] = []
+    if args.keep_best:
+        record["best"] = None
+
+    def validate(epoch, weights):
+        """One scored pass over the validation set on the averaged or the raw weights: a printed line and a record entry."""
+        t0 = time.perf_counter()
+        if weights == "ema":
+            with harness.ema_weights(model, optimizer):
+                res = harness.evaluate(model, val_set, group=not args.no_group)
+        else:
+            res = harness.evaluate(model, val_set, group=not args.no_group)
+        seconds = time.perf_counter() - t0                                # evaluate ends with its read-back: the GPU is done
+        entry = {"epoch": epoch, "weights": weights, "l1": res["l1"], "mse": res["mse"], "psnr": res["psnr"], "ssim": res["ssim"],
+                 "per_pair": res["per_pair"], "seconds": seconds}
+        record["val"].append(entry)
+        say(f"Epoch [{epoch}/{args.epochs}] Validation ({weights}, {res['samples']} samples): L1 {res['l1']:.6f} MSE {res['mse']:.6e} "
+            f"PSNR {res['psnr']:.3f} dB SSIM {res['ssim']:.5f} ({seconds:.2f} s)")
+        return entry
+
+    def keep_best(entry):
+        """Rank 0 keeps one file: the validated weights of the best epoch so far by --keep_best."""
+        value, best = entry[args.keep_best], record["best"]
+        better = best is None or (value < best["value"] if args.keep_best == "l1" else value > best["value"])
+        if not better:
+            return
+        path = os.path.join(args.checkpoint_dir, "best", f"model_epoch_{entry['epoch']}.pth")
+        if rank == 0:
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            sd = optimizer.ema_state_dict(model) if entry["weights"] == "ema" else model.state_dict()
+            torch.save({k: v.detach().cpu() for k, v in sd.items()}, path)
+            if best is not None and best["path"] != path and os.path.exists(best["path"]):
+                os.remove(best["path"])                                   # the single file is replaced
+            say(f"Kept best checkpoint ({args.keep_best} {value:.6f}): {path}")
+        record["best"] = {"epoch": entry["epoch"], "metric": args.keep_best, "value": value, "weights": entry["weights"], "path": path}
+
     timed = []                                                            # patch mode: (start, sampler done, step done) events
     steps_done = 0
     stop = False
@@ -286,9 +395,17 @@ def run(args):
             avg = torch.stack(losses).mean().item()
             say(f"Epoch [{epoch + 1}/{args.epochs}] completed. Average Loss: {avg:.6f}")
             record["epochs"].append({"epoch": epoch + 1, "steps": len(losses), "average_loss": avg})
+            if validating and (epoch + 1) % args.val_interval == 0:
+                entry = validate(epoch + 1, "ema" if ema else "raw")
+                if args.val_both:
+                    validate(epoch + 1, "raw")
+                if args.keep_best:
+                    keep_best(entry)
             if (epoch + 1) % args.checkpoint_interval == 0 or stop:
                 if rank == 0:
-                    path = harness.save_checkpoint(model, args.checkpoint_dir, epoch + 1, optimizer if args.save_optimizer else None)
+                    path = harness.save_checkpoint(model, args.checkpoint_dir, epoch + 1, optimizer if args.save_optimizer else None,
+                                                   ema=optimizer if ema else None,
+                                                   ema_extra={"dropout_calls": getattr(model, "_dropout_calls", None)})
                     say(f"Saved checkpoint: {path}")
                     record["checkpoints"].append(path)
             if stop:
@@ -298,6 +415,9 @@ def run(args):
         record["guard"] = {k: stats[k] for k in ("applied", "clipped", "skipped")}
         if guarded:
             say(f"Optimizer steps applied: {stats['applied']}, clipped: {stats['clipped']}, skipped: {stats['skipped']}")
+    if ema:
+        record["ema"] = {"decay": args.ema_decay, "warmup": args.ema_warmup, "updates": optimizer.ema_updates}
+        say(f"EMA updates applied: {record['ema']['updates']}")
     if len(timed) > 1:                                                    # GPU time between stream events, first step (warm-up) left out
         torch.cuda.synchronize()
         sampler_ms = sum(m[0].elapsed_time(m[1]) for m in timed[1:]) / (len(timed) - 1)

@@ -76,6 +76,7 @@ SIGNATURES = {
     "tup_grad_sumsq_partial": [P, P, I, P, P],
     "tup_grad_guard_finish": [P, I, c_double, I, P, P],
     "tup_adam_step_guarded": [P, P, I, P, P],
+    "tup_adam_step_ema": [P, P, I, P, P],
     # patch training samples (csrc/patch_pairs.hip)
     "tup_patch_pairs": [P, I, I, I, P, P, P, I, P, P, P],
     "tup_l1_loss_partial": [P, P, P, c_longlong, I, P],

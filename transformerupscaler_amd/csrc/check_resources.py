@@ -46,6 +46,8 @@ GUARDED = [
     ("grad_accumulate.hip", ["grad_accumulate_kernel"]),
     # no counted hand-off: streaming kernels at 4 B (norm pass) and 28 B (step) per element, same reasoning
     ("step_guard.hip", ["grad_sumsq_kernel", "guard_finish_kernel", "adam_guarded_kernel"]),
+    # ... and the step with the weight average at 36 B per element (an entry of its own: the line above is quoted by a test)
+    ("step_guard.hip", ["adam_ema_kernel"]),
     # no counted hand-off: byte work at ~15 B of memory traffic per HR pixel whose tap loops index small LDS tiles; scratch would add
     # memory traffic to a kernel that exists to remove it
     ("patch_pairs.hip", ["patch_pairs_kernel"]),

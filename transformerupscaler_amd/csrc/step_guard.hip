@@ -14,6 +14,14 @@
 // a fixed LDS tree; over workgroups: ascending stripes, then the same tree), so the record is bitwise reproducible from run to
 // run, with or without ops.deterministic.
 // Bound: HBM.  The norm pass reads the gradients once (4 B per element); the step moves 4 reads + 3 writes as tup_adam_step.
+//
+// tup_adam_step_ema is the same step with an exponential moving average of the weights kept in the same launch (adam_ema_kernel):
+// after the update, e = e + ema_w * (p_new - e) from the p held in registers, so the average costs one more read and one more write
+// per element (5 reads + 4 writes of 4 B) instead of a second pass over all parameters, and it obeys the guard: a step skipped on
+// the device leaves e where it was, which the host could not arrange without a synchronisation.  p, m and v come out bit-equal to
+// the step the optimizer would have launched without the average, so the kernel carries both arithmetic forms (record field
+// `form`): tup_adam_step's (csrc/pack_plan.hip) and adam_guarded_kernel's below.  A segment with g == NULL is a parameter that has
+// an average but no gradient in this step (the other scales' upsamplers of a mixed-scale step): its average moves, nothing else.
 #include "common.h"
 
 struct NormSeg {
@@ -40,6 +48,17 @@ struct AdamWSeg {
     float decay;                            // torch.optim.AdamW's: p *= decay, decay = 1 - lr * weight_decay rounded from double (1: none)
 };
 static_assert(sizeof(AdamWSeg) == 72, "guarded segment record = 72 bytes (the host packs it as 9 int64 words)");
+
+struct AdamEmaSeg {
+    float* p; const float* g; float* m; float* v;          // g == NULL: no gradient in this step, the average alone moves
+    long long n;
+    float step_size, bc2, beta2, omb1, omb2, eps;           // bc2: form 0: 1 / sqrt(bias_correction2) (AdamSeg), form 1: its sqrt (AdamWSeg)
+    float wd_l2, decay;                                     // form 1 only, as in AdamWSeg
+    float* e;                                               // the average, updated in place
+    float ema_w;                                            // 1 - decay of this update, rounded from double on the host
+    int form;                                               // 0: tup_adam_step's arithmetic, 1: tup_adam_step_guarded's
+};
+static_assert(sizeof(AdamEmaSeg) == 88, "EMA segment record = 88 bytes (the host packs it as 11 int64 words)");
 
 namespace {
 constexpr int GUARD_CHUNK = 4096;
@@ -147,6 +166,74 @@ __global__ __launch_bounds__(256) void adam_guarded_kernel(const AdamWSeg* __res
         s.p[i] = fmaf(neg_step, m / d, p);
     }
 }
+
+// e = e + w * (p - e) in three separately rounded operations, so that sub / mul / add in torch reproduce it bit for bit
+__device__ __forceinline__ float ema_update(float e, float p, float w)
+{
+#pragma clang fp contract(off)
+    float d = p - e;
+    d = d * w;
+    return e + d;
+}
+
+// adam_step_kernel (form 0) or adam_guarded_kernel (form 1) followed by the average's update on the new p.  Form 0 spells out what
+// the compiler makes of adam_step_kernel's expressions (checked in its ISA): m and the denominator and p are fused multiply-adds, v
+// is two rounded products and their sum.
+template <bool GUARDED>
+__global__ __launch_bounds__(256) void adam_ema_kernel(const AdamEmaSeg* __restrict__ segs, const int* __restrict__ chunks,
+                                                       const GuardRec* __restrict__ guard)
+{
+    float coef = 1.f;
+    if constexpr (GUARDED) {
+        if (guard->apply == 0) return;      // uniform: the whole grid leaves p, m, v and e as they are
+        coef = guard->coef;
+    }
+    const int seg = chunks[2 * blockIdx.x], first = chunks[2 * blockIdx.x + 1];
+    const AdamEmaSeg s = segs[seg];
+    const long long end = min((long long)first + GUARD_CHUNK, s.n);
+    const float w = s.ema_w;
+    if (s.g == nullptr) {                   // uniform per workgroup: p is read, never written; m and v are not touched
+        for (long long i = first + threadIdx.x; i < end; i += 256) s.e[i] = ema_update(s.e[i], s.p[i], w);
+        return;
+    }
+    const float omb1 = s.omb1, omb2 = s.omb2, beta2 = s.beta2, neg_step = -s.step_size;
+    if (s.form == 0) {
+        for (long long i = first + threadIdx.x; i < end; i += 256) {
+#pragma clang fp contract(off)
+            const float g = s.g[i];
+            float m = s.m[i], v = s.v[i];
+            m = fmaf(g - m, omb1, m);
+            const float gg = g * g * omb2;
+            v = v * beta2 + gg;
+            const float denom = fmaf(sqrtf(v), s.bc2, s.eps);
+            s.m[i] = m; s.v[i] = v;
+            const float p = fmaf(neg_step, m / denom, s.p[i]);
+            s.p[i] = p;
+            s.e[i] = ema_update(s.e[i], p, w);
+        }
+        return;
+    }
+    const float wd = s.wd_l2, decay = s.decay;
+    const bool l2 = wd != 0.f, scale = coef != 1.f;
+    for (long long i = first + threadIdx.x; i < end; i += 256) {
+#pragma clang fp contract(off)
+        float g = s.g[i], p = s.p[i];
+        float m = s.m[i], v = s.v[i];
+        if (scale) g = g * coef;
+        if (l2) g = fmaf(wd, p, g);
+        p = p * decay;
+        m = fmaf(omb1, g - m, m);
+        v = v * beta2;
+        v = fmaf(omb2, g * g, v);
+        float d = sqrtf(v);
+        d = d / s.bc2;
+        d = d + s.eps;
+        s.m[i] = m; s.v[i] = v;
+        p = fmaf(neg_step, m / d, p);
+        s.p[i] = p;
+        s.e[i] = ema_update(s.e[i], p, w);
+    }
+}
 }  // namespace
 
 // segs: device array [nseg] of 16-byte records {const float* g; long long n}; chunks: device int [nchunks][2] = (segment index, first
@@ -180,6 +267,20 @@ extern "C" int tup_adam_step_guarded(const void* segs, const int* chunks, int nc
         adam_guarded_kernel<true><<<dim3((unsigned)nchunks), dim3(256), 0, s>>>((const AdamWSeg*)segs, chunks, (const GuardRec*)guard);
     else
         adam_guarded_kernel<false><<<dim3((unsigned)nchunks), dim3(256), 0, s>>>((const AdamWSeg*)segs, chunks, nullptr);
+    TUP_CHECK_LAUNCH();
+    return 0;
+}
+
+// segs: device array [nseg] of 88-byte records (AdamEmaSeg above); chunks as for tup_adam_step; guard: the record
+// tup_grad_guard_finish wrote on the same stream, or NULL (always apply, coef = 1).  Segments with g == NULL update e alone.
+extern "C" int tup_adam_step_ema(const void* segs, const int* chunks, int nchunks, const void* guard, void* stream)
+{
+    if (nchunks <= 0) return 0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (guard != nullptr)
+        adam_ema_kernel<true><<<dim3((unsigned)nchunks), dim3(256), 0, s>>>((const AdamEmaSeg*)segs, chunks, (const GuardRec*)guard);
+    else
+        adam_ema_kernel<false><<<dim3((unsigned)nchunks), dim3(256), 0, s>>>((const AdamEmaSeg*)segs, chunks, nullptr);
     TUP_CHECK_LAUNCH();
     return 0;
 }

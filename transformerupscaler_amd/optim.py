@@ -22,7 +22,17 @@ step's pre-clip norm (reading it takes no synchronisation of its own); ``optimiz
 
 The host computes the bias corrections from `step`, so it has to learn of a skipped step: every guarded step copies the 64-byte
 guard record to a pinned slot behind an event, the NEXT `step()` waits for that event (the GPU is then at most one step behind the
-host) and takes the skipped step's `step` increments back.  `state_dict()` and `guard_stats()` settle the same way."""
+host) and takes the skipped step's `step` increments back.  `state_dict()` and `guard_stats()` settle the same way.
+
+``ema_decay=d`` (0 <= d < 1) keeps an exponential moving average of every stepped parameter, updated inside the step's own launch
+(`tup_adam_step_ema`, csrc/step_guard.hip): ``e = e + (1 - d_n) * (p_new - e)`` as three rounded fp32 operations, with
+``d_n = ema_decay_at(n, d, ema_warmup)`` and n the count of applied updates (``optimizer.ema_updates``).  A step the guard skips on
+the device moves neither the weights nor the average nor n.  The buffers live outside ``optimizer.state`` (`state_dict()` stays
+torch's); a parameter's buffer is created at its first step as a copy of the parameter before that update, and from then on it is
+in every step's table, with a gradient or without (a segment with ``g == NULL``: the average alone moves).  The raw parameters,
+`exp_avg` and `exp_avg_sq` are bit-equal to the same run without the option.  Groups that fall through to torch's step update
+their averages with the same three torch operations.  ``ema_state_dict(model)`` / ``load_ema_state_dict(model, sd, updates)``
+export and load the average in the model's `state_dict()` layout; ``harness.ema_weights(model, optimizer)`` runs the model on it."""
 from __future__ import annotations
 
 import math
@@ -37,18 +47,112 @@ _CHUNK = 4096
 _REC = struct.Struct("<QQQQqffffff")            # AdamSeg of csrc/pack_plan.hip (64 bytes)
 _REC_GUARDED = struct.Struct("<QQQQqffffffff")  # AdamWSeg of csrc/step_guard.hip (72 bytes): ..., bc2_sqrt in place of its inverse, wd_l2, decay
 _REC_NORM = struct.Struct("<Qq")                # NormSeg (16 bytes): g, n
+_REC_EMA = struct.Struct("<QQQQqffffffffQfi")   # AdamEmaSeg (88 bytes): AdamWSeg's fields (bc2: by form), e, ema_w, form (0: _REC's arithmetic, 1: _REC_GUARDED's)
 _REC_GUARD = struct.Struct("<ddfifiQQQQ")       # GuardRec (64 bytes): sumsq, norm, coef, apply, norm_f32, clipped, steps, applied, clipped, skipped
 
 
-class _FusedAdamStep:
+def ema_decay_at(n: int, decay: float, warmup: bool = False) -> float:
+    """The decay d_n of EMA update n (0-based count of applied updates): `decay`, or with `warmup` timm's schedule
+    ``min(decay, (1 + n) / (10 + n))`` (0.1 at n = 0, reaching `decay` and staying there)."""
+    decay = float(decay)
+    return min(decay, (1 + n) / (10 + n)) if warmup else decay
+
+
+def _f32(x: float) -> float:
+    """x rounded to fp32 (round to nearest, as the record's field holds it)."""
+    return struct.unpack("<f", struct.pack("<f", x))[0]
+
+
+class _EmaBook:
+    """The host side of the weight average, shared by the fused step below and harness's torch arm: the options, the buffers (a
+    dict parameter -> tensor outside `optimizer.state`), the count of applied updates and the three-op update in torch."""
+
+    def _init_ema(self, ema_decay, ema_warmup) -> None:
+        if ema_decay is not None:
+            ema_decay = float(ema_decay)
+            if not 0.0 <= ema_decay < 1.0:                    # also a NaN
+                raise ValueError(f"ema_decay must be in [0, 1) or None, got {ema_decay}")
+        self.ema_decay = ema_decay
+        self.ema_warmup = bool(ema_warmup)
+        self._ema = {}
+        self._ema_n = 0
+        self._ema_swapped = False                             # harness.ema_weights is active: the parameters hold the averages
+
+    def _ema_settle(self) -> None:
+        settle = getattr(self, "_settle", None)
+        if settle is not None:
+            settle()
+
+    @property
+    def ema_updates(self) -> int:
+        """The settled count of applied EMA updates (a step skipped on the device is not one)."""
+        self._ema_settle()
+        return self.__dict__.get("_ema_n", 0)
+
+    def _ema_weight(self) -> float:
+        """fp32(1 - d_n) of the next update, rounded from double."""
+        return _f32(1.0 - ema_decay_at(self._ema_n, self.ema_decay, self.ema_warmup))
+
+    def _ema_buffer(self, p):
+        """p's buffer, created on first use as a copy of p as it is now (before its first update)."""
+        e = self._ema.get(p)
+        if e is None:
+            e = self._ema[p] = p.detach().clone(memory_format=torch.contiguous_format)
+        return e
+
+    @staticmethod
+    def _ema_torch_update(p, e, w: float) -> None:
+        """e = e + w * (p - e): sub, mul, add, each rounded -- the kernel's three operations."""
+        d = torch.sub(p.detach(), e)
+        d.mul_(w)
+        e.add_(d)
+
+    def _ema_check_step(self) -> None:
+        if self.__dict__.get("_ema_swapped", False):
+            raise RuntimeError("optimizer.step() inside harness.ema_weights(): the parameters hold the averaged weights")
+
+    def ema_state_dict(self, model) -> dict:
+        """The averaged weights with exactly ``model.state_dict()``'s keys and order: a parameter's average, or the parameter itself
+        where it has no buffer (never stepped: its average is its value); buffers are copied."""
+        if self.__dict__.get("ema_decay") is None:
+            raise RuntimeError("ema_state_dict(): the optimizer was built without ema_decay")
+        self._ema_settle()
+        params = dict(model.named_parameters(remove_duplicate=False))
+        out = {}
+        for k, v in model.state_dict().items():
+            p = params.get(k)
+            e = None if p is None or self._ema_swapped else self._ema.get(p)
+            out[k] = (v if e is None else e).detach().clone()
+        return out
+
+    def load_ema_state_dict(self, model, sd, updates: int = 0) -> None:
+        """Load averages in the `ema_state_dict` layout (every parameter of `model` gets a buffer) and set the update count."""
+        if self.__dict__.get("ema_decay") is None:
+            raise RuntimeError("load_ema_state_dict(): the optimizer was built without ema_decay")
+        self._ema_check_step()
+        self._ema_settle()
+        params = dict(model.named_parameters())
+        missing = [k for k in params if k not in sd]
+        if missing:
+            raise KeyError(f"load_ema_state_dict(): no entry for {missing[:3]}{' ...' if len(missing) > 3 else ''}")
+        for k, p in params.items():
+            v = sd[k]
+            if tuple(v.shape) != tuple(p.shape):
+                raise ValueError(f"load_ema_state_dict(): {k} has shape {tuple(v.shape)}, the parameter {tuple(p.shape)}")
+            self._ema[p] = v.detach().to(device=p.device, dtype=p.dtype, copy=True).contiguous()
+        self._ema_n = int(updates)
+
+
+class _FusedAdamStep(_EmaBook):
     """The step of `Adam` and `AdamW` below (a mix-in in front of the torch class)."""
 
-    def __init__(self, params, *args, max_grad_norm=None, skip_nonfinite=False, **kwargs):
+    def __init__(self, params, *args, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False, **kwargs):
         if max_grad_norm is not None:
             max_grad_norm = float(max_grad_norm)
             if not max_grad_norm >= 0.0:                      # negative or NaN
                 raise ValueError(f"max_grad_norm must be >= 0 or None, got {max_grad_norm}")
         super().__init__(params, *args, **kwargs)
+        self._init_ema(ema_decay, ema_warmup)
         self.max_grad_norm = max_grad_norm
         self.skip_nonfinite = bool(skip_nonfinite)
         if self._guarded:
@@ -79,11 +183,13 @@ class _FusedAdamStep:
         pending = self.__dict__.pop("_pending", None)
         if pending is None:
             return
-        event, slot, params = pending
+        event, slot, params, ema_counted = pending
         event.synchronize()
         rec = _REC_GUARD.unpack(bytes(slot.numpy().tobytes()))
         self.__dict__["_settled"] = rec
         if rec[3] == 0:                                       # apply == 0: GradScaler's semantics, nothing moved
+            if ema_counted:                                   # ... the average included
+                self.__dict__["_ema_n"] -= 1
             for p in params:
                 st = self.state[p]
                 st["step"] -= 1
@@ -118,9 +224,15 @@ class _FusedAdamStep:
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._ema_check_step()
         guarded = self._guarded
         if guarded:
             self._settle()
+        ema = self.__dict__.get("ema_decay") is not None
+        ema_w = self._ema_weight() if ema else 0.0
+        idle_recs: List[bytes] = []                            # EMA on: parameters with a buffer and no gradient in this step (g = NULL)
+        idle_sizes: List[int] = []
+        torch_ema: list = []                                   # ... and the parameters whose average torch updates (fall-through groups)
         decoupled_cls = isinstance(self, torch.optim.AdamW)
         recs: List[bytes] = []
         norm_recs: List[bytes] = []                            # the norm pass's (g, n) table, in the order of `recs`
@@ -133,6 +245,7 @@ class _FusedAdamStep:
         extended = guarded or any(group.get("weight_decay", 0) != 0 for group in self.param_groups)
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.grad is not None]
+            idle = [p for p in group["params"] if p.grad is None and p in self._ema] if ema else []
             ok = self._fusable(group) and all(
                 p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.dtype == torch.float32
                 and not p.grad.is_sparse and p.grad.device == p.device for p in ps)
@@ -145,7 +258,18 @@ class _FusedAdamStep:
                     self._require_guardable(group, ps)
                     raise ValueError("max_grad_norm / skip_nonfinite need contiguous fp32 parameters with dense fp32 gradients on one GPU")
                 fallback_groups.append(group)
+                if ema:
+                    torch_ema += [(p, self._ema_buffer(p)) for p in ps + idle]
                 continue
+            for p in idle:                                    # the average still moves (timm, swa_utils.AveragedModel: every update)
+                e = self._ema[p]
+                if p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and (device is None or p.device == device):
+                    device = p.device
+                    idle_recs.append(_REC_EMA.pack(p.data_ptr(), 0, 0, 0, p.numel(), 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0,
+                                                   e.data_ptr(), ema_w, 0))
+                    idle_sizes.append(p.numel())
+                else:
+                    torch_ema.append((p, e))
             beta1, beta2 = group["betas"]
             wd = float(group.get("weight_decay", 0))
             decoupled = decoupled_cls or bool(group.get("decoupled_weight_decay", False))
@@ -161,19 +285,29 @@ class _FusedAdamStep:
                 t = float(st["step"])
                 bc1, bc2 = 1.0 - beta1 ** t, 1.0 - beta2 ** t
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                if extended:
+                if ema:                                       # the record of either form below, then e, ema_w, form
+                    e = self._ema_buffer(p)
+                    recs.append(_REC_EMA.pack(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                                              p.numel(), group["lr"] / bc1, math.sqrt(bc2) if extended else 1.0 / math.sqrt(bc2), beta2,
+                                              1.0 - beta1, 1.0 - beta2, group["eps"], wd_l2 if extended else 0.0,
+                                              decay if extended else 1.0, e.data_ptr(), ema_w, 1 if extended else 0))
+                elif extended:
                     recs.append(_REC_GUARDED.pack(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                                                   p.numel(), group["lr"] / bc1, math.sqrt(bc2), beta2, 1.0 - beta1, 1.0 - beta2,
                                                   group["eps"], wd_l2, decay))
-                    if guarded:
-                        norm_recs.append(_REC_NORM.pack(g.data_ptr(), p.numel()))
                 else:
                     recs.append(_REC.pack(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(),
                                           group["lr"] / bc1, 1.0 / math.sqrt(bc2), beta2, 1.0 - beta1, 1.0 - beta2, group["eps"]))
+                if guarded:
+                    norm_recs.append(_REC_NORM.pack(g.data_ptr(), p.numel()))
                 sizes.append(p.numel())
                 updated.append(p)
                 if g is not p.grad:
                     keep.append(g)
+        n_norm = sum(-(-n // _CHUNK) for n in sizes)           # workgroups of the gradient segments: the norm pass runs on these
+        recs += idle_recs                                      # gradient segments first, so that the norm table is the chunk table's head
+        sizes += idle_sizes
+        ema_counted = ema and bool(recs or torch_ema)
         if recs:
             key = tuple(sizes)
             cache = self.__dict__.setdefault("_chunk_cache", {})
@@ -206,8 +340,10 @@ class _FusedAdamStep:
                 if events[slot] is None:
                     events[slot] = torch.cuda.Event()
                 events[slot].record()
-                if guarded:
-                    self._guarded_launches(segs, norm_off, chunks, device, updated, _stream())
+                if guarded and (n_norm or not ema):
+                    self._guarded_launches(segs, norm_off, chunks, device, updated, _stream(), n_norm, ema, ema_counted)
+                elif ema:                                     # (under the guard: averages alone, no gradient to decide on)
+                    _lib.call("tup_adam_step_ema", segs.data_ptr(), chunks.data_ptr(), chunks.shape[0], None, _stream())
                 elif extended:
                     _lib.call("tup_adam_step_guarded", segs.data_ptr(), chunks.data_ptr(), chunks.shape[0], None, _stream())
                 else:
@@ -225,10 +361,15 @@ class _FusedAdamStep:
                 super().step()
             finally:
                 self.param_groups = saved
+        for p, e in torch_ema:
+            self._ema_torch_update(p, e, ema_w)
+        if ema_counted:
+            self._ema_n += 1
         return loss
 
-    def _guarded_launches(self, segs, norm_off, chunks, device, updated, stream) -> None:
-        """Norm, finish, step; then the record's asynchronous copy to a pinned slot for the next step()'s `_settle`."""
+    def _guarded_launches(self, segs, norm_off, chunks, device, updated, stream, n_norm, ema, ema_counted) -> None:
+        """Norm, finish, step; then the record's asynchronous copy to a pinned slot for the next step()'s `_settle`.  The norm pass
+        takes the chunk table's first `n_norm` rows (the segments with a gradient; without EMA that is all of them)."""
         d = self.__dict__
         guard = d.get("_guard")
         if guard is None or guard.device != device:
@@ -241,14 +382,14 @@ class _FusedAdamStep:
         if partials is None or partials.numel() < nchunks or partials.device != device:
             partials = d["_partials"] = torch.empty(max(nchunks, 1024), dtype=torch.float64, device=device)
         max_norm = -1.0 if self.max_grad_norm is None else self.max_grad_norm
-        _lib.call("tup_grad_sumsq_partial", segs.data_ptr() + norm_off, chunks.data_ptr(), nchunks, partials.data_ptr(), stream)
-        _lib.call("tup_grad_guard_finish", partials.data_ptr(), nchunks, max_norm, int(self.skip_nonfinite), guard.data_ptr(), stream)
-        _lib.call("tup_adam_step_guarded", segs.data_ptr(), chunks.data_ptr(), nchunks, guard.data_ptr(), stream)
+        _lib.call("tup_grad_sumsq_partial", segs.data_ptr() + norm_off, chunks.data_ptr(), n_norm, partials.data_ptr(), stream)
+        _lib.call("tup_grad_guard_finish", partials.data_ptr(), n_norm, max_norm, int(self.skip_nonfinite), guard.data_ptr(), stream)
+        _lib.call("tup_adam_step_ema" if ema else "tup_adam_step_guarded", segs.data_ptr(), chunks.data_ptr(), nchunks, guard.data_ptr(), stream)
         turn = d["_guard_turn"] = d["_guard_turn"] ^ 1
         # the slot's previous content (two steps ago) was consumed by the last step()'s _settle
         d["_guard_slots"][turn].copy_(guard, non_blocking=True)
         d["_guard_events"][turn].record()
-        d["_pending"] = (d["_guard_events"][turn], d["_guard_slots"][turn], list(updated))
+        d["_pending"] = (d["_guard_events"][turn], d["_guard_slots"][turn], list(updated), ema_counted)
 
 
 class Adam(_FusedAdamStep, torch.optim.Adam):
