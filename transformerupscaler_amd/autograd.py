@@ -10,37 +10,28 @@ parity fixtures use.  The masks are not torch's Philox stream --
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, List, Optional
-
-import os
+from typing import Dict
 
 import torch
 
 from . import ops, packing
+from .blocks_train import (BlockSpec, blocks_backward, blocks_forward, conv_tail_backward, decoder_backward, node_backward,
+                           site_seed, token_rowmask)
 from .weights import BLOCKS, active_param_names, upsampler_layout
-
-BF16, F32 = torch.bfloat16, torch.float32
 
 # Data-parallel training (dp.py): a reducer attached to the module is told, in reverse execution order,
 # as soon as a group of parameter gradients is final, so its all-reduce overlaps the rest of the backward.
 
-_ROWMASK_CACHE = {}
 
-
-def _valid_token_rowmask(B, H, W, device):
-    key = (B, H, W, str(device))
-    if key not in _ROWMASK_CACHE:
-        ht, wt, nwy, nwx = ops.window_geometry(H, W)
-        ty = (torch.arange(nwy).view(-1, 1, 1, 1) * 8 + torch.arange(8).view(1, 1, -1, 1))
-        tx = (torch.arange(nwx).view(1, -1, 1, 1) * 8 + torch.arange(8).view(1, 1, 1, -1))
-        m = ((ty < ht) & (tx < wt)).expand(nwy, nwx, 8, 8).reshape(1, -1).expand(B, -1).reshape(-1)
-        _ROWMASK_CACHE[key] = m.to(torch.uint8).contiguous().to(device)
-    return _ROWMASK_CACHE[key]
-
-
-def site_seed(seed: int, block: int, site: int) -> int:
-    """Per-dropout-site seed (site 0 = attn_drop, 1 = proj_drop, 2 = MLP dropout of block `block`)."""
-    return (seed * 0x9E3779B9 + (3 * block + site + 1) * 0x85EBCA6B) & 0xFFFFFFFF
+def _block_spec(frags_t, frags_n=None):
+    """FastTransformer's block for blocks_train: width 192 / 12 heads, relative-position bias, all three dropout sites."""
+    return BlockSpec(
+        norm=ops.layernorm, norm_bwd=ops.layernorm_bwd,
+        attn_fwd=lambda i, qkv, drop_p, seed: ops.window_attn(qkv, frags_t[i], drop_p, seed, save_lse=True),
+        attn_bwd=lambda i, s, g_att, drop_p, seed: ops.window_attn_bwd(s["qkv"], g_att, s["att"], s["lse"], frags_n[i], drop_p, seed),
+        hidden=768, keys=("qkv", "proj"),
+        names=(".attn.qkv.weight", ".attn.qkv.bias", ".attn.proj.weight", ".attn.proj.bias"),
+        prefix="window_blocks", proj_drop=True, table_grad=True)
 
 
 pe_merge = True          # A/B attribute (tests flip it): the gradient merge at `feat` inside patch_embed's input gradient
@@ -72,21 +63,7 @@ def forward_train(pk, frags_t, x, scale, res_out, require_ratio, drop_p=0.0, see
     else:
         ui = sv["ui"] = ops.conv_c64_thin(ups[-1], pk["up1_conv.w"], None, 3, relu=True)
     xw = ops.patch_embed(feat, pk["pe.w"], pk["pe.b"])
-    blocks = []
-    for i in range(BLOCKS):
-        s = {"x_in": xw}
-        s["y1"], s["mean1"], s["rstd1"] = ops.layernorm(xw, pk[f"b{i}.norm1.w"], pk[f"b{i}.norm1.b"], save_stats=True)
-        s["qkv"] = ops.gemm_tokens(s["y1"], pk[f"b{i}.qkv.w"], pk[f"b{i}.qkv.b"], "bf16")
-        s["att"], s["lse"] = ops.window_attn(s["qkv"], frags_t[i], drop_p, site_seed(seed, i, 0), save_lse=True)
-        xm = s["x_mid"] = ops.gemm_tokens(s["att"], pk[f"b{i}.proj.w"], pk[f"b{i}.proj.b"], "res", res=xw,
-                                          drop_p=drop_p, drop_seed=site_seed(seed, i, 1))
-        s["y2"], s["mean2"], s["rstd2"] = ops.layernorm(xm, pk[f"b{i}.norm2.w"], pk[f"b{i}.norm2.b"], save_stats=True)
-        s["hpre"] = torch.empty((xm.shape[0], 768), dtype=BF16, device=x.device)
-        s["hid"] = ops.gemm_tokens(s["y2"], pk[f"b{i}.fc1.w"], pk[f"b{i}.fc1.b"], "gelu", aux=s["hpre"])
-        xw = ops.gemm_tokens(s["hid"], pk[f"b{i}.fc2.w"], pk[f"b{i}.fc2.b"], "res", res=xm,
-                             drop_p=drop_p, drop_seed=site_seed(seed, i, 2))
-        blocks.append(s)
-    sv["blocks"] = blocks
+    xw, sv["blocks"] = blocks_forward(_block_spec(frags_t), pk, BLOCKS, xw, drop_p, seed)
     sv["xw_out"] = xw
     comb = sv["comb"] = ops.patch_unembed(xw, pk["pu.w"], pk["pu.b"], feat)
     dec = sv["dec"] = ops.conv_c64(comb, pk["dec1.w"], pk["dec1.b"], 1, relu=True)
@@ -139,17 +116,8 @@ def backward_train(pk, frags_t, frags_n, sv, scale, gout, reducer=None, want_inp
         g_t = ops.conv_planar_dgrad(g_t, pk[f"fu.{si}.raw"], r)
         ready(k + ".weight", k + ".bias")
     g_res = g_t                                                   # d residual, planar [B][3][H][W]
-    # ---- decoder_conv2 (64->3) and decoder_conv1's ReLU ----
-    dwp, db = ops.conv_thin_wgrad(sv["dec"], g_res, True)
-    g["decoder_conv2.weight"], g["decoder_conv2.bias"] = dwp.permute(0, 2, 1).reshape(3, 64, 3, 3), db
-    g_dec = ops.conv1(g_res, pk["dec2.wd"], None, relu=False, out_mask=sv["dec"])
-    ready("decoder_conv2.weight", "decoder_conv2.bias")
-    # ---- decoder_conv1 (64->64) ----
-    dwp, db = ops.conv_c64_wgrad(sv["comb"], g_dec, 1)
-    g["decoder_conv1.weight"], g["decoder_conv1.bias"] = packing.unpack_conv_c64_wgrad(dwp, db, 1)
-    g_comb = ops.conv_c64(g_dec, pk["dec1.wd"], None, 1)
-    del g_dec
-    ready("decoder_conv1.weight", "decoder_conv1.bias")
+    # ---- decoder_conv2 (64->3), decoder_conv1's ReLU, decoder_conv1 (64->64) ----
+    g_comb = decoder_backward(pk, sv, g, ready, g_res)
     # ---- patch_unembed (+ skip) ----
     # patch_unembed's bias gradient = the column sums of g_comb.  Without a gradient reducer they ride along in the kernel that reads
     # g_comb last (the merged patch_embed input gradient at the end of this function); with one, the bias has to be ready NOW so that
@@ -162,49 +130,9 @@ def backward_train(pk, frags_t, frags_n, sv, scale, gout, reducer=None, want_inp
     g_x = ops.patch_unembed_bwd(g_comb, pk["pu.wd"])
     ready("patch_unembed.weight", "patch_unembed.bias")
     # ---- transformer blocks (reverse) ----
-    drop_p, seed = sv["drop_p"], sv["seed"]
-    g_xd = None
-    for i in reversed(range(BLOCKS)):
-        s, p = sv["blocks"][i], f"window_blocks.{i}"
-        # gradient entering mlp.2's output: through the MLP dropout mask (the residual path keeps g_x itself); from the second
-        # block of the loop on the previous LayerNorm1 backward has written it already (fused dropout_bwd)
-        if g_xd is not None:
-            g_o, g_xd = g_xd, None
-        else:
-            g_o = ops.dropout_bwd(g_x, drop_p, site_seed(seed, i, 2)) if drop_p > 0 else g_x
-        g[p + ".mlp.2.weight"], g[p + ".mlp.2.bias"] = ops.gemm_wgrad_bias(g_o, s["hid"])
-        g_h = ops.gemm_tokens(g_o, pk[f"b{i}.fc2.wd"], None, "gelu_bwd", aux=s["hpre"])
-        del g_o
-        g[p + ".mlp.0.weight"], g[p + ".mlp.0.bias"] = ops.gemm_wgrad_bias(g_h, s["y2"])
-        g_y2 = ops.gemm_tokens(g_h, pk[f"b{i}.fc1.wd"], None, "bf16")
-        del g_h
-        if drop_p > 0:          # + proj_drop's backward of the result (bf16), in the same pass
-            g_xm, g[p + ".norm2.weight"], g[p + ".norm2.bias"], g_o = ops.layernorm_bwd(
-                g_y2, s["x_mid"], s["mean2"], s["rstd2"], pk[f"b{i}.norm2.w"], gres=g_x, drop=(drop_p, site_seed(seed, i, 1)))
-        else:
-            g_xm, g[p + ".norm2.weight"], g[p + ".norm2.bias"] = ops.layernorm_bwd(
-                g_y2, s["x_mid"], s["mean2"], s["rstd2"], pk[f"b{i}.norm2.w"], gres=g_x)
-            g_o = g_xm      # proj_drop
-        g[p + ".attn.proj.weight"], g[p + ".attn.proj.bias"] = ops.gemm_wgrad_bias(g_o, s["att"])
-        g_att = ops.gemm_tokens(g_o, pk[f"b{i}.proj.wd"], None, "bf16")
-        del g_o
-        g_qkv, g[p + ".attn.relative_position_bias_table"] = ops.window_attn_bwd(
-            s["qkv"], g_att, s["att"], s["lse"], frags_n[i], drop_p, site_seed(seed, i, 0))
-        g[p + ".attn.qkv.weight"], g[p + ".attn.qkv.bias"] = ops.gemm_wgrad_bias(g_qkv, s["y1"])
-        g_y1 = ops.gemm_tokens(g_qkv, pk[f"b{i}.qkv.wd"], None, "bf16")
-        del g_qkv, g_att
-        if drop_p > 0 and i > 0:          # + the MLP dropout's backward for the block below
-            g_x, g[p + ".norm1.weight"], g[p + ".norm1.bias"], g_xd = ops.layernorm_bwd(
-                g_y1, s["x_in"], s["mean1"], s["rstd1"], pk[f"b{i}.norm1.w"], gres=g_xm, drop=(drop_p, site_seed(seed, i - 1, 2)))
-        else:
-            g_x, g[p + ".norm1.weight"], g[p + ".norm1.bias"] = ops.layernorm_bwd(
-                g_y1, s["x_in"], s["mean1"], s["rstd1"], pk[f"b{i}.norm1.w"], gres=g_xm)
-        ready(*[p + sfx for sfx in (".mlp.2.bias", ".mlp.2.weight", ".mlp.0.bias", ".mlp.0.weight", ".norm2.weight",
-                                    ".norm2.bias", ".attn.proj.bias", ".attn.proj.weight",
-                                    ".attn.relative_position_bias_table", ".attn.qkv.bias", ".attn.qkv.weight",
-                                    ".norm1.weight", ".norm1.bias")])
+    g_x = blocks_backward(_block_spec(frags_t, frags_n), pk, sv["blocks"], g, ready, g_x, sv["drop_p"], sv["seed"])
     # ---- patch_embed ----
-    g["patch_embed.bias"] = ops.colsum(g_x, rowmask=_valid_token_rowmask(B, H, W, x.device))
+    g["patch_embed.bias"] = ops.colsum(g_x, rowmask=token_rowmask(B, (H + 7) // 8, (W + 7) // 8, x.device))
     g["patch_embed.weight"] = ops.patch_wgrad(g_x, feat, reflect=True).view(192, 8, 8, 64).permute(0, 3, 1, 2)
     # the input gradient of patch_embed: when the map needs no reflect padding (H, W multiples of 8) it is computed LAST, with the
     # merge of the three gradient paths into `feat` and conv2's ReLU gate in its epilogue (no padded map, no feat_grad_combine pass)
@@ -246,11 +174,7 @@ def backward_train(pk, frags_t, frags_n, sv, scale, gout, reducer=None, want_inp
     else:
         g_feat = ops.feat_grad_combine(g_comb, g_up, g_pe, feat)
     del g_comb, g_up, g_pe
-    dwp, db = ops.conv_c64_wgrad(sv["feat1"], g_feat, 1)
-    g["conv2.weight"], g["conv2.bias"] = packing.unpack_conv_c64_wgrad(dwp, db, 1)
-    g_f1 = ops.conv_c64(g_feat, pk["conv2.wd"], None, 1, mask=sv["feat1"])
-    g["conv1.weight"], g["conv1.bias"] = ops.conv1_wgrad(x, g_f1)
-    ready("conv2.weight", "conv2.bias", "conv1.weight", "conv1.bias")
+    g_f1 = conv_tail_backward(pk, sv, g, ready, g_feat)
     if want_input_grad:
         g["__input__"] = ops.conv_c64_thin(g_f1, pk["conv1.wd"], None, 3, relu=False)
     return g
@@ -271,38 +195,12 @@ class _FastTransformerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        # the fused-L1 hand-off is validated BEFORE the reducer opens its episode: a refusal here must not leave it open
-        fused = getattr(ctx, "_fused_l1", None)
-        l1_scale = None
-        if fused is not None:
-            target, l1_scale, stand_in = fused
-            ctx._fused_l1 = None
-            if gout.data_ptr() != stand_in.data_ptr() or any(st != 0 for st in gout.stride()):
-                raise RuntimeError("l1_loss(..., fuse_into_model_backward=True): the model output has a consumer besides the loss "
-                                   "(its gradient is not the loss's stand-in); call l1_loss without the fusion")
-            gout = target
-        reducer = getattr(ctx.module, "_grad_reducer", None)
-        if reducer is not None:
-            reducer.begin(ctx.names)          # raises if this step's parameters are not in the reducer's layout
-        ops.zero_pool_begin(gout.device)
-        try:
-            grads = backward_train(ctx.pk, ctx.frags[0], ctx.frags[1], ctx.sv, ctx.scale, gout, reducer,
-                                   want_input_grad=bool(ctx.needs_input_grad[1]), l1_scale=l1_scale)
-        except BaseException:
-            if reducer is not None:
-                reducer._abort()
-            raise
-        finally:
-            ops.zero_pool_end()
-        gx = grads.pop("__input__", None)       # the reference supplies d/dx too (an input that requires grad)
-        if reducer is not None:
-            grads = reducer.finish()          # averaged over ranks (views of the flat bucket buffer)
-        ctx.sv = None
-        outs = []
-        for n in ctx.names:
-            gr = grads.get(n)
-            outs.append(None if gr is None else gr.contiguous())      # reducer: views of this episode's own flat buffer (dp.py)
-        return (None, None if gx is None else gx.to(ctx.x_dtype), None, None, None, None) + tuple(outs)
+        def run(gout, reducer, l1_scale):
+            return backward_train(ctx.pk, ctx.frags[0], ctx.frags[1], ctx.sv, ctx.scale, gout, reducer,
+                                  want_input_grad=bool(ctx.needs_input_grad[1]), l1_scale=l1_scale)
+        own, outs = node_backward(ctx, gout, run, _FastTransformerFn.accepts_fused_l1)
+        gx = own.pop("__input__", None)       # the reference supplies d/dx too (an input that requires grad)
+        return (None, None if gx is None else gx.to(ctx.x_dtype), None, None, None, None) + outs
 
 
 def fast_transformer_function(module, x, scale, res_out, require_ratio):

@@ -39,7 +39,8 @@ from .weights import VALID_SCALES, active_param_names, param_shapes
 
 
 def _ft_backward_key(name: str):
-    """Sort key = the order in which autograd.backward_train finalises FastTransformer gradients."""
+    """Sort key = the order in which autograd.backward_train (with blocks_train's decoder head, block loop and conv tail inside it)
+    finalises FastTransformer gradients."""
     if name.startswith("final_upscale_conv."):
         return (0, 0)
     if name.startswith("final_upscale.upsamplers."):

@@ -6,6 +6,7 @@ maps, fp32 planar for the 3-channel images, fp32 residual stream for the tokens.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import math
@@ -24,16 +25,16 @@ stage_timer = None
 fuse_attention = 3      # A/B attribute (tests set 0 .. 3; no environment switch)
 
 
-class _NullCtx:
-    def __enter__(self):
-        return None
+_NO_TIMER = contextlib.nullcontext()
 
-    def __exit__(self, *a):
-        return False
+
+def stage(timer, name: str):
+    """Context manager around one timed stage: timer(name), or nothing when no timer is installed (autograd_rt has its own hook)."""
+    return timer(name) if timer is not None else _NO_TIMER
 
 
 def _stage(name: str):
-    return stage_timer(name) if stage_timer is not None else _NullCtx()
+    return stage(stage_timer, name)
 
 
 def resolve_scale(h: int, w: int, res_out, upscale_factor: Optional[int]):

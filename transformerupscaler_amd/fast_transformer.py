@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import engine, ops, packing
+from .blocks_train import next_dropout
 from .weights import VALID_SCALES, upsampler_layout
 
 
@@ -140,15 +141,7 @@ class TransformerModel(nn.Module):
         self._pack_cache: Dict[int, tuple] = {}
         self._dropout_calls = 0
 
-    def _next_dropout(self):
-        """(p, seed) for the next training forward: p = 0 in eval mode; the seed advances every call and is
-        offset by torch's seed and the data-parallel rank so replicas draw different masks."""
-        if not self.training or self.dropout_p <= 0.0:
-            return 0.0, 0
-        import os
-        self._dropout_calls += 1
-        base = (torch.initial_seed() + 7919 * int(os.environ.get("RANK", "0"))) & 0x7FFFFFFF
-        return self.dropout_p, (base * 2654435761 + self._dropout_calls) & 0xFFFFFFFF
+    _next_dropout = next_dropout          # (p, seed) of the next training forward
 
     # ---- packed-weight cache, invalidated by in-place parameter updates (optimizer steps) ----
     def _versions(self):

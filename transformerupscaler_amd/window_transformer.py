@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, packing
+from .blocks_train import blocks_infer, next_dropout
 from .fast_transformer import WindowTransformerBlock, _ConvParams
 
 use_pack_plan = True          # A/B attribute: training re-pack as two gather launches (pack_plan.py)
@@ -54,14 +55,7 @@ class TransformerModel(nn.Module):
         self._pack_cache = {}
         self._dropout_calls = 0
 
-    def _next_dropout(self):
-        """(p, seed) of the next training forward (see fast_transformer.TransformerModel._next_dropout)."""
-        if not self.training or self.dropout_p <= 0.0:
-            return 0.0, 0
-        import os
-        self._dropout_calls += 1
-        base = (torch.initial_seed() + 7919 * int(os.environ.get("RANK", "0"))) & 0x7FFFFFFF
-        return self.dropout_p, (base * 2654435761 + self._dropout_calls) & 0xFFFFFFFF
+    _next_dropout = next_dropout          # (p, seed) of the next training forward
 
     def invalidate_packed(self) -> None:
         """Drop the packed-weight cache (after ``p.data`` writes, which do not bump the version counter the cache is keyed on)."""
@@ -112,14 +106,7 @@ class TransformerModel(nn.Module):
         del feat
         xw = ops.wt_patch_embed(feat_down, pk["pe.w"], pk["pe.b"])                          # model.py:247-268
         heads = self.num_heads
-        for i in range(pk["nblocks"]):
-            y = ops.layernorm128(xw, pk[f"b{i}.norm1.w"], pk[f"b{i}.norm1.b"])
-            qkv = ops.gemm_tokens(y, pk[f"b{i}.qkv.w"], pk[f"b{i}.qkv.b"], "bf16")
-            att = ops.window_attn_h(qkv, frags[i], heads)
-            ops.gemm_tokens(att, pk[f"b{i}.proj.w"], pk[f"b{i}.proj.b"], "res", res=xw, out=xw)
-            y = ops.layernorm128(xw, pk[f"b{i}.norm2.w"], pk[f"b{i}.norm2.b"])
-            hid = ops.gemm_tokens(y, pk[f"b{i}.fc1.w"], pk[f"b{i}.fc1.b"], "gelu")
-            ops.gemm_tokens(hid, pk[f"b{i}.fc2.w"], pk[f"b{i}.fc2.b"], "res", res=xw, out=xw)
+        blocks_infer(pk, xw, ("qkv", "proj"), lambda i, qkv: ops.window_attn_h(qkv, frags[i], heads))
         hs, ws = (hd // 8) * 8, (wd // 8) * 8                                               # crop for the skip, model.py:284-288
         skip = feat_down if (hs, ws) == (hd, wd) else feat_down[:, :hs, :ws, :].contiguous()
         comb = ops.wt_patch_unembed(xw, pk["pu.w"], pk["pu.b"], skip)
