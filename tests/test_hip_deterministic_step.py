@@ -162,7 +162,7 @@ def test_layernorm_bwd_det(M, C, drop):
     gamma = torch.rand((C,), generator=g, device=DEV) + 0.5
     mean = x.mean(1).contiguous()
     rstd = (x.var(1, unbiased=False) + 1e-5).rsqrt().contiguous()
-    wrapper = ops.layernorm_bwd if C == 192 else ops.layernorm128_bwd
+    wrapper = ops.layernorm_bwd
     entry = "tup_layernorm_bwd_det" if C == 192 else "tup_layernorm128_bwd_det"
     dr = (0.1, 12345) if drop else None
     ref = wrapper(gy, x, mean, rstd, gamma, gres=gres, drop=dr)

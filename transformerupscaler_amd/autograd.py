@@ -15,23 +15,12 @@ from typing import Dict
 import torch
 
 from . import ops, packing
-from .blocks_train import (BlockSpec, blocks_backward, blocks_forward, conv_tail_backward, decoder_backward, node_backward,
-                           site_seed, token_rowmask)
+from .blocks_train import (blocks_backward, blocks_forward, conv_tail_backward, decoder_backward, node_backward,
+                           site_seed, token_rowmask, window_block_spec)
 from .weights import BLOCKS, active_param_names, upsampler_layout
 
 # Data-parallel training (dp.py): a reducer attached to the module is told, in reverse execution order,
 # as soon as a group of parameter gradients is final, so its all-reduce overlaps the rest of the backward.
-
-
-def _block_spec(frags_t, frags_n=None):
-    """FastTransformer's block for blocks_train: width 192 / 12 heads, relative-position bias, all three dropout sites."""
-    return BlockSpec(
-        norm=ops.layernorm, norm_bwd=ops.layernorm_bwd,
-        attn_fwd=lambda i, qkv, drop_p, seed: ops.window_attn(qkv, frags_t[i], drop_p, seed, save_lse=True),
-        attn_bwd=lambda i, s, g_att, drop_p, seed: ops.window_attn_bwd(s["qkv"], g_att, s["att"], s["lse"], frags_n[i], drop_p, seed),
-        hidden=768, keys=("qkv", "proj"),
-        names=(".attn.qkv.weight", ".attn.qkv.bias", ".attn.proj.weight", ".attn.proj.bias"),
-        prefix="window_blocks", proj_drop=True, table_grad=True)
 
 
 pe_merge = True          # A/B attribute (tests flip it): the gradient merge at `feat` inside patch_embed's input gradient
@@ -63,7 +52,7 @@ def forward_train(pk, frags_t, x, scale, res_out, require_ratio, drop_p=0.0, see
     else:
         ui = sv["ui"] = ops.conv_c64_thin(ups[-1], pk["up1_conv.w"], None, 3, relu=True)
     xw = ops.patch_embed(feat, pk["pe.w"], pk["pe.b"])
-    xw, sv["blocks"] = blocks_forward(_block_spec(frags_t), pk, BLOCKS, xw, drop_p, seed)
+    xw, sv["blocks"] = blocks_forward(window_block_spec(768, frags_t), pk, BLOCKS, xw, drop_p, seed)
     sv["xw_out"] = xw
     comb = sv["comb"] = ops.patch_unembed(xw, pk["pu.w"], pk["pu.b"], feat)
     dec = sv["dec"] = ops.conv_c64(comb, pk["dec1.w"], pk["dec1.b"], 1, relu=True)
@@ -130,7 +119,7 @@ def backward_train(pk, frags_t, frags_n, sv, scale, gout, reducer=None, want_inp
     g_x = ops.patch_unembed_bwd(g_comb, pk["pu.wd"])
     ready("patch_unembed.weight", "patch_unembed.bias")
     # ---- transformer blocks (reverse) ----
-    g_x = blocks_backward(_block_spec(frags_t, frags_n), pk, sv["blocks"], g, ready, g_x, sv["drop_p"], sv["seed"])
+    g_x = blocks_backward(window_block_spec(768, frags_t, frags_n), pk, sv["blocks"], g, ready, g_x, sv["drop_p"], sv["seed"])
     # ---- patch_embed ----
     g["patch_embed.bias"] = ops.colsum(g_x, rowmask=token_rowmask(B, (H + 7) // 8, (W + 7) // 8, x.device))
     g["patch_embed.weight"] = ops.patch_wgrad(g_x, feat, reflect=True).view(192, 8, 8, 64).permute(0, 3, 1, 2)

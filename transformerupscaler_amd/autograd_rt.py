@@ -33,7 +33,7 @@ def _block_spec(B, N):
         with stage(stage_timer, "rt_attn_bwd"):
             return ops.rt_attention_bwd(s["qkv"], s["att"], g_att, s["lse"], B, N, drop_p=drop_p, drop_seed=seed)
     return BlockSpec(
-        norm=ops.layernorm128, norm_bwd=ops.layernorm128_bwd, attn_fwd=attn_fwd, attn_bwd=attn_bwd,
+        attn_fwd=attn_fwd, attn_bwd=attn_bwd,
         hidden=512, keys=("in", "out"),
         names=(".attn.in_proj_weight", ".attn.in_proj_bias", ".attn.out_proj.weight", ".attn.out_proj.bias"),
         prefix="transformer_blocks", proj_drop=False, table_grad=False)

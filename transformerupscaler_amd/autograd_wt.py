@@ -11,32 +11,20 @@ from typing import Dict
 import torch
 
 from . import ops
-from .blocks_train import (BlockSpec, blocks_backward, blocks_forward, conv_tail_backward, decoder_backward, downsample_backward,
-                           node_backward, stem_forward, token_rowmask)
+from .blocks_train import (blocks_backward, blocks_forward, conv_tail_backward, decoder_backward, downsample_backward, node_backward,
+                           stem_forward, token_rowmask, window_block_spec)
 from .window_transformer import pad_to_even
 
 
-def _block_spec(heads, frags_t, frags_n=None):
-    """WindowTransformer's block for blocks_train: FastTransformer's window block at width 128 with `heads` heads."""
-    return BlockSpec(
-        norm=ops.layernorm128, norm_bwd=ops.layernorm128_bwd,
-        attn_fwd=lambda i, qkv, drop_p, seed: ops.window_attn_h(qkv, frags_t[i], heads, drop_p, seed, save_lse=True),
-        attn_bwd=lambda i, s, g_att, drop_p, seed: ops.window_attn_bwd_h(s["qkv"], g_att, s["att"], s["lse"], frags_n[i], heads,
-                                                                         drop_p, seed),
-        hidden=512, keys=("qkv", "proj"),
-        names=(".attn.qkv.weight", ".attn.qkv.bias", ".attn.proj.weight", ".attn.proj.bias"),
-        prefix="window_blocks", proj_drop=True, table_grad=True)
-
-
-def forward_train(pk, frags_t, heads, x, res_out, drop_p: float, seed: int):
+def forward_train(pk, frags_t, x, res_out, drop_p: float, seed: int):
     B, _, H, W = x.shape
     x = x.contiguous().float()
-    sv = {"x": x, "drop_p": drop_p, "seed": seed, "heads": heads}
+    sv = {"x": x, "drop_p": drop_p, "seed": seed}
     # odd sizes: + one zero row / column before the stride-2 conv; the skip is cropped to whole patches
     sv["feat1"], sv["feat"], sv["feat_down"], skip = stem_forward(pk, x, pad=pad_to_even, crop=True)
     sv["skip"] = skip
     xw = ops.wt_patch_embed(sv["feat_down"], pk["pe.w"], pk["pe.b"])
-    xw, sv["blocks"] = blocks_forward(_block_spec(heads, frags_t), pk, pk["nblocks"], xw, drop_p, seed)
+    xw, sv["blocks"] = blocks_forward(window_block_spec(512, frags_t), pk, pk["nblocks"], xw, drop_p, seed)
     sv["xw_out"] = xw
     comb = ops.wt_patch_unembed(xw, pk["pu.w"], pk["pu.b"], skip)
     dec = ops.conv_c64(comb, pk["dec1.w"], pk["dec1.b"], 1, relu=True)
@@ -53,7 +41,7 @@ def backward_train(pk, frags_t, frags_n, sv, gout, reducer=None) -> Dict[str, to
         if reducer is not None:
             reducer.on_ready(list(names), g)
 
-    x, heads = sv["x"], sv["heads"]
+    x = sv["x"]
     B, _, H, W = x.shape
     hd, wd = (H + 1) // 2, (W + 1) // 2
     hs, ws = sv["skip"].shape[1], sv["skip"].shape[2]
@@ -66,7 +54,7 @@ def backward_train(pk, frags_t, frags_n, sv, gout, reducer=None) -> Dict[str, to
     g_x = ops.wt_patch_unembed_bwd(g_comb, pk["pu.wd"])
     ready("patch_unembed.weight", "patch_unembed.bias")
     # ---- window blocks (reverse) ----
-    g_x = blocks_backward(_block_spec(heads, frags_t, frags_n), pk, sv["blocks"], g, ready, g_x, sv["drop_p"], sv["seed"])
+    g_x = blocks_backward(window_block_spec(512, frags_t, frags_n), pk, sv["blocks"], g, ready, g_x, sv["drop_p"], sv["seed"])
     # ---- patch_embed (real tokens only: the zero pad carries no bias, model.py:256-263) ----
     g["patch_embed.bias"] = ops.colsum(g_x, rowmask=token_rowmask(B, hd // 8, wd // 8, x.device))
     g["patch_embed.weight"] = ops.wt_patch_wgrad(g_x, sv["feat_down"]).view(128, 8, 8, 64).permute(0, 3, 1, 2)
@@ -89,7 +77,7 @@ class _WindowTransformerFn(torch.autograd.Function):
     def forward(ctx, module, x, res_out, names, *params):
         pk, frags_t, frags_n = module.packed(backward=True)
         drop_p, seed = module._next_dropout()
-        out, sv = forward_train(pk, frags_t, module.num_heads, x, res_out, drop_p, seed)
+        out, sv = forward_train(pk, frags_t, x, res_out, drop_p, seed)
         ctx.module, ctx.names, ctx.sv, ctx.pk, ctx.frags = module, names, sv, pk, (frags_t, frags_n)
         return out
 

@@ -18,9 +18,7 @@ BF16 = torch.bfloat16
 
 
 class BlockSpec(NamedTuple):
-    norm: Callable              # LayerNorm forward op (ops.layernorm | ops.layernorm128)
-    norm_bwd: Callable          # ... and its backward
-    attn_fwd: Callable          # (i, qkv, drop_p, seed) -> (att, lse); the model file closes it over frags / heads / (B, N)
+    attn_fwd: Callable          # (i, qkv, drop_p, seed) -> (att, lse); closed over the bias fragments or (B, N)
     attn_bwd: Callable          # (i, s, g_att, drop_p, seed) -> g_qkv, or (g_qkv, g_table) when table_grad; None in a forward-only spec
     hidden: int                 # MLP hidden width
     keys: Tuple[str, str]       # packed-weight keys of the two attention projections: ("qkv", "proj") | ("in", "out")
@@ -28,6 +26,17 @@ class BlockSpec(NamedTuple):
     prefix: str                 # "window_blocks" | "transformer_blocks"
     proj_drop: bool             # dropout behind the output projection (nn.MultiheadAttention has none)
     table_grad: bool            # attn_bwd also returns the relative-position table gradient
+
+
+def window_block_spec(hidden, frags_t, frags_n=None):
+    """The 8x8-window block of FastTransformer (width 192 / 12 heads) and WindowTransformer (128 / 8; ops.window_attn reads the
+    head count off qkv): relative-position bias, all three dropout sites.  frags_n: the backward's bias fragments."""
+    return BlockSpec(
+        attn_fwd=lambda i, qkv, drop_p, seed: ops.window_attn(qkv, frags_t[i], drop_p, seed, save_lse=True),
+        attn_bwd=lambda i, s, g_att, drop_p, seed: ops.window_attn_bwd(s["qkv"], g_att, s["att"], s["lse"], frags_n[i], drop_p, seed),
+        hidden=hidden, keys=("qkv", "proj"),
+        names=(".attn.qkv.weight", ".attn.qkv.bias", ".attn.proj.weight", ".attn.proj.bias"),
+        prefix="window_blocks", proj_drop=True, table_grad=True)
 
 
 def site_seed(seed: int, block: int, site: int) -> int:
@@ -68,7 +77,7 @@ def blocks_forward(spec: BlockSpec, pk, nblocks, xw, drop_p, seed):
     for i in range(nblocks):
         b = f"b{i}."
         s = {"x_in": xw}
-        s["y1"], s["mean1"], s["rstd1"] = spec.norm(xw, pk[b + "norm1.w"], pk[b + "norm1.b"], save_stats=True)
+        s["y1"], s["mean1"], s["rstd1"] = ops.layernorm(xw, pk[b + "norm1.w"], pk[b + "norm1.b"], save_stats=True)
         s["qkv"] = ops.gemm_tokens(s["y1"], pk[b + k_in + ".w"], pk[b + k_in + ".b"], "bf16")
         s["att"], s["lse"] = spec.attn_fwd(i, s["qkv"], drop_p, site_seed(seed, i, 0))
         if spec.proj_drop:
@@ -77,7 +86,7 @@ def blocks_forward(spec: BlockSpec, pk, nblocks, xw, drop_p, seed):
         else:
             xm = ops.gemm_tokens(s["att"], pk[b + k_out + ".w"], pk[b + k_out + ".b"], "res", res=xw)
         s["x_mid"] = xm
-        s["y2"], s["mean2"], s["rstd2"] = spec.norm(xm, pk[b + "norm2.w"], pk[b + "norm2.b"], save_stats=True)
+        s["y2"], s["mean2"], s["rstd2"] = ops.layernorm(xm, pk[b + "norm2.w"], pk[b + "norm2.b"], save_stats=True)
         s["hpre"] = torch.empty((xm.shape[0], spec.hidden), dtype=BF16, device=xm.device)
         s["hid"] = ops.gemm_tokens(s["y2"], pk[b + "fc1.w"], pk[b + "fc1.b"], "gelu", aux=s["hpre"])
         xw = ops.gemm_tokens(s["hid"], pk[b + "fc2.w"], pk[b + "fc2.b"], "res", res=xm,
@@ -109,10 +118,10 @@ def blocks_backward(spec: BlockSpec, pk, blocks, g, ready, g_x, drop_p, seed):
         g_y2 = ops.gemm_tokens(g_h, pk[b + "fc1.wd"], None, "bf16")
         del g_h
         if spec.proj_drop and drop_p > 0:          # + proj_drop's backward of the result (bf16), in the same pass
-            g_xm, g[p + ".norm2.weight"], g[p + ".norm2.bias"], g_o = spec.norm_bwd(
+            g_xm, g[p + ".norm2.weight"], g[p + ".norm2.bias"], g_o = ops.layernorm_bwd(
                 g_y2, s["x_mid"], s["mean2"], s["rstd2"], pk[b + "norm2.w"], gres=g_x, drop=(drop_p, site_seed(seed, i, 1)))
         else:
-            g_xm, g[p + ".norm2.weight"], g[p + ".norm2.bias"] = spec.norm_bwd(
+            g_xm, g[p + ".norm2.weight"], g[p + ".norm2.bias"] = ops.layernorm_bwd(
                 g_y2, s["x_mid"], s["mean2"], s["rstd2"], pk[b + "norm2.w"], gres=g_x)
             g_o = g_xm
         g[p + w_out], g[p + b_out] = ops.gemm_wgrad_bias(g_o, s["att"])
@@ -126,10 +135,10 @@ def blocks_backward(spec: BlockSpec, pk, blocks, g, ready, g_x, drop_p, seed):
         g_y1 = ops.gemm_tokens(g_qkv, pk[b + k_in + ".wd"], None, "bf16")
         del g_qkv, g_att
         if drop_p > 0 and i > 0:          # + the MLP dropout's backward for the block below
-            g_x, g[p + ".norm1.weight"], g[p + ".norm1.bias"], g_xd = spec.norm_bwd(
+            g_x, g[p + ".norm1.weight"], g[p + ".norm1.bias"], g_xd = ops.layernorm_bwd(
                 g_y1, s["x_in"], s["mean1"], s["rstd1"], pk[b + "norm1.w"], gres=g_xm, drop=(drop_p, site_seed(seed, i - 1, 2)))
         else:
-            g_x, g[p + ".norm1.weight"], g[p + ".norm1.bias"] = spec.norm_bwd(
+            g_x, g[p + ".norm1.weight"], g[p + ".norm1.bias"] = ops.layernorm_bwd(
                 g_y1, s["x_in"], s["mean1"], s["rstd1"], pk[b + "norm1.w"], gres=g_xm)
         ready(*[p + sfx for sfx in announce])
     return g_x
@@ -141,11 +150,11 @@ def blocks_infer(pk, xw, keys, attn):
     k_in, k_out = keys
     for i in range(pk["nblocks"]):
         b = f"b{i}."
-        y = ops.layernorm128(xw, pk[b + "norm1.w"], pk[b + "norm1.b"])
+        y = ops.layernorm(xw, pk[b + "norm1.w"], pk[b + "norm1.b"])
         qkv = ops.gemm_tokens(y, pk[b + k_in + ".w"], pk[b + k_in + ".b"], "bf16")
         att = attn(i, qkv)
         ops.gemm_tokens(att, pk[b + k_out + ".w"], pk[b + k_out + ".b"], "res", res=xw, out=xw)
-        y = ops.layernorm128(xw, pk[b + "norm2.w"], pk[b + "norm2.b"])
+        y = ops.layernorm(xw, pk[b + "norm2.w"], pk[b + "norm2.b"])
         hid = ops.gemm_tokens(y, pk[b + "fc1.w"], pk[b + "fc1.b"], "gelu")
         ops.gemm_tokens(hid, pk[b + "fc2.w"], pk[b + "fc2.b"], "res", res=xw, out=xw)
     return xw

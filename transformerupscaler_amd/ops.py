@@ -7,16 +7,16 @@ on the caller's current HIP stream.
 from __future__ import annotations
 
 import contextlib
-import os
+import ctypes
 import struct
 
 import numpy as np
 import torch
 
-from . import _lib
-from .resize_taps import aa_taps
+from . import _lib, resize_taps
 
-BF16, F32 = torch.bfloat16, torch.float32
+BF16, F16, F32 = torch.bfloat16, torch.float16, torch.float32
+_DTYPE_CODE = {BF16: 0, F32: 1}          # the a_dtype / p_dtype / q_dtype argument of the token-matrix entries
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -50,6 +50,42 @@ def _chk(t: torch.Tensor, dtype, shape=None, name="tensor"):
 
 def _opt(t, dtype, shape, name):
     return None if t is None else _chk(t, dtype, shape, name)
+
+
+def _seed(seed):
+    """A dropout seed as the unsigned 32-bit argument of the C ABI."""
+    return int(seed) & 0xFFFFFFFF
+
+
+# ---- device tables: every tap / band / plan table is built on the host by a pure function of resize_taps.py and uploaded once ----
+_tables = {}
+
+
+def _table(build, device, sizes):
+    """build(*sizes) on `device`, memoised on (builder, device, sizes): the numpy arrays of the tuple it returns are uploaded, its
+    plain integers pass through, None stays None."""
+    key = (build, str(device), sizes)
+    if key not in _tables:
+        host = build(*sizes)
+        _tables[key] = None if host is None else tuple(
+            torch.from_numpy(np.ascontiguousarray(v)).to(device) if isinstance(v, np.ndarray) else v for v in host)
+    return _tables[key]
+
+
+def _taps_on(device, in_size, out_size):
+    return _table(resize_taps.aa_taps, device, (in_size, out_size))
+
+
+def _inv_taps_on(device, in_size, out_size):
+    return _table(resize_taps.aa_inverse_ranges, device, (in_size, out_size))
+
+
+def _bicubic_on(device, in_size, out_size):
+    return _table(resize_taps.bicubic_taps, device, (in_size, out_size))
+
+
+def _pil_taps_on(device, in_size, out_size):
+    return _table(resize_taps.pil_bilinear_coeffs, device, (in_size, out_size))
 
 
 # ---- zero pool: the backward pass needs ~130 small zero-initialised fp32 buffers per step (atomically accumulated weight /
@@ -192,18 +228,6 @@ def conv_planar(x, w28, bias, r=1, add=None, clamp=False):
     return (out[0], out[1]) if both else out
 
 
-_TAP_CACHE = {}
-
-
-def _taps_on(device, in_size, out_size):
-    key = (str(device), in_size, out_size)
-    if key not in _TAP_CACHE:
-        lo, n, w, k = aa_taps(in_size, out_size)
-        _TAP_CACHE[key] = (torch.from_numpy(lo).to(device), torch.from_numpy(n).to(device),
-                           torch.from_numpy(w).to(device), k)
-    return _TAP_CACHE[key]
-
-
 def resize_aa(x, size, clamp=False):
     """clamp = "both" (training): returns (unclamped, clamped), written by the same kernel pass."""
     B, C, Hi, Wi = x.shape
@@ -223,19 +247,10 @@ TAIL_TILE_H = 16          # = OT_H of csrc/tail_fused.hip
 
 def tail_fused(x, wfu, bfu, wfc, bfc, ui, r, out_hw, clamp=True):
     """Last final_upscale stage + final_upscale_conv + "+ upscaled_input" + Resize(out_hw) + clamp in one kernel."""
-    from .resize_taps import taps_or_identity, tile_extent
     B, C, H, W = x.shape
     Hs, Ws = H * r, W * r
     Ho, Wo = out_hw
-    key = (str(x.device), "tail", Hs, Ws, Ho, Wo)
-    if key not in _TAP_CACHE:
-        ylo, yn, yw, ky = taps_or_identity(Hs, Ho)
-        xlo, xn, xw, kx = taps_or_identity(Ws, Wo)
-        d = x.device
-        _TAP_CACHE[key] = (torch.from_numpy(ylo).to(d), torch.from_numpy(yn).to(d), torch.from_numpy(np.ascontiguousarray(yw)).to(d), ky,
-                           torch.from_numpy(xlo).to(d), torch.from_numpy(xn).to(d), torch.from_numpy(np.ascontiguousarray(xw)).to(d), kx,
-                           tile_extent(Hs, Ho, TAIL_TILE_H), tile_extent(Ws, Wo, 64))
-    ylo, yn, yw, ky, xlo, xn, xw, kx, eh, ew = _TAP_CACHE[key]
+    ylo, yn, yw, ky, xlo, xn, xw, kx, eh, ew = _table(resize_taps.tail_fused_tables, x.device, (Hs, Ws, Ho, Wo, TAIL_TILE_H, 64))
     out = torch.empty((B, 3, Ho, Wo), dtype=F32, device=x.device)
     _lib.call("tup_tail_fused_fwd", _chk(x, F32, None, "x"), _chk(wfu, F32, (3 * r * r, 28), "wfu"), _chk(bfu, F32, (3 * r * r,), "bfu"),
               _chk(wfc, F32, (3, 28), "wfc"), _chk(bfc, F32, (3,), "bfc"), _chk(ui, F32, (B, 3, Hs, Ws), "ui"), out.data_ptr(),
@@ -248,38 +263,9 @@ TAIL_STREAM_WAVES_PER_SIMD = 3      # csrc/tail_stream.hip: 150 registers (152 o
 
 
 def _tail_stream_plan(device, B, H, W, Ho, Wo):
-    """Decomposition of the fused streaming tail + Resize (csrc/tail_stream.hip, RESIZE = true): strip stride, band height, the
-    output columns / rows each strip / band owns.  None when a tap table has more than 4 taps (then the Resize runs as its own kernel)."""
-    key = (str(device), "tail_stream", B, H, W, Ho, Wo)
-    if key not in _TAP_CACHE:
-        from .resize_taps import aa_taps
-        ylo, yn, yw, ky = aa_taps(2 * H, Ho)
-        xlo, xn, xw, kx = aa_taps(2 * W, Wo)
-        plan = None
-        if int(yn.max()) <= 4 and int(xn.max()) <= 4:
-            sc = 60 - (int(xn.max()) - 1 + 1) // 2
-            ext = (int(yn.max()) - 1 + 1) // 2
-            nstrip = (W + sc - 1) // sc
-            nb = max(1, (256 * 4 * TAIL_STREAM_WAVES_PER_SIMD) // max(1, B * nstrip))      # fill the chip once at the kernel's occupancy
-            bh = max(12, ((H + nb - 1) // nb + 2) // 3 * 3)
-            nband = (H + bh - 1) // bh
-            oxb = np.searchsorted(xlo, 2 * sc * np.arange(nstrip + 1), side="left").astype(np.int32)
-            oyb = np.searchsorted(ylo, 2 * bh * np.arange(nband + 1), side="left").astype(np.int32)
-            oxb[-1], oyb[-1] = Wo, Ho
-            ok = True
-            for s_ in range(nstrip):           # every owned column's taps inside the strip's 120 valid HR columns, <= 128 gathered
-                a, b_ = int(oxb[s_]), int(oxb[s_ + 1])
-                if b_ > a:
-                    ok &= bool((xlo[a:b_] + xn[a:b_]).max() <= 2 * s_ * sc + 120) and b_ - a <= 128
-            for k_ in range(nband):            # every owned row's taps inside the rows the band computes
-                a, b_ = int(oyb[k_]), int(oyb[k_ + 1])
-                if b_ > a:
-                    ok &= bool((ylo[a:b_] + yn[a:b_]).max() <= 2 * min(H, (k_ + 1) * bh + ext))
-            if ok:
-                t = lambda arr: torch.from_numpy(np.ascontiguousarray(arr)).to(device)
-                plan = (t(ylo), t(yn), t(yw), ky, t(xlo), t(xn), t(xw), kx, t(oxb), t(oyb), sc, bh, ext)
-        _TAP_CACHE[key] = plan
-    return _TAP_CACHE[key]
+    """resize_taps.tail_stream_plan on `device`, sized to fill the chip once at the kernel's occupancy.  None: the Resize runs as
+    its own kernel."""
+    return _table(resize_taps.tail_stream_plan, device, (B, H, W, Ho, Wo, 256 * 4 * TAIL_STREAM_WAVES_PER_SIMD))
 
 
 def tail_stream_fits(B, H, W, out_hw=None):
@@ -334,35 +320,76 @@ def clamp01(x):
     return out
 
 
+# LayerNorm rows are 192 wide (FastTransformer) or 128 wide (the two other models); each width has its own C entries
+_LAYERNORM = {192: ("tup_layernorm_fwd", "tup_layernorm_bwd"), 128: ("tup_layernorm128_fwd", "tup_layernorm128_bwd")}
+
+
+def _layernorm_entries(D):
+    if D not in _LAYERNORM:
+        raise ValueError(f"LayerNorm rows must be 192 or 128 wide, got {D}")
+    return _LAYERNORM[D]
+
+
 def layernorm(x, gamma, beta, save_stats=False):
     M, D = x.shape
-    assert D == 192
-    y = torch.empty((M, 192), dtype=BF16, device=x.device)
+    entry = _layernorm_entries(D)[0]
+    y = torch.empty((M, D), dtype=BF16, device=x.device)
     mean = rstd = None
     if save_stats:
         mean = torch.empty((M,), dtype=F32, device=x.device)
         rstd = torch.empty((M,), dtype=F32, device=x.device)
-    _lib.call("tup_layernorm_fwd", _chk(x, F32, None, "x"), _chk(gamma, F32, (192,), "gamma"),
-              _chk(beta, F32, (192,), "beta"), y.data_ptr(), None if mean is None else mean.data_ptr(),
-              None if rstd is None else rstd.data_ptr(), M, _stream())
+    _lib.call(entry, _chk(x, F32, None, "x"), _chk(gamma, F32, (D,), "gamma"), _chk(beta, F32, (D,), "beta"), y.data_ptr(),
+              None if mean is None else mean.data_ptr(), None if rstd is None else rstd.data_ptr(), M, _stream())
     return (y, mean, rstd) if save_stats else y
 
 
-def relpos_bias_expand(table):
-    frag = torch.empty((12, 4, 4, 64, 4), dtype=F32, device=table.device)
-    _lib.call("tup_relpos_bias_expand", _chk(table, F32, (225, 12), "table"), frag.data_ptr(), _stream())
+# Window attention has 12 heads (FastTransformer, width 192) or 8 (WindowTransformer, width 128).  Per head count the C entries:
+# forward, backward, bias expansion in the forward / the backward kernel's layout, table-gradient reduce -- and the `heads`
+# argument that only the general entries take
+_WINDOW_ATTN = {
+    12: ("tup_window_attn_fwd", "tup_window_attn_bwd", "tup_relpos_bias_expand", "tup_relpos_bias_expand_n",
+         "tup_relpos_bias_reduce", ()),
+    8: ("tup_window_attn_fwd_h", "tup_window_attn_bwd_h", "tup_relpos_bias_expand_h", "tup_relpos_bias_expand_n_h",
+        "tup_relpos_bias_reduce_h", (8,)),
+}
+
+
+def _window_attn_entries(heads):
+    if heads not in _WINDOW_ATTN:
+        raise ValueError(f"window attention takes 12 or 8 heads of 16 channels, got {heads}")
+    return _WINDOW_ATTN[heads]
+
+
+def _relpos_expand(table, which):
+    heads = table.shape[1]
+    entries = _window_attn_entries(heads)
+    frag = torch.empty((heads, 4, 4, 64, 4), dtype=F32, device=table.device)
+    _lib.call(entries[which], _chk(table, F32, (225, heads), "table"), frag.data_ptr(), *entries[5], _stream())
     return frag
 
 
+def relpos_bias_expand(table):
+    """Relative-position table fp32 [225][heads] -> the dense bias in the forward kernel's fragment layout."""
+    return _relpos_expand(table, 2)
+
+
+def relpos_bias_expand_n(table):
+    """... in the backward kernel's fragment layout."""
+    return _relpos_expand(table, 3)
+
+
 def window_attn(qkv, bias_frag, drop_p=0.0, drop_seed=0, save_lse=False):
-    """WindowAttention core.  save_lse (training): also returns the fp32 [M // 64][12][64] log-sum-exp of every score row, which
-    window_attn_bwd rebuilds the probabilities from."""
+    """WindowAttention core on bf16 [M][48 heads].  save_lse (training): also returns the fp32 [M // 64][heads][64] log-sum-exp of
+    every score row, which window_attn_bwd rebuilds the probabilities from."""
     M, D = qkv.shape
-    assert D == 576 and M % 64 == 0
-    out = torch.empty((M, 192), dtype=BF16, device=qkv.device)
-    lse = torch.empty((M // 64, 12, 64), dtype=F32, device=qkv.device) if save_lse else None
-    _lib.call("tup_window_attn_fwd", _chk(qkv, BF16, None, "qkv"), _chk(bias_frag, F32, (12, 4, 4, 64, 4), "bias"),
-              out.data_ptr(), lse.data_ptr() if save_lse else None, M // 64, float(drop_p), int(drop_seed) & 0xFFFFFFFF, _stream())
+    heads = D // 48
+    fwd, _, _, _, _, hargs = _window_attn_entries(heads)
+    if D != 48 * heads or M % 64 != 0:
+        raise ValueError(f"qkv: expected [64 windows][48 heads], got {tuple(qkv.shape)}")
+    out = torch.empty((M, 16 * heads), dtype=BF16, device=qkv.device)
+    lse = torch.empty((M // 64, heads, 64), dtype=F32, device=qkv.device) if save_lse else None
+    _lib.call(fwd, _chk(qkv, BF16, None, "qkv"), _chk(bias_frag, F32, (heads, 4, 4, 64, 4), "bias"),
+              out.data_ptr(), lse.data_ptr() if save_lse else None, M // 64, *hargs, float(drop_p), _seed(drop_seed), _stream())
     return (out, lse) if save_lse else out
 
 
@@ -372,7 +399,6 @@ def gemm_tokens(a, wt, bias, epilogue, res=None, out=None, aux=None, drop_p=0.0,
     M, K = a.shape
     N = wt.shape[0]
     assert tuple(wt.shape) == (N, K) and N % 64 == 0 and K % 64 == 0
-    a_dtype = {BF16: 0, F32: 1}[a.dtype]
     epi = {"bf16": 0, "gelu": 1, "res": 2, "gelu_bwd": 3}[epilogue]
     resp = auxp = None
     if epi == 2:
@@ -384,9 +410,9 @@ def gemm_tokens(a, wt, bias, epilogue, res=None, out=None, aux=None, drop_p=0.0,
         out = torch.empty((M, N), dtype=BF16, device=a.device)
         if epi == 3 or (epi == 1 and aux is not None):
             auxp = _chk(aux, BF16, (M, N), "aux")
-    _lib.call("tup_gemm_tokens_fwd", _chk(a, a.dtype, None, "a"), a_dtype, K, _chk(wt, BF16, None, "wt"),
+    _lib.call("tup_gemm_tokens_fwd", _chk(a, a.dtype, None, "a"), _DTYPE_CODE[a.dtype], K, _chk(wt, BF16, None, "wt"),
               _opt(bias, F32, (N,), "bias"), resp, auxp, out.data_ptr(), N, M, N, K, epi, float(drop_p),
-              int(drop_seed) & 0xFFFFFFFF, _stream())
+              _seed(drop_seed), _stream())
     return out
 
 
@@ -421,24 +447,29 @@ def fused_attn_block(x, gamma, beta, wh, bh, bias_frag, wproj, bproj):
     return x
 
 
-F16 = torch.float16
+def _pointer_table(blocks, operands, what):
+    """(ctypes array of the blocks' device pointers, number of blocks, the tensors -- kept alive by the caller holding the tuple)
+    for the multi-block kernels.  operands: per tensor of a block (dtype, shape), or (dtype, element count) for a flat packed one."""
+    if not 1 <= len(blocks) <= 8:
+        raise ValueError("1..8 blocks per launch")
+    ptrs = []
+    for blk in blocks:
+        assert len(blk) == len(operands)
+        for i, (t, (dt, sh)) in enumerate(zip(blk, operands)):
+            if isinstance(sh, int):
+                if t.numel() != sh:
+                    raise ValueError(f"{what} operand {i}: {t.numel()} elements, expected {sh}")
+                sh = None
+            ptrs.append(_chk(t, dt, sh, f"{what} operand {i}"))
+    return ((ctypes.c_void_p * len(ptrs))(*ptrs), len(blocks), [list(b) for b in blocks])
 
 
 def block_table(blocks):
     """Pointer table for tup_fused_blocks32_fwd: `blocks` = per block the 9 tensors (wh, bh, bias_frag, wproj, bproj, w1, b1, w2, b2)
     with norm1 / norm2 folded into attn.qkv / mlp.0 (packing.fold_layernorm), w1 / b1 = mlp.0 / 4 (packing.pack_fc1_fused_q),
-    w2 = 4 W2 in fp16 (packing.pack_fc2_h4), validated here.  Returns (ctypes array [nblk*9] of device pointers, nblk, the
-    tensors -- kept alive by the caller holding the tuple)."""
-    import ctypes
-    shapes = [(BF16, (12, 64, 192)), (F32, (12, 48)), (F32, (12, 4, 4, 64, 4)), (BF16, (192, 192)), (F32, (192,)),
-              (BF16, (768, 192)), (F32, (768,)), (F16, (192, 768)), (F32, (192,))]
-    if not 1 <= len(blocks) <= 8:
-        raise ValueError("1..8 blocks per launch")
-    ptrs = []
-    for blk in blocks:
-        assert len(blk) == 9
-        ptrs += [_chk(t, dt, sh, f"block operand {i}") for i, (t, (dt, sh)) in enumerate(zip(blk, shapes))]
-    return ((ctypes.c_void_p * len(ptrs))(*ptrs), len(blocks), [list(b) for b in blocks])
+    w2 = 4 W2 in fp16 (packing.pack_fc2_h4), validated here."""
+    return _pointer_table(blocks, [(BF16, (12, 64, 192)), (F32, (12, 48)), (F32, (12, 4, 4, 64, 4)), (BF16, (192, 192)), (F32, (192,)),
+                                   (BF16, (768, 192)), (F32, (768,)), (F16, (192, 768)), (F32, (192,))], "block")
 
 
 def fused_blocks32(x, table):
@@ -459,19 +490,9 @@ def clock_probe():
 
 def stream_table(blocks):
     """Pointer table for tup_blocks_stream_fwd: per block the 7 tensors of packing.pack_stream_block (wqk, wv, wproj, w1, w2, tab,
-    sbias), validated here.  Returns (ctypes array, nblk, the tensors -- kept alive by the caller holding the tuple)."""
-    import ctypes
-    shapes = [(BF16, 12 * 6144), (BF16, 6 * 6144), (BF16, 6 * 6144), (BF16, 24 * 6144), (F16, 24 * 6144), (F32, 1536), (F32, 12 * 2 * 2 * 64 * 16)]
-    if not 1 <= len(blocks) <= 8:
-        raise ValueError("1..8 blocks per launch")
-    ptrs = []
-    for blk in blocks:
-        assert len(blk) == 7
-        for i, (t, (dt, n)) in enumerate(zip(blk, shapes)):
-            if t.numel() != n:
-                raise ValueError(f"stream block operand {i}: {t.numel()} elements, expected {n}")
-            ptrs.append(_chk(t, dt, None, f"stream block operand {i}"))
-    return ((ctypes.c_void_p * len(ptrs))(*ptrs), len(blocks), [list(b) for b in blocks])
+    sbias), validated here."""
+    return _pointer_table(blocks, [(BF16, 12 * 6144), (BF16, 6 * 6144), (BF16, 6 * 6144), (BF16, 24 * 6144), (F16, 24 * 6144),
+                                   (F32, 1536), (F32, 12 * 2 * 2 * 64 * 16)], "stream block")
 
 
 def blocks_stream(x, table, out_bf16=False):
@@ -541,43 +562,33 @@ def patch_unembed(x, wt, bias, skip):
 # ------------------------------------------------------------------------------------------------
 # backward wrappers
 # ------------------------------------------------------------------------------------------------
-def gemm_wgrad(p, q, out=None):
-    """out[NI][NJ] fp32 (+)= p^T q; p [M][NI], q [M][NJ] (bf16 or fp32)."""
+def _gemm_wgrad(p, q, out, want_bias):
     M, NI = p.shape
     NJ = q.shape[1]
     assert q.shape[0] == M and NI % 64 == 0 and NJ % 64 == 0
     if out is None:
         out = _zeros((NI, NJ), p.device)
-    if deterministic_enabled():
-        slab = _det_slab(wgrad_slab_floats(0, M, NI, NJ), p.device)
-        _lib.call("tup_gemm_wgrad_bias_det", _chk(p, p.dtype, None, "p"), {BF16: 0, F32: 1}[p.dtype], NI,
-                  _chk(q, q.dtype, None, "q"), {BF16: 0, F32: 1}[q.dtype], NJ, _chk(out, F32, (NI, NJ), "out"), NJ, None,
-                  M, NI, NJ, slab.data_ptr(), _stream())
-        return out
-    _lib.call("tup_gemm_wgrad", _chk(p, p.dtype, None, "p"), {BF16: 0, F32: 1}[p.dtype], NI,
-              _chk(q, q.dtype, None, "q"), {BF16: 0, F32: 1}[q.dtype], NJ, _chk(out, F32, (NI, NJ), "out"), NJ,
-              M, NI, NJ, _stream())
-    return out
+    # (out and db are neighbours in the zero pool: the deterministic entry then adds weight and bias slices in one reduce launch)
+    db = _zeros((NI,), p.device) if want_bias else None
+    head = (_chk(p, p.dtype, None, "p"), _DTYPE_CODE[p.dtype], NI, _chk(q, q.dtype, None, "q"), _DTYPE_CODE[q.dtype], NJ,
+            _chk(out, F32, (NI, NJ), "out"), NJ)
+    slab = _det_slab(0, M, NI, NJ, p.device)
+    if want_bias or slab is not None:
+        # tup_gemm_wgrad has no twin of its own: its deterministic form is the bias twin with a null bias pointer
+        _reduce("tup_gemm_wgrad_bias", slab, *head, None if db is None else db.data_ptr(), M, NI, NJ)
+    else:
+        _lib.call("tup_gemm_wgrad", *head, M, NI, NJ, _stream())
+    return out, db
+
+
+def gemm_wgrad(p, q, out=None):
+    """out[NI][NJ] fp32 (+)= p^T q; p [M][NI], q [M][NJ] (bf16 or fp32)."""
+    return _gemm_wgrad(p, q, out, False)[0]
 
 
 def gemm_wgrad_bias(p, q):
     """(dW [NI][NJ], db [NI]) = (p^T q, column sums of p): weight and bias gradient of a Linear layer in one pass over p."""
-    M, NI = p.shape
-    NJ = q.shape[1]
-    assert q.shape[0] == M and NI % 64 == 0 and NJ % 64 == 0
-    out = _zeros((NI, NJ), p.device)
-    db = _zeros((NI,), p.device)
-    if deterministic_enabled():
-        # (out and db are neighbours in the zero pool: the entry then adds weight and bias slices in one reduce launch)
-        slab = _det_slab(wgrad_slab_floats(0, M, NI, NJ), p.device)
-        _lib.call("tup_gemm_wgrad_bias_det", _chk(p, p.dtype, None, "p"), {BF16: 0, F32: 1}[p.dtype], NI,
-                  _chk(q, q.dtype, None, "q"), {BF16: 0, F32: 1}[q.dtype], NJ, out.data_ptr(), NJ, db.data_ptr(),
-                  M, NI, NJ, slab.data_ptr(), _stream())
-        return out, db
-    _lib.call("tup_gemm_wgrad_bias", _chk(p, p.dtype, None, "p"), {BF16: 0, F32: 1}[p.dtype], NI,
-              _chk(q, q.dtype, None, "q"), {BF16: 0, F32: 1}[q.dtype], NJ, out.data_ptr(), NJ, db.data_ptr(),
-              M, NI, NJ, _stream())
-    return out, db
+    return _gemm_wgrad(p, q, None, True)
 
 
 PATCH_WGRAD_WIDE = True          # A/B switch: the wide-tile kernel (tup_patch_wgrad_bf16) for the two patch weights
@@ -588,25 +599,14 @@ def patch_wgrad(p, fmap, reflect):
     _, _, nwy, nwx = window_geometry(H, W)
     out = _zeros((192, 4096), p.device)
     M = B * nwy * nwx * 64
-    det = deterministic_enabled()
-    if PATCH_WGRAD_WIDE and B * H * W * 128 < 2 ** 31:
+    pp = _chk(p, F32, (M, 192), "p")
+    wide = PATCH_WGRAD_WIDE and B * H * W * 128 < 2 ** 31
+    if wide:
         # bf16 token rows (the rounding the fp32 entry applies on load): the wide kernel fetches its operands by DMA
-        _chk(p, F32, (B * nwy * nwx * 64, 192), "p")
         pb = p.to(BF16)
-        if det:
-            slab = _det_slab(wgrad_slab_floats(1, M, 192, 4096), p.device)
-            _lib.call("tup_patch_wgrad_bf16_det", pb.data_ptr(), _chk(fmap, BF16, None, "map"), out.data_ptr(), B, H, W, int(reflect),
-                      slab.data_ptr(), _stream())
-            return out
-        _lib.call("tup_patch_wgrad_bf16", pb.data_ptr(), _chk(fmap, BF16, None, "map"), out.data_ptr(), B, H, W, int(reflect), _stream())
-        return out
-    if det:
-        slab = _det_slab(wgrad_slab_floats(0, M, 192, 4096), p.device)
-        _lib.call("tup_patch_wgrad_det", _chk(p, F32, (M, 192), "p"), _chk(fmap, BF16, None, "map"),
-                  out.data_ptr(), B, H, W, int(reflect), slab.data_ptr(), _stream())
-        return out
-    _lib.call("tup_patch_wgrad", _chk(p, F32, (B * nwy * nwx * 64, 192), "p"), _chk(fmap, BF16, None, "map"),
-              out.data_ptr(), B, H, W, int(reflect), _stream())
+        pp = pb.data_ptr()
+    _reduce("tup_patch_wgrad_bf16" if wide else "tup_patch_wgrad", _det_slab(int(wide), M, 192, 4096, p.device),
+            pp, _chk(fmap, BF16, None, "map"), out.data_ptr(), B, H, W, int(reflect))
     return out
 
 
@@ -614,47 +614,30 @@ def colsum(g, out=None, rowmask=None):
     M, N = g.shape
     if out is None:
         out = _zeros((N,), g.device)
-    if deterministic_enabled():
-        slab = _det_slab(wgrad_slab_floats(2, M, N), g.device)
-        _lib.call("tup_colsum_det", _chk(g, g.dtype, None, "g"), {BF16: 0, F32: 1}[g.dtype], N, _chk(out, F32, (N,), "out"),
-                  M, N, _opt(rowmask, torch.uint8, (M,), "rowmask"), slab.data_ptr(), _stream())
-        return out
-    _lib.call("tup_colsum", _chk(g, g.dtype, None, "g"), {BF16: 0, F32: 1}[g.dtype], N, _chk(out, F32, (N,), "out"),
-              M, N, _opt(rowmask, torch.uint8, (M,), "rowmask"), _stream())
+    _reduce("tup_colsum", _det_slab(2, M, N, 0, g.device), _chk(g, g.dtype, None, "g"), _DTYPE_CODE[g.dtype], N,
+            _chk(out, F32, (N,), "out"), M, N, _opt(rowmask, torch.uint8, (M,), "rowmask"))
     return out
 
 
 def layernorm_bwd(gy, x, mean, rstd, gamma, gres=None, drop=None):
     """drop = (p, seed): also returns dx * dropout mask / (1 - p) as bf16 (dropout_bwd of dx, fused): (dx, dgamma, dbeta, gdrop)."""
-    M = x.shape[0]
-    dx = torch.empty((M, 192), dtype=F32, device=x.device)
-    dg = _zeros((192,), x.device)
-    db = _zeros((192,), x.device)
-    gd = torch.empty((M, 192), dtype=BF16, device=x.device) if drop else None
-    if deterministic_enabled():
-        slab = _det_slab(wgrad_slab_floats(3, M, 192), x.device)
-        _lib.call("tup_layernorm_bwd_det", _chk(gy, BF16, (M, 192), "gy"), _chk(x, F32, (M, 192), "x"), _chk(mean, F32, (M,), "mean"),
-                  _chk(rstd, F32, (M,), "rstd"), _chk(gamma, F32, (192,), "gamma"), _opt(gres, F32, (M, 192), "gres"),
-                  dx.data_ptr(), dg.data_ptr(), db.data_ptr(), M, gd.data_ptr() if drop else None,
-                  float(drop[0]) if drop else 0.0, (int(drop[1]) & 0xFFFFFFFF) if drop else 0, slab.data_ptr(), _stream())
-        return (dx, dg, db, gd) if drop else (dx, dg, db)
-    _lib.call("tup_layernorm_bwd", _chk(gy, BF16, (M, 192), "gy"), _chk(x, F32, (M, 192), "x"), _chk(mean, F32, (M,), "mean"),
-              _chk(rstd, F32, (M,), "rstd"), _chk(gamma, F32, (192,), "gamma"), _opt(gres, F32, (M, 192), "gres"),
-              dx.data_ptr(), dg.data_ptr(), db.data_ptr(), M, gd.data_ptr() if drop else None,
-              float(drop[0]) if drop else 0.0, (int(drop[1]) & 0xFFFFFFFF) if drop else 0, _stream())
+    M, D = x.shape
+    entry = _layernorm_entries(D)[1]
+    dx = torch.empty((M, D), dtype=F32, device=x.device)
+    dg = _zeros((D,), x.device)
+    db = _zeros((D,), x.device)
+    gd = torch.empty((M, D), dtype=BF16, device=x.device) if drop else None
+    _reduce(entry, _det_slab(3, M, D, 0, x.device), _chk(gy, BF16, (M, D), "gy"), _chk(x, F32, (M, D), "x"),
+            _chk(mean, F32, (M,), "mean"), _chk(rstd, F32, (M,), "rstd"), _chk(gamma, F32, (D,), "gamma"),
+            _opt(gres, F32, (M, D), "gres"), dx.data_ptr(), dg.data_ptr(), db.data_ptr(), M, gd.data_ptr() if drop else None,
+            float(drop[0]) if drop else 0.0, _seed(drop[1]) if drop else 0)
     return (dx, dg, db, gd) if drop else (dx, dg, db)
-
-
-def relpos_bias_expand_n(table):
-    frag = torch.empty((12, 4, 4, 64, 4), dtype=F32, device=table.device)
-    _lib.call("tup_relpos_bias_expand_n", _chk(table, F32, (225, 12), "table"), frag.data_ptr(), _stream())
-    return frag
 
 
 def dropout_bwd(g, drop_p, drop_seed):
     """bf16 [M][192] = fp32 g * mask / (1 - p) for the site keyed by drop_seed."""
     out = torch.empty(g.shape, dtype=BF16, device=g.device)
-    _lib.call("tup_dropout_bwd", _chk(g, F32, None, "g"), out.data_ptr(), g.numel(), float(drop_p), int(drop_seed) & 0xFFFFFFFF, _stream())
+    _lib.call("tup_dropout_bwd", _chk(g, F32, None, "g"), out.data_ptr(), g.numel(), float(drop_p), _seed(drop_seed), _stream())
     return out
 
 
@@ -665,17 +648,21 @@ def _attn_bwd_scratch(nwin, heads):
 
 
 def window_attn_bwd(qkv, gout, att, lse, bias_n, drop_p=0.0, drop_seed=0):
-    """att, lse: what window_attn(..., save_lse=True) returned.  Returns (gqkv bf16 [M][576], dtable fp32 [225][12])."""
-    M = qkv.shape[0]
-    assert M % 64 == 0
-    gqkv = torch.empty((M, 576), dtype=BF16, device=qkv.device)
-    dbias = torch.empty((12, 4, 4, 64, 4), dtype=F32, device=qkv.device)
-    scratch = torch.empty(_attn_bwd_scratch(M // 64, 12), dtype=F32, device=qkv.device)
-    _lib.call("tup_window_attn_bwd", _chk(qkv, BF16, (M, 576), "qkv"), _chk(gout, BF16, (M, 192), "gout"),
-              _chk(att, BF16, (M, 192), "att"), _chk(lse, F32, (M // 64, 12, 64), "lse"), _chk(bias_n, F32, (12, 4, 4, 64, 4), "bias_n"),
-              gqkv.data_ptr(), dbias.data_ptr(), scratch.data_ptr(), M // 64, float(drop_p), int(drop_seed) & 0xFFFFFFFF, _stream())
-    dtable = torch.empty((225, 12), dtype=F32, device=qkv.device)
-    _lib.call("tup_relpos_bias_reduce", dbias.data_ptr(), dtable.data_ptr(), _stream())
+    """att, lse: what window_attn(..., save_lse=True) returned.  Returns (gqkv bf16 [M][48 heads], dtable fp32 [225][heads])."""
+    M, D = qkv.shape
+    heads = D // 48
+    _, bwd, _, _, reduce, hargs = _window_attn_entries(heads)
+    if M % 64 != 0:
+        raise ValueError(f"qkv: expected [64 windows][48 heads], got {tuple(qkv.shape)}")
+    gqkv = torch.empty((M, 48 * heads), dtype=BF16, device=qkv.device)
+    dbias = torch.empty((heads, 4, 4, 64, 4), dtype=F32, device=qkv.device)
+    scratch = torch.empty(_attn_bwd_scratch(M // 64, heads), dtype=F32, device=qkv.device)
+    _lib.call(bwd, _chk(qkv, BF16, (M, 48 * heads), "qkv"), _chk(gout, BF16, (M, 16 * heads), "gout"),
+              _chk(att, BF16, (M, 16 * heads), "att"), _chk(lse, F32, (M // 64, heads, 64), "lse"),
+              _chk(bias_n, F32, (heads, 4, 4, 64, 4), "bias_n"), gqkv.data_ptr(), dbias.data_ptr(), scratch.data_ptr(), M // 64,
+              *hargs, float(drop_p), _seed(drop_seed), _stream())
+    dtable = torch.empty((225, heads), dtype=F32, device=qkv.device)
+    _lib.call(reduce, dbias.data_ptr(), dtable.data_ptr(), *hargs, _stream())
     return gqkv, dtable
 
 
@@ -747,16 +734,20 @@ def wgrad_slab_floats(kind, M, NI, NJ=0):
     return n
 
 
-# One slab per device and stream, grown to the largest request and reused: the kernels of a backward run in stream order, and a
-# deterministic entry is done with its slab when its reduce launch has run.  (A slab per call would be ~40 allocations of up to
-# 50 MB per step.)  Replacing a slab by a larger one while kernels that use the old one are still queued is safe only because the
-# slab is allocated on, and used on, the same (current) stream: the caching allocator hands the old block out again in stream
-# order.  The cache never shrinks; release_det_slabs() returns the memory (call it also before destroying a side stream that ran
-# deterministic steps, so that a later stream with a recycled handle does not inherit its slab).
+# The token-path slab: one per device and stream, grown to the largest request and reused: the kernels of a backward run in stream
+# order, and a deterministic entry is done with its slab when its reduce launch has run.  (A slab per call would be ~40 allocations
+# of up to 50 MB per step.)  Replacing a slab by a larger one while kernels that use the old one are still queued is safe only
+# because the slab is allocated on, and used on, the same (current) stream: the caching allocator hands the old block out again in
+# stream order.  The cache never shrinks; release_det_slabs() returns the memory (call it also before destroying a side stream that
+# ran deterministic steps, so that a later stream with a recycled handle does not inherit its slab).
 _det_slabs = {}
 
 
-def _det_slab(n, device):
+def _det_slab(kind, M, NI, NJ, device):
+    """The token-path slab for wgrad_slab_floats(kind, M, NI, NJ) in deterministic mode; None (and no size query) outside it."""
+    if not deterministic_enabled():
+        return None
+    n = wgrad_slab_floats(kind, M, NI, NJ)
     key = (_cur_dev(), _stream())
     slab = _det_slabs.get(key)
     if slab is None or slab.numel() < n:
@@ -779,7 +770,19 @@ def conv_wgrad_slab_floats(kind, B, H, W, r=1):
 
 
 def _slab(kind, B, H, W, device, r=1):
+    """The slab of a weight-gradient conv in deterministic mode, a fresh allocation per wrapper call; None outside it."""
+    if not deterministic_enabled():
+        return None
     return torch.empty((conv_wgrad_slab_floats(kind, B, H, W, r),), dtype=F32, device=device)
+
+
+def _reduce(entry, slab, *args):
+    """Launches a reduction on the current stream: `entry`, which accumulates with float atomics, or, given a slab (what _det_slab
+    / _slab return in deterministic mode), its twin `entry`_det, which takes the same arguments and the slab before the stream."""
+    if slab is None:
+        _lib.call(entry, *args, _stream())
+    else:
+        _lib.call(entry + "_det", *args, slab.data_ptr(), _stream())
 
 
 def conv_c64_wgrad(x, gmap, gr=1):
@@ -788,15 +791,10 @@ def conv_c64_wgrad(x, gmap, gr=1):
     assert C == 64 and tuple(gmap.shape) == (B, H * gr, W * gr, 64)
     dwp = _zeros((gr * gr, 64, 9, 64), x.device)
     db = _zeros((gr * gr, 64), x.device)
-    if deterministic_enabled():
-        slab = _slab(0, B, H, W, x.device)
-        for sp in range(gr * gr):
-            _lib.call("tup_conv3x3_c64_wgrad_det", _chk(x, BF16, None, "x"), _chk(gmap, BF16, None, "gmap"), dwp[sp].data_ptr(),
-                      db[sp].data_ptr(), B, H, W, gr, sp, slab.data_ptr(), _stream())
-        return dwp, db
+    slab = _slab(0, B, H, W, x.device)
     for sp in range(gr * gr):
-        _lib.call("tup_conv3x3_c64_wgrad", _chk(x, BF16, None, "x"), _chk(gmap, BF16, None, "gmap"), dwp[sp].data_ptr(),
-                  db[sp].data_ptr(), B, H, W, gr, sp, _stream())
+        _reduce("tup_conv3x3_c64_wgrad", slab, _chk(x, BF16, None, "x"), _chk(gmap, BF16, None, "gmap"), dwp[sp].data_ptr(),
+                db[sp].data_ptr(), B, H, W, gr, sp)
     return dwp, db
 
 
@@ -805,13 +803,8 @@ def conv_thin_wgrad(x, gpl, want_bias):
     assert C == 64
     dwp = _zeros((3, 9, 64), x.device)
     db = _zeros((3,), x.device) if want_bias else None
-    if deterministic_enabled():
-        slab = _slab(1, B, H, W, x.device)
-        _lib.call("tup_conv3x3_thin_wgrad_det", _chk(x, BF16, None, "x"), _chk(gpl, F32, (B, 3, H, W), "gpl"), dwp.data_ptr(),
-                  None if db is None else db.data_ptr(), B, H, W, slab.data_ptr(), _stream())
-        return dwp, db
-    _lib.call("tup_conv3x3_thin_wgrad", _chk(x, BF16, None, "x"), _chk(gpl, F32, (B, 3, H, W), "gpl"), dwp.data_ptr(),
-              None if db is None else db.data_ptr(), B, H, W, _stream())
+    _reduce("tup_conv3x3_thin_wgrad", _slab(1, B, H, W, x.device), _chk(x, BF16, None, "x"), _chk(gpl, F32, (B, 3, H, W), "gpl"),
+            dwp.data_ptr(), None if db is None else db.data_ptr(), B, H, W)
     return dwp, db
 
 
@@ -843,13 +836,8 @@ def conv_planar_wgrad(x, gpl, r):
     cout = 3 * r * r
     dw = _zeros((cout, 3, 3, 3), x.device)
     db = _zeros((cout,), x.device)
-    if deterministic_enabled():
-        slab = _slab(2, B, H, W, x.device, r)
-        _lib.call("tup_conv3x3_planar_wgrad_det", _chk(x, F32, None, "x"), _chk(gpl, F32, (B, 3, H * r, W * r), "gpl"),
-                  dw.data_ptr(), db.data_ptr(), B, H, W, r, slab.data_ptr(), _stream())
-        return dw, db
-    _lib.call("tup_conv3x3_planar_wgrad", _chk(x, F32, None, "x"), _chk(gpl, F32, (B, 3, H * r, W * r), "gpl"),
-              dw.data_ptr(), db.data_ptr(), B, H, W, r, _stream())
+    _reduce("tup_conv3x3_planar_wgrad", _slab(2, B, H, W, x.device, r), _chk(x, F32, None, "x"),
+            _chk(gpl, F32, (B, 3, H * r, W * r), "gpl"), dw.data_ptr(), db.data_ptr(), B, H, W, r)
     return dw, db
 
 
@@ -860,18 +848,6 @@ def conv_planar_dgrad(gpl, w, r):
     _lib.call("tup_conv3x3_planar_dgrad", _chk(gpl, F32, None, "gpl"), _chk(w, F32, (3 * r * r, 3, 3, 3), "w"),
               gx.data_ptr(), B, H, W, r, _stream())
     return gx
-
-
-_INV_CACHE = {}
-
-
-def _inv_taps_on(device, in_size, out_size):
-    key = (str(device), in_size, out_size)
-    if key not in _INV_CACHE:
-        from .resize_taps import aa_inverse_ranges
-        o0, on = aa_inverse_ranges(in_size, out_size)
-        _INV_CACHE[key] = (torch.from_numpy(o0).to(device), torch.from_numpy(on).to(device))
-    return _INV_CACHE[key]
 
 
 def resize_aa_bwd(gout, in_hw, pre=None, l1_scale=None):
@@ -941,7 +917,7 @@ def rt_attention(qkv, B, N, save_lse=False, drop_p=0.0, drop_seed=0):
     out = torch.empty((B * N, 128), dtype=BF16, device=qkv.device)
     lse = torch.empty((B, 8, N), dtype=F32, device=qkv.device) if save_lse else None
     _lib.call("tup_rt_attention_fwd", _chk(qkv, BF16, (B * N, 384), "qkv"), out.data_ptr(),
-              None if lse is None else lse.data_ptr(), B, N, float(drop_p), int(drop_seed) & 0xFFFFFFFF, _stream())
+              None if lse is None else lse.data_ptr(), B, N, float(drop_p), _seed(drop_seed), _stream())
     return (out, lse) if save_lse else out
 
 
@@ -951,55 +927,17 @@ def rt_attention_bwd(qkv, out, gout, lse, B, N, drop_p=0.0, drop_seed=0):
     work = torch.empty((B, 8, N), dtype=F32, device=qkv.device)
     _lib.call("tup_rt_attention_bwd", _chk(qkv, BF16, (B * N, 384), "qkv"), _chk(out, BF16, (B * N, 128), "out"),
               _chk(gout, BF16, (B * N, 128), "gout"), _chk(lse, F32, (B, 8, N), "lse"), work.data_ptr(), gqkv.data_ptr(), B, N,
-              float(drop_p), int(drop_seed) & 0xFFFFFFFF, _stream())
+              float(drop_p), _seed(drop_seed), _stream())
     return gqkv
-
-
-def layernorm128(x, gamma, beta, save_stats=False):
-    M = x.shape[0]
-    y = torch.empty((M, 128), dtype=BF16, device=x.device)
-    mean = rstd = None
-    if save_stats:
-        mean = torch.empty((M,), dtype=F32, device=x.device)
-        rstd = torch.empty((M,), dtype=F32, device=x.device)
-    _lib.call("tup_layernorm128_fwd", _chk(x, F32, (M, 128), "x"), _chk(gamma, F32, (128,), "gamma"), _chk(beta, F32, (128,), "beta"),
-              y.data_ptr(), None if mean is None else mean.data_ptr(), None if rstd is None else rstd.data_ptr(), M, _stream())
-    return (y, mean, rstd) if save_stats else y
-
-
-def layernorm128_bwd(gy, x, mean, rstd, gamma, gres=None, drop=None):
-    """As layernorm_bwd for 128-wide rows."""
-    M = x.shape[0]
-    dx = torch.empty((M, 128), dtype=F32, device=x.device)
-    dg = _zeros((128,), x.device)
-    db = _zeros((128,), x.device)
-    gd = torch.empty((M, 128), dtype=BF16, device=x.device) if drop else None
-    if deterministic_enabled():
-        slab = _det_slab(wgrad_slab_floats(3, M, 128), x.device)
-        _lib.call("tup_layernorm128_bwd_det", _chk(gy, BF16, (M, 128), "gy"), _chk(x, F32, (M, 128), "x"), _chk(mean, F32, (M,), "mean"),
-                  _chk(rstd, F32, (M,), "rstd"), _chk(gamma, F32, (128,), "gamma"), _opt(gres, F32, (M, 128), "gres"),
-                  dx.data_ptr(), dg.data_ptr(), db.data_ptr(), M, gd.data_ptr() if drop else None,
-                  float(drop[0]) if drop else 0.0, (int(drop[1]) & 0xFFFFFFFF) if drop else 0, slab.data_ptr(), _stream())
-        return (dx, dg, db, gd) if drop else (dx, dg, db)
-    _lib.call("tup_layernorm128_bwd", _chk(gy, BF16, (M, 128), "gy"), _chk(x, F32, (M, 128), "x"), _chk(mean, F32, (M,), "mean"),
-              _chk(rstd, F32, (M,), "rstd"), _chk(gamma, F32, (128,), "gamma"), _opt(gres, F32, (M, 128), "gres"),
-              dx.data_ptr(), dg.data_ptr(), db.data_ptr(), M, gd.data_ptr() if drop else None,
-              float(drop[0]) if drop else 0.0, (int(drop[1]) & 0xFFFFFFFF) if drop else 0, _stream())
-    return (dx, dg, db, gd) if drop else (dx, dg, db)
 
 
 def rt_patch_wgrad(p, fmap):
     """fp32 [128][4096] = p^T patches(fmap); p fp32 [B*T][128] (plain token grid), fmap NHWC bf16."""
     B, H, W, C = fmap.shape
+    M = B * (H // 8) * (W // 8)
     out = _zeros((128, 4096), p.device)
-    if deterministic_enabled():
-        M = B * (H // 8) * (W // 8)
-        slab = _det_slab(wgrad_slab_floats(0, M, 128, 4096), p.device)
-        _lib.call("tup_rt_patch_wgrad_det", _chk(p, F32, (M, 128), "p"), _chk(fmap, BF16, None, "map"),
-                  out.data_ptr(), B, H, W, slab.data_ptr(), _stream())
-        return out
-    _lib.call("tup_rt_patch_wgrad", _chk(p, F32, (B * (H // 8) * (W // 8), 128), "p"), _chk(fmap, BF16, None, "map"),
-              out.data_ptr(), B, H, W, _stream())
+    _reduce("tup_rt_patch_wgrad", _det_slab(0, M, 128, 4096, p.device), _chk(p, F32, (M, 128), "p"), _chk(fmap, BF16, None, "map"),
+            out.data_ptr(), B, H, W)
     return out
 
 
@@ -1028,101 +966,14 @@ def conv_c64_wgrad_s2d(x, gmap, xr):
     assert tuple(x.shape) == (B, H * xr, W * xr, 64)
     dwp = _zeros((xr * xr, 64, 9, 64), x.device)
     db = _zeros((64,), x.device)
-    if deterministic_enabled():
-        slab = _slab(0, B, H, W, x.device)
-        for sp in range(xr * xr):
-            _lib.call("tup_conv3x3_c64_wgrad_s2d_det", _chk(x, BF16, None, "x"), _chk(gmap, BF16, None, "gmap"), dwp[sp].data_ptr(),
-                      db.data_ptr() if sp == 0 else None, B, H, W, xr, sp, slab.data_ptr(), _stream())
-        return dwp, db
+    slab = _slab(0, B, H, W, x.device)
     for sp in range(xr * xr):
-        _lib.call("tup_conv3x3_c64_wgrad_s2d", _chk(x, BF16, None, "x"), _chk(gmap, BF16, None, "gmap"), dwp[sp].data_ptr(),
-                  db.data_ptr() if sp == 0 else None, B, H, W, xr, sp, _stream())
+        _reduce("tup_conv3x3_c64_wgrad_s2d", slab, _chk(x, BF16, None, "x"), _chk(gmap, BF16, None, "gmap"), dwp[sp].data_ptr(),
+                db.data_ptr() if sp == 0 else None, B, H, W, xr, sp)
     return dwp, db
 
 
-_BIC_CACHE = {}
-
-
-def _bicubic_on(device, in_size, out_size):
-    key = (str(device), in_size, out_size)
-    if key not in _BIC_CACHE:
-        from .resize_taps import bicubic_taps
-        idx, w = bicubic_taps(in_size, out_size)
-        _BIC_CACHE[key] = (torch.from_numpy(idx).to(device), torch.from_numpy(w).to(device))
-    return _BIC_CACHE[key]
-
-
-_BICT_CACHE = {}
-
-
-def _bicubic_t_on(device, in_size, out_size):
-    key = (str(device), in_size, out_size)
-    if key not in _BICT_CACHE:
-        from .resize_taps import bicubic_taps, transpose_taps
-        idx, w = bicubic_taps(in_size, out_size)
-        _BICT_CACHE[key] = tuple(torch.from_numpy(t).to(device) for t in transpose_taps(idx, w, in_size))
-    return _BICT_CACHE[key]
-
-
-_BICB_CACHE = {}
-_BIC_YB = 16
 bicubic_bwd_banded = True        # A/B attribute: per-source-row gather of the row pass
-
-
-def _bicubic_bands_on(device, in_size, out_size):
-    """Band tables of the row pass of rt_bicubic_bwd: for source rows 16b .. 16b+15 the contiguous range of output rows that touch
-    them and the dense weights [rows][16] (transpose of the forward tap matrix)."""
-    key = (str(device), in_size, out_size)
-    if key not in _BICB_CACHE:
-        import numpy as np
-        from .resize_taps import bicubic_taps
-        idx, w = bicubic_taps(in_size, out_size)             # [out][4]
-        nb = (in_size + _BIC_YB - 1) // _BIC_YB
-        lo = np.full(in_size, out_size, dtype=np.int64); hi = np.full(in_size, -1, dtype=np.int64)
-        for k in range(4):
-            np.minimum.at(lo, idx[:, k], np.arange(out_size)); np.maximum.at(hi, idx[:, k], np.arange(out_size))
-        r0 = np.array([lo[b * _BIC_YB:(b + 1) * _BIC_YB].min() for b in range(nb)], dtype=np.int64)
-        r1 = np.array([hi[b * _BIC_YB:(b + 1) * _BIC_YB].max() for b in range(nb)], dtype=np.int64)
-        n = (r1 - r0 + 1).clip(min=1)
-        r0 = np.minimum(r0, out_size - 1)
-        nr_max = int(n.max())
-        bw = np.zeros((nb, nr_max, _BIC_YB), dtype=np.float32)
-        rows = np.arange(out_size)
-        for k in range(4):
-            y = idx[:, k]; b = y // _BIC_YB
-            np.add.at(bw, (b, rows - r0[b], y - b * _BIC_YB), w[:, k].astype(np.float32))
-        _BICB_CACHE[key] = (torch.from_numpy(r0.astype(np.int32)).to(device), torch.from_numpy(n.astype(np.int32)).to(device),
-                            torch.from_numpy(bw).to(device), nr_max)
-    return _BICB_CACHE[key]
-
-
-_BICC_CACHE = {}
-
-
-def _bicubic_cols_on(device, in_size, out_size):
-    """Dense column tables of rt_bicubic_bwd: (xoT int32 [kmax][in], xwT fp32 [kmax][in], kmax, blk_c0, blk_n) from the transposed
-    tap lists; None when a 256-column block's stretch exceeds the kernel's LDS tile (very large ratios)."""
-    key = (str(device), in_size, out_size)
-    if key not in _BICC_CACHE:
-        import numpy as np
-        from .resize_taps import bicubic_taps, transpose_taps
-        idx, w = bicubic_taps(in_size, out_size)
-        xs, xo, xw = transpose_taps(idx, w, in_size)
-        cnt = np.diff(xs)
-        kmax = int(cnt.max())
-        xoT = np.zeros((kmax, in_size), dtype=np.int32); xwT = np.zeros((kmax, in_size), dtype=np.float32)
-        for x in range(in_size):
-            n = cnt[x]
-            xoT[:n, x] = xo[xs[x]:xs[x] + n]; xwT[:n, x] = xw[xs[x]:xs[x] + n]
-            xoT[n:, x] = xo[xs[x]]                                  # padding: in-range index, weight 0
-        nblk = (in_size + 255) // 256
-        c0 = np.array([xoT[:, j * 256:(j + 1) * 256].min() for j in range(nblk)], dtype=np.int32)
-        c1 = np.array([xoT[:, j * 256:(j + 1) * 256].max() for j in range(nblk)], dtype=np.int32)
-        nn = c1 - c0 + 1
-        _BICC_CACHE[key] = None if int(nn.max()) > 4096 else (
-            torch.from_numpy(xoT).to(device), torch.from_numpy(xwT).to(device), kmax, torch.from_numpy(c0).to(device),
-            torch.from_numpy(nn.astype(np.int32)).to(device))
-    return _BICC_CACHE[key]
 
 
 def rt_bicubic_bwd(gout, out, in_hw, l1_scale=None):
@@ -1131,11 +982,13 @@ def rt_bicubic_bwd(gout, out, in_hw, l1_scale=None):
     and the upstream gradient sign(out - target) * l1_scale is formed inside the kernel."""
     B, C, Ho, Wo = gout.shape
     Ha, Wa = in_hw
-    ga = torch.empty((B, C, Ha, Wa), dtype=F32, device=gout.device)
-    tmp = torch.empty((B, C, Ha, Wo), dtype=F32, device=gout.device)
-    cols = _bicubic_cols_on(gout.device, Wa, Wo) if bicubic_bwd_banded else None
+    dev = gout.device
+    ga = torch.empty((B, C, Ha, Wa), dtype=F32, device=dev)
+    tmp = torch.empty((B, C, Ha, Wo), dtype=F32, device=dev)
+    # (no column tables: a 256-column block's stretch exceeds the kernel's LDS tile)
+    cols = _table(resize_taps.bicubic_cols, dev, (Wa, Wo)) if bicubic_bwd_banded else None
     if cols is not None:
-        r0, bn, bw, nr_max = _bicubic_bands_on(gout.device, Ha, Ho)
+        r0, bn, bw, nr_max = _table(resize_taps.bicubic_bands, dev, (Ha, Ho))
         xoT, xwT, kmax, c0, cn = cols
         _lib.call("tup_rt_bicubic_bwd_banded", _chk(gout, F32, None, "gout"), _opt(out, F32, (B, C, Ho, Wo), "out"), ga.data_ptr(),
                   tmp.data_ptr(), r0.data_ptr(), bn.data_ptr(), bw.data_ptr(), nr_max, xoT.data_ptr(), xwT.data_ptr(), kmax,
@@ -1144,8 +997,8 @@ def rt_bicubic_bwd(gout, out, in_hw, l1_scale=None):
         return ga
     if l1_scale is not None:
         raise RuntimeError("the fused L1 form of rt_bicubic_bwd needs the banded kernels (ratio too large or TUP_BICUBIC_BWD_GATHER set)")
-    xs, xo, xw = _bicubic_t_on(gout.device, Wa, Wo)
-    ys, yo, yw = _bicubic_t_on(gout.device, Ha, Ho)
+    xs, xo, xw = _table(resize_taps.bicubic_taps_transposed, dev, (Wa, Wo))
+    ys, yo, yw = _table(resize_taps.bicubic_taps_transposed, dev, (Ha, Ho))
     _lib.call("tup_rt_bicubic_bwd", _chk(gout, F32, None, "gout"), _opt(out, F32, (B, C, Ho, Wo), "out"), ga.data_ptr(), tmp.data_ptr(),
               ys.data_ptr(), yo.data_ptr(), yw.data_ptr(), xs.data_ptr(), xo.data_ptr(), xw.data_ptr(), B * C, Ha, Wa, Ho, Wo, _stream())
     return ga
@@ -1221,18 +1074,6 @@ def bra_backward(g, ui, feat, comp, wu, bu, w3):
     _lib.call("tup_bra_chain", G.data_ptr(), Gb.data_ptr(), _chk(wu, F32, (256, 64, 3, 3), "wu"), _chk(bu, F32, (256,), "bu"),
               _chk(w3, F32, (3, 64, 3, 3), "w3"), dM.data_ptr(), dMb.data_ptr(), dwu.data_ptr(), dbu.data_ptr(), dw3.data_ptr(), _stream())
     return dfeat, dwu, dbu, dw3, G, Gb
-
-
-_PIL_TAPS = {}
-
-
-def _pil_taps_on(device, in_size, out_size):
-    from .resize_taps import pil_bilinear_coeffs
-    key = (str(device), in_size, out_size)
-    if key not in _PIL_TAPS:
-        lo, n, k, ks = pil_bilinear_coeffs(in_size, out_size)
-        _PIL_TAPS[key] = (torch.from_numpy(lo).to(device), torch.from_numpy(n).to(device), torch.from_numpy(k).to(device), ks)
-    return _PIL_TAPS[key]
 
 
 def resize_frames(frames_u8, size, to_tensor=False, bgr=False):
@@ -1356,28 +1197,17 @@ def patch_pairs(frames, boxes, p, scale, out=None):
     return lr, hr
 
 
-# ---- WindowTransformer: window block at width 128 / 8 heads ----
-def relpos_bias_expand_h(table, heads):
-    frag = torch.empty((heads, 4, 4, 64, 4), dtype=F32, device=table.device)
-    _lib.call("tup_relpos_bias_expand_h", _chk(table, F32, (225, heads), "table"), frag.data_ptr(), heads, _stream())
-    return frag
-
-
-def window_attn_h(qkv, bias_frag, heads, drop_p=0.0, drop_seed=0, save_lse=False):
-    M, D = qkv.shape
-    assert D == 48 * heads and M % 64 == 0
-    out = torch.empty((M, 16 * heads), dtype=BF16, device=qkv.device)
-    lse = torch.empty((M // 64, heads, 64), dtype=F32, device=qkv.device) if save_lse else None
-    _lib.call("tup_window_attn_fwd_h", _chk(qkv, BF16, None, "qkv"), _chk(bias_frag, F32, (heads, 4, 4, 64, 4), "bias"),
-              out.data_ptr(), lse.data_ptr() if save_lse else None, M // 64, heads, float(drop_p), int(drop_seed) & 0xFFFFFFFF, _stream())
-    return (out, lse) if save_lse else out
+# ---- WindowTransformer: the patch GEMMs in window layout, without reflect padding ----
+def _wt_windows(H, W):
+    """Windows down and across the floor(H/8) x floor(W/8) token grid."""
+    return (H // 8 + 7) // 8, (W // 8 + 7) // 8
 
 
 def wt_patch_embed(feat, wt, bias):
     """Stride-8 patch conv without padding (floor(H/8) x floor(W/8) tokens) -> fp32 window-layout tokens [M][N]."""
     B, H, W, C = feat.shape
     N = wt.shape[0]
-    nwy, nwx = (H // 8 + 7) // 8, (W // 8 + 7) // 8
+    nwy, nwx = _wt_windows(H, W)
     x = torch.empty((B * nwy * nwx * 64, N), dtype=F32, device=feat.device)
     _lib.call("tup_wt_patch_embed_fwd", _chk(feat, BF16, None, "feat"), _chk(wt, BF16, (N, 4096), "wt"), _chk(bias, F32, (N,), "bias"),
               x.data_ptr(), B, H, W, N, _stream())
@@ -1388,7 +1218,7 @@ def wt_patch_unembed(x, wt, bias, skip):
     """skip + ConvTranspose(k8, s8)(window_reverse(x)): skip / result NHWC bf16 [B][Ht*8][Wt*8][64]."""
     B, Hs, Ws, C = skip.shape
     K = wt.shape[1]
-    nwy, nwx = (Hs // 8 + 7) // 8, (Ws // 8 + 7) // 8
+    nwy, nwx = _wt_windows(Hs, Ws)
     out = torch.empty_like(skip)
     _lib.call("tup_wt_patch_unembed_fwd", _chk(x, F32, (B * nwy * nwx * 64, K), "x"), _chk(wt, BF16, (4096, K), "wt"),
               _chk(bias, F32, (64,), "bias"), _chk(skip, BF16, None, "skip"), out.data_ptr(), B, Hs, Ws, K, _stream())
@@ -1410,40 +1240,15 @@ def l1_loss_bwd(a, b, gout):
     return ga
 
 
-def relpos_bias_expand_n_h(table, heads):
-    frag = torch.empty((heads, 4, 4, 64, 4), dtype=F32, device=table.device)
-    _lib.call("tup_relpos_bias_expand_n_h", _chk(table, F32, (225, heads), "table"), frag.data_ptr(), heads, _stream())
-    return frag
-
-
-def window_attn_bwd_h(qkv, gout, att, lse, bias_n, heads, drop_p=0.0, drop_seed=0):
-    """returns (gqkv bf16 [M][48*heads], dtable fp32 [225][heads])."""
-    M = qkv.shape[0]
-    assert M % 64 == 0
-    gqkv = torch.empty((M, 48 * heads), dtype=BF16, device=qkv.device)
-    dbias = torch.empty((heads, 4, 4, 64, 4), dtype=F32, device=qkv.device)
-    scratch = torch.empty(_attn_bwd_scratch(M // 64, heads), dtype=F32, device=qkv.device)
-    _lib.call("tup_window_attn_bwd_h", _chk(qkv, BF16, (M, 48 * heads), "qkv"), _chk(gout, BF16, (M, 16 * heads), "gout"),
-              _chk(att, BF16, (M, 16 * heads), "att"), _chk(lse, F32, (M // 64, heads, 64), "lse"),
-              _chk(bias_n, F32, (heads, 4, 4, 64, 4), "bias_n"),
-              gqkv.data_ptr(), dbias.data_ptr(), scratch.data_ptr(), M // 64, heads, float(drop_p), int(drop_seed) & 0xFFFFFFFF, _stream())
-    dtable = torch.empty((225, heads), dtype=F32, device=qkv.device)
-    _lib.call("tup_relpos_bias_reduce_h", dbias.data_ptr(), dtable.data_ptr(), heads, _stream())
-    return gqkv, dtable
-
-
 def wt_patch_wgrad(p, fmap):
     """fp32 [NI][4096] = p^T patches(fmap); p fp32 window-layout tokens [M][NI] over the floor(H/8) x floor(W/8) grid."""
     B, H, W, C = fmap.shape
     NI = p.shape[1]
+    nwy, nwx = _wt_windows(H, W)
+    M = B * nwy * nwx * 64
     out = _zeros((NI, 4096), p.device)
-    if deterministic_enabled():
-        M = B * ((H // 8 + 7) // 8) * ((W // 8 + 7) // 8) * 64
-        slab = _det_slab(wgrad_slab_floats(0, M, NI, 4096), p.device)
-        _lib.call("tup_wt_patch_wgrad_det", _chk(p, F32, (M, NI), "p"), _chk(fmap, BF16, None, "map"), out.data_ptr(), B, H, W, NI,
-                  slab.data_ptr(), _stream())
-        return out
-    _lib.call("tup_wt_patch_wgrad", _chk(p, F32, None, "p"), _chk(fmap, BF16, None, "map"), out.data_ptr(), B, H, W, NI, _stream())
+    _reduce("tup_wt_patch_wgrad", _det_slab(0, M, NI, 4096, p.device), _chk(p, F32, (M, NI), "p"), _chk(fmap, BF16, None, "map"),
+            out.data_ptr(), B, H, W, NI)
     return out
 
 
@@ -1451,7 +1256,7 @@ def wt_patch_unembed_bwd(gmap, wd):
     """d tokens (window layout, fp32 [M][N]) of the WindowTransformer patch_unembed: the patch_embed GEMM with W^T, no bias."""
     B, H, W, C = gmap.shape
     N = wd.shape[0]
-    nwy, nwx = (H // 8 + 7) // 8, (W // 8 + 7) // 8
+    nwy, nwx = _wt_windows(H, W)
     x = torch.empty((B * nwy * nwx * 64, N), dtype=F32, device=gmap.device)
     _lib.call("tup_wt_patch_embed_fwd", _chk(gmap, BF16, None, "gmap"), _chk(wd, BF16, (N, 4096), "wd"), None,
               x.data_ptr(), B, H, W, N, _stream())

@@ -139,3 +139,93 @@ def pil_bilinear_coeffs(in_size: int, out_size: int):
         lo[i], n[i] = a, b - a
     ki = np.where(kk < 0, np.trunc(-0.5 + kk * (1 << PIL_PRECISION_BITS)), np.trunc(0.5 + kk * (1 << PIL_PRECISION_BITS)))
     return lo, n, np.ascontiguousarray(ki.astype(np.int32)), ksize
+
+
+def tail_fused_tables(in_h: int, in_w: int, out_h: int, out_w: int, tile_h: int, tile_w: int):
+    """Row and column tables of the tiled fused tail (csrc/tail_fused.hip) and the input extent of its output tiles."""
+    return taps_or_identity(in_h, out_h) + taps_or_identity(in_w, out_w) + (tile_extent(in_h, out_h, tile_h), tile_extent(in_w, out_w, tile_w))
+
+
+def tail_stream_plan(B: int, H: int, W: int, Ho: int, Wo: int, workgroups: int):
+    """Decomposition of the fused streaming tail + Resize (csrc/tail_stream.hip, RESIZE = true) of B LR maps H x W to Ho x Wo:
+    (ylo, yn, yw, ky, xlo, xn, xw, kx, oxb, oyb, strip stride, band height, band extension) with oxb / oyb the output columns /
+    rows each strip / band owns.  `workgroups` fills the chip once at the kernel's occupancy.  None when a tap table has more
+    than 4 taps or an owned output reads beyond what its strip / band computes (then the Resize runs as its own kernel)."""
+    ylo, yn, yw, ky = aa_taps(2 * H, Ho)
+    xlo, xn, xw, kx = aa_taps(2 * W, Wo)
+    if int(yn.max()) > 4 or int(xn.max()) > 4:
+        return None
+    sc = 60 - (int(xn.max()) - 1 + 1) // 2
+    ext = (int(yn.max()) - 1 + 1) // 2
+    nstrip = (W + sc - 1) // sc
+    nb = max(1, workgroups // max(1, B * nstrip))
+    bh = max(12, ((H + nb - 1) // nb + 2) // 3 * 3)
+    nband = (H + bh - 1) // bh
+    oxb = np.searchsorted(xlo, 2 * sc * np.arange(nstrip + 1), side="left").astype(np.int32)
+    oyb = np.searchsorted(ylo, 2 * bh * np.arange(nband + 1), side="left").astype(np.int32)
+    oxb[-1], oyb[-1] = Wo, Ho
+    for s in range(nstrip):           # every owned column's taps inside the strip's 120 valid HR columns, <= 128 gathered
+        a, b = int(oxb[s]), int(oxb[s + 1])
+        if b > a and ((xlo[a:b] + xn[a:b]).max() > 2 * s * sc + 120 or b - a > 128):
+            return None
+    for k in range(nband):            # every owned row's taps inside the rows the band computes
+        a, b = int(oyb[k]), int(oyb[k + 1])
+        if b > a and (ylo[a:b] + yn[a:b]).max() > 2 * min(H, (k + 1) * bh + ext):
+            return None
+    return ylo, yn, yw, ky, xlo, xn, xw, kx, oxb, oyb, sc, bh, ext
+
+
+def bicubic_taps_transposed(in_size: int, out_size: int):
+    """transpose_taps of bicubic_taps: the per-source lists of the gather-form bicubic backward."""
+    idx, w = bicubic_taps(in_size, out_size)
+    return transpose_taps(idx, w, in_size)
+
+
+BICUBIC_BAND_ROWS = 16
+
+
+def bicubic_bands(in_size: int, out_size: int):
+    """Band tables of the row pass of the banded bicubic backward: for source rows 16b .. 16b+15 the contiguous range of output
+    rows that touch them (first int32 [bands], count int32 [bands]) and the dense weights fp32 [bands][rows][16] (transpose of the
+    forward tap matrix), rows = the largest count."""
+    yb = BICUBIC_BAND_ROWS
+    idx, w = bicubic_taps(in_size, out_size)             # [out][4]
+    nb = (in_size + yb - 1) // yb
+    lo = np.full(in_size, out_size, dtype=np.int64)
+    hi = np.full(in_size, -1, dtype=np.int64)
+    rows = np.arange(out_size)
+    for k in range(4):
+        np.minimum.at(lo, idx[:, k], rows)
+        np.maximum.at(hi, idx[:, k], rows)
+    r0 = np.array([lo[b * yb:(b + 1) * yb].min() for b in range(nb)], dtype=np.int64)
+    r1 = np.array([hi[b * yb:(b + 1) * yb].max() for b in range(nb)], dtype=np.int64)
+    n = (r1 - r0 + 1).clip(min=1)
+    r0 = np.minimum(r0, out_size - 1)
+    nr_max = int(n.max())
+    bw = np.zeros((nb, nr_max, yb), dtype=np.float32)
+    for k in range(4):
+        y = idx[:, k]
+        b = y // yb
+        np.add.at(bw, (b, rows - r0[b], y - b * yb), w[:, k].astype(np.float32))
+    return r0.astype(np.int32), n.astype(np.int32), bw, nr_max
+
+
+def bicubic_cols(in_size: int, out_size: int):
+    """Dense column tables of the banded bicubic backward: (xoT int32 [kmax][in], xwT fp32 [kmax][in], kmax, and per 256-column
+    block the first output column int32 [blocks] and the count int32 [blocks] it reads) from the transposed tap lists; None when
+    a block's stretch exceeds the kernel's LDS tile of 4096 columns (very large ratios)."""
+    xs, xo, xw = bicubic_taps_transposed(in_size, out_size)
+    cnt = np.diff(xs)
+    kmax = int(cnt.max())
+    xoT = np.zeros((kmax, in_size), dtype=np.int32)
+    xwT = np.zeros((kmax, in_size), dtype=np.float32)
+    for x in range(in_size):
+        n = cnt[x]
+        xoT[:n, x] = xo[xs[x]:xs[x] + n]
+        xwT[:n, x] = xw[xs[x]:xs[x] + n]
+        xoT[n:, x] = xo[xs[x]]                                  # padding: in-range index, weight 0
+    nblk = (in_size + 255) // 256
+    c0 = np.array([xoT[:, j * 256:(j + 1) * 256].min() for j in range(nblk)], dtype=np.int32)
+    c1 = np.array([xoT[:, j * 256:(j + 1) * 256].max() for j in range(nblk)], dtype=np.int32)
+    nn = (c1 - c0 + 1).astype(np.int32)
+    return None if int(nn.max()) > 4096 else (xoT, xwT, kmax, c0, nn)

@@ -72,10 +72,10 @@ class TransformerModel(nn.Module):
                 pk = packed_with_plan(self, "wt", sd, lambda d: packing.pack_wt_state_dict(d, backward=True))
             if pk is None:
                 pk = packing.pack_wt_state_dict(sd, backward=backward)
-            frags = [ops.relpos_bias_expand_h(pk[f"b{i}.table"], self.num_heads) for i in range(pk["nblocks"])]
+            frags = [ops.relpos_bias_expand(pk[f"b{i}.table"]) for i in range(pk["nblocks"])]
             entry = (ver, pk, frags)
             if backward:
-                entry += ([ops.relpos_bias_expand_n_h(pk[f"b{i}.table"], self.num_heads) for i in range(pk["nblocks"])],)
+                entry += ([ops.relpos_bias_expand_n(pk[f"b{i}.table"]) for i in range(pk["nblocks"])],)
             self._pack_cache[bool(backward)] = hit = entry
         return hit[1:]
 
@@ -97,7 +97,7 @@ class TransformerModel(nn.Module):
             from .autograd_wt import forward_train
             pk, frags_t, _ = self.packed(backward=True)
             drop_p, seed = self._next_dropout()
-            out, _ = forward_train(pk, frags_t, self.num_heads, x, tuple(int(v) for v in res_out), drop_p, seed)
+            out, _ = forward_train(pk, frags_t, x, tuple(int(v) for v in res_out), drop_p, seed)
             return out.to(torch.get_autocast_gpu_dtype()) if torch.is_autocast_enabled() else out
         pk, frags = self.packed()
         x = x.contiguous().float()
@@ -105,8 +105,7 @@ class TransformerModel(nn.Module):
         feat_down = ops.conv_c64(pad_to_even(feat), pk["ds.w"], pk["ds.b"], 1, relu=False, in_r=2)        # model.py:244
         del feat
         xw = ops.wt_patch_embed(feat_down, pk["pe.w"], pk["pe.b"])                          # model.py:247-268
-        heads = self.num_heads
-        blocks_infer(pk, xw, ("qkv", "proj"), lambda i, qkv: ops.window_attn_h(qkv, frags[i], heads))
+        blocks_infer(pk, xw, ("qkv", "proj"), lambda i, qkv: ops.window_attn(qkv, frags[i]))
         hs, ws = (hd // 8) * 8, (wd // 8) * 8                                               # crop for the skip, model.py:284-288
         skip = feat_down if (hs, ws) == (hd, wd) else feat_down[:, :hs, :ws, :].contiguous()
         comb = ops.wt_patch_unembed(xw, pk["pu.w"], pk["pu.b"], skip)
