@@ -219,23 +219,41 @@ TUP_DEVICE int variant_of(int Y, int X, int Hs, int Ws) {
     return ((Y == 0) ? 1 : (Y == Hs - 1 ? 2 : 0)) * 3 + ((X == 0) ? 1 : (X == Ws - 1 ? 2 : 0));
 }
 
-// ---- input gradient, ring part: the LR pixels within 2 of the image border receive, on top of the main kernel's result, the
-// contributions of the HR ring pixels through their weight variants.  One wave per LR frame pixel, lane = channel. ----
+// ---- input gradient, ring part: the LR pixels within 2 of the image border receive, besides the main kernel's sum, the
+// contributions of the HR ring pixels through their weight variants.  One wave per LR frame pixel, lane = channel.  The frame
+// pixel's main sum (g12 against the interior variant, what bra_dgrad_kernel stored there as bf16) is formed again here in fp32, so
+// that the pixel is rounded to bf16 ONCE: adding the ring share to the stored bf16 value rounded it twice. ----
 __global__ __launch_bounds__(256) void bra_dgrad_ring_kernel(const float* __restrict__ g, const float* __restrict__ ui,
-                                                             const bf16_t* __restrict__ wv, bf16_t* __restrict__ out, int B, int H, int W)
+                                                             const bf16_t* __restrict__ g12, const bf16_t* __restrict__ wv,
+                                                             bf16_t* __restrict__ out, int B, int H, int W)
 {
     const int lane = threadIdx.x & 63;
     const int Hs = 2 * H, Ws = 2 * W;
     // frame pixels: rows 0..2 and H-3..H-1 in full, then columns 0..2 and W-3..W-1 of the remaining rows (H, W >= 6 assumed by the host)
     const int nrow = 6 * W, ncol = 6 * (H - 6), per_img = nrow + ncol;
-    const long long gid = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    // the wave index as a scalar: the frame pixel, its neighbours and their g / g12 values are then wave-uniform for the compiler too
+    // (scalar address arithmetic and scalar loads; only the weight loads and the sums are per lane)
+    const long long gid = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (gid >= (long long)per_img * B) return;
     const int b = (int)(gid / per_img);
     int k = (int)(gid - (long long)b * per_img);
     int fy, fx;
     if (k < nrow) { const int rr = k / W; fy = rr < 3 ? rr : H - 6 + rr; fx = k - rr * W; }
     else { k -= nrow; const int rr = k / 6, cc = k - rr * 6; fy = 3 + rr; fx = cc < 3 ? cc : W - 6 + cc; }
-    float acc = 0.f;
+    float acc = 0.f, mainv = 0.f;
+    for (int ly = max(fy - 2, 0); ly <= min(fy + 2, H - 1); ++ly)
+        for (int lx = max(fx - 2, 0); lx <= min(fx + 2, W - 1); ++lx) {
+            const int tap = (fy - ly + 2) * 5 + (fx - lx + 2);
+            const u32x4* gp = reinterpret_cast<const u32x4*>(g12 + (((size_t)b * H + ly) * W + lx) * 16);      // wave-uniform
+            const u32x4 lo = gp[0], hi = gp[1];
+            const uint32_t w6[6] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1]};                                 // n = 0..11 (ring already zero)
+            if ((w6[0] | w6[1] | w6[2] | w6[3] | w6[4] | w6[5]) == 0u) continue;
+#pragma unroll
+            for (int n = 0; n < NOUT; ++n) {
+                const float gv = __builtin_bit_cast(float, (n & 1) ? (w6[n >> 1] & 0xffff0000u) : (w6[n >> 1] << 16));
+                mainv = fmaf(gv, bf16_to_f32(wv[((size_t)n * NTAP + tap) * 64 + lane]), mainv);                  // variant 0
+            }
+        }
     for (int ly = max(fy - 2, 0); ly <= min(fy + 2, H - 1); ++ly) {
         if (ly != 0 && ly != H - 1 && fx - 2 > 0 && fx + 2 < W - 1) continue;         // no ring pixel in this LR row within reach
         for (int lx = max(fx - 2, 0); lx <= min(fx + 2, W - 1); ++lx) {
@@ -255,7 +273,7 @@ __global__ __launch_bounds__(256) void bra_dgrad_ring_kernel(const float* __rest
         }
     }
     bf16_t* o = out + (((size_t)b * H + fy) * W + fx) * 64 + lane;
-    *o = f32_to_bf16(bf16_to_f32(*o) + acc);
+    *o = f32_to_bf16(mainv + acc);
 }
 
 // ---- weight gradient, main part: G0[n][t][ci] += sum_px g12[px][n] feat[px + (ty-2, tx-2)][ci] (ring pixels are zero in g12).
@@ -607,7 +625,7 @@ extern "C" int tup_bra_backward(const float* g, const float* ui, const void* fea
                                                                              B, H, W, tilesX, tilesY);
     TUP_CHECK_LAUNCH();
     const long long nframe = (long long)B * (6LL * W + 6LL * (H - 6));
-    bra_dgrad_ring_kernel<<<dim3((unsigned)((nframe + 3) / 4)), dim3(256), 0, s>>>(g, ui, (const bf16_t*)wv, (bf16_t*)dfeat, B, H, W);
+    bra_dgrad_ring_kernel<<<dim3((unsigned)((nframe + 3) / 4)), dim3(256), 0, s>>>(g, ui, (const bf16_t*)g12, (const bf16_t*)wv, (bf16_t*)dfeat, B, H, W);
     TUP_CHECK_LAUNCH();
     TUP_SET_DYN_LDS((bra_wgrad_kernel), WGRAD_LDS);
     bra_wgrad_kernel<<<dim3((unsigned)(nt < 256 ? nt : 256)), dim3(512), WGRAD_LDS, s>>>((const bf16_t*)feat, (const bf16_t*)g12, G, B, H, W, tilesX, tilesY);

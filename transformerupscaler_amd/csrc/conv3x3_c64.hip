@@ -407,8 +407,11 @@ __global__ __launch_bounds__(512, 2) void conv_c64_persistent_kernel(
             for (int m = 0; m < NM; ++m) {
                 if (step + 2 < NSTEPS) {
 #pragma unroll
+                    // request j goes out before MFMA m = floor(j NM / PER): every one of the PER requests is issued also when
+                    // the step has fewer MFMAs than requests (CT = 1: NM = 4, PER = 5; "j NM <= m PER" never issued the weight
+                    // fragment there); for CT = 4 (NM = 16, PER = 8) this is the same schedule, j = m / 2
                     for (int j = 0; j < PER; ++j)
-                        if (j == rd && j * NM <= m * PER) { load_one(step + 2, (step + 2) % 3, j); ++rd; }
+                        if (j == rd && j * NM < (m + 1) * PER) { load_one(step + 2, (step + 2) % 3, j); ++rd; }
                 }
                 const int pg = m / CT, ct = m % CT;
                 acc[pg][ct] = mfma16x16x32(wf[cur][ct], pf[cur][pg], acc[pg][ct]);
