@@ -35,6 +35,7 @@ SIGNATURES = {
     "tup_tail_stream_r2_resize_fwd": [P] * 7 + [P, P, P, I, P, P, P, I, P, P] + [I] * 9 + [P],
     "tup_tail_stream_r2_parts_fwd": [P, P, P, P, I] + [P] * 6 + [I, I, I, I, P],
     "tup_tail_stream_r2_resize_parts_fwd": [P, P, P, P, I] + [P] * 6 + [P, P, P, I, P, P, P, I, P, P] + [I] * 9 + [P],
+    "tup_tail_stream_weight_source": [I],
     "tup_clamp01_fwd": [P, P, c_longlong, P],
     "tup_layernorm_fwd": [P, P, P, P, P, P, I, P],
     "tup_relpos_bias_expand": [P, P, P],

@@ -259,7 +259,7 @@ def tail_fused(x, wfu, bfu, wfc, bfc, ui, r, out_hw, clamp=True):
     return out
 
 
-TAIL_STREAM_WAVES_PER_SIMD = 3      # csrc/tail_stream.hip: 150 registers (152 on unfinished decoder pieces), 52 KB of LDS per four-wave workgroup
+TAIL_STREAM_WAVES_PER_SIMD = 3      # csrc/tail_stream.hip: 127 registers (148 on unfinished decoder pieces), 51 KB of LDS per four-wave workgroup
 
 
 def _tail_stream_plan(device, B, H, W, Ho, Wo):
@@ -312,6 +312,16 @@ def tail_stream_r2(x, wfu_t, bfu, wfc_t, bfc, ui, clamp=True, out_hw=None, parts
               xlo.data_ptr(), xn.data_ptr(), xw.data_ptr(), kx, oxb.data_ptr(), oyb.data_ptr(), B, H, W, Ho, Wo, sc, bh, ext,
               int(clamp), _stream())
     return out
+
+
+TAIL_STREAM_WEIGHT_SOURCES = ("scalar", "lds")
+
+
+def tail_stream_weight_source(source):
+    """Which arm of the streaming tail (csrc/tail_stream.hip) tail_stream_r2 launches from now on, process-wide: "scalar" = the weights
+    as scalar operands of the packed FMAs (the default), "lds" = the LDS image and vector-register ring.  Both give the same bits; the
+    switch exists for same-box A/B runs and the equality tests."""
+    _lib.call("tup_tail_stream_weight_source", TAIL_STREAM_WEIGHT_SOURCES.index(source))
 
 
 def clamp01(x):
