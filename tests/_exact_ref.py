@@ -507,6 +507,8 @@ def all_cases():
     for sh in SCHEDULES:
         t[f"c64-r1-{sid(sh)}"] = lambda sh=sh: c64_case(sh, 1, want=("addmask",))
         t[f"c64-r2-{sid(sh)}"] = lambda sh=sh: c64_case(sh, 2, want=("plain",))
+        t[f"conv12-{sid(sh)}"] = lambda sh=sh: conv12_case(sh)           # conv12_fused_kernel and decoder_fused_kernel walk the
+        t[f"decoder-{sid(sh)}"] = lambda sh=sh: decoder_case(sh)         # same two-group schedule (csrc/conv_pingpong.h)
     for sh, co in THIN_SCHEDULES:
         t[f"thin{co}-{sid(sh)}"] = lambda sh=sh, co=co: thin_case(sh, co)
     rs = sid(ROUNDING_SHAPE)

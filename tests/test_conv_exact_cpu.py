@@ -47,7 +47,7 @@ def test_case_tables_cover_what_the_issue_lists():
         assert {f"bra-r{r}-{R._sid(sh)}" for r in (2, 3, 6)} <= names
     for sh in R.SCHEDULES:
         s = R._sid(sh)
-        assert {f"c64-r1-{s}", f"c64-r2-{s}", f"thin3-{s}", f"thin16-{s}", f"bra-r2-{s}"} <= names
+        assert {f"c64-r1-{s}", f"c64-r2-{s}", f"thin3-{s}", f"thin16-{s}", f"bra-r2-{s}", f"conv12-{s}", f"decoder-{s}"} <= names
     assert "decoder-3x117x440" in names
     assert sum(n.endswith("-rounding") for n in names) == 6
     # tile counts the schedule comments promise (8 x 32 tiles; grid = min(tiles, 256); bands when grid % 8 == 0)

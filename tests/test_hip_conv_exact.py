@@ -133,15 +133,32 @@ def test_conv12_fused(dev, shape):
     _run_conv12(dev, R.conv12_case(shape), shape)
 
 
-@pytest.mark.parametrize("shape", R.DECODER_SHAPES, ids=ids)
-def test_decoder_fused(dev, shape):
-    """decoder_fused(finish=True) against torch conv -> relu -> bf16 -> conv + bias; (3, 117, 440) for the per-tile seam buffers."""
+@pytest.mark.parametrize("shape", R.SCHEDULES, ids=ids)
+def test_conv12_fused_schedules(dev, shape):
+    """conv12_fused_kernel walks the two-group schedule of csrc/conv_pingpong.h: XCD bands with second tiles, round robin, one tile
+    per XCD, groups with 0, 1 and 2 tiles (tile counts per shape: _exact_ref.SCHED_LARGE / SCHED_SMALL)."""
+    _run_conv12(dev, R.conv12_case(shape), shape)
+
+
+def _run_decoder(dev, shape):
     from transformerupscaler_amd import ops, packing
     case = R.decoder_case(shape)
     o, exp = case.operands, _expected(case, shape)
     p1, pb1 = (t.to(dev) for t in packing.pack_conv_c64(o["w1"], o["b1"], 1))
     got = ops.decoder_fused(R.nhwc_bf16(o["x"]).to(dev), p1, pb1, packing.pack_dec2_scatter(o["w2"]).to(dev), o["b2"].to(dev))
     R.assert_bit_equal(got, exp["out"], layout="nchw", what=f"decoder_fused {shape}")
+
+
+@pytest.mark.parametrize("shape", R.DECODER_SHAPES, ids=ids)
+def test_decoder_fused(dev, shape):
+    """decoder_fused(finish=True) against torch conv -> relu -> bf16 -> conv + bias; (3, 117, 440) for the per-tile seam buffers."""
+    _run_decoder(dev, shape)
+
+
+@pytest.mark.parametrize("shape", R.SCHEDULES, ids=ids)
+def test_decoder_fused_schedules(dev, shape):
+    """decoder_fused_kernel over the same schedules as test_conv12_fused_schedules."""
+    _run_decoder(dev, shape)
 
 
 def _run_bra(dev, shape, r):

@@ -5,10 +5,10 @@
 //                        zero border, Hp = 8 tilesY + 4, Wp = 32 tilesX + 4: every conv2 tile's 12 x 36 input halo is in range
 //                        and conv1's zero padding is already in the data.  8 B per pixel; each value is the bf16 conv1 stages
 //                        (f32_to_bf16 in conv_thin.hip).
-// conv12_fused_kernel    the persistent ping-pong skeleton of conv_c64_persistent_kernel<4,0,3> (copied, so that
-//                        conv3x3_c64.hip stays byte-for-byte what training, the up-convs and decoder_conv1's unfused arm run).
-//                        The K loop and the store phase are unchanged; the idle wave group no longer DMA-fetches its next
-//                        10 x 34 feat1 halo image but computes it:
+// conv12_fused_kernel    the persistent ping-pong conv of conv_pingpong.h: tile walk, K loop and weight staging are the ones
+//                        conv_c64_persistent_kernel<4,0,3> uses, the store phase is that kernel's with ReLU.  What this kernel adds
+//                        is its phase loop: the idle wave group does not DMA-fetch its next 10 x 34 feat1 halo image but
+//                        computes it:
 //   * the halo is cut into 22 runs of 16 pixels in image order (q = 16 G + p, G = wave + 4 j): 6 runs for waves 0 / 1, 5 for 2 / 3;
 //   * lane (g, p) needs conv1's k = 8 g .. 8 g + 7, k = (dy 3 + dx) 3 + c.  It loads five words of four pixels of the compact
 //     copy (S0.hi, S1, S2, S3, S4.lo; which pixel each slot is depends on g only, a table in LDS) and forms the four
@@ -20,28 +20,18 @@
 //   * the compact-copy loads (and conv1's A fragments) are issued BEFORE the finished tile's stores: vmcnt retires in order, so
 //     loads issued behind the stores would wait for the stores' write latency.
 // Every run reads only what its own wave loads, so no wave of the group waits for another before the phase barrier.
-#include "common.h"
+#include "conv_pingpong.h"
 
 namespace {
 
 constexpr int TH = 8, TW = 32, HALO_W = TW + 2, HALO_H = TH + 2, NPIX_HALO = HALO_H * HALO_W;
 constexpr int IN_BYTES = NPIX_HALO * 128;
-constexpr int WROWS = 64, WSLAB = WROWS * 128, WCHUNKS = 9 * WROWS * 8;
+constexpr int WROWS = 64, WSLAB = WROWS * 128;
 constexpr int NRUNS = (NPIX_HALO + 15) / 16;                 // 22 runs of 16 halo pixels
 constexpr int RUNS_PER_WAVE = (NRUNS + 3) / 4;               // 6
 // [9 taps][64 rows][128 B] conv2 weights | 2 x halo image | conv2 bias [64] | conv1 bias [64] | per-g slot table [4][16] words
 constexpr size_t C12_LDS = (size_t)9 * WSLAB + 2 * (size_t)IN_BYTES + 256 + 256 + 256;
 static_assert(C12_LDS <= 163840, "LDS budget");
-
-__device__ __attribute__((aligned(16))) unsigned int c12_store_sink[64 * 8];
-
-// ReLU'd bf16 pair: ONE v_cvt_pk_bf16_f32 (RNE, the rounding of pack_bf16x2) + v_pk_max_i16 against 0 (a negative bf16 is a negative
-// int16).  pack_bf16x2's two scalar conversions compile to two v_cvt_pk_bf16_f32 and a v_perm_b32.
-TUP_DEVICE uint32_t relu_pack_bf16x2(float lo, float hi) {
-    typedef short s16x2 __attribute__((ext_vector_type(2)));
-    const bf16x2 v = __builtin_convertvector(f32x2{lo, hi}, bf16x2);
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), s16x2{0, 0}));
-}
 
 __global__ __launch_bounds__(256) void conv1_compact_kernel(const float* __restrict__ x, u32x2* __restrict__ xc, int H, int W,
                                                             int Hp, int Wp)
@@ -77,64 +67,13 @@ __global__ __launch_bounds__(512, 2) void conv12_fused_kernel(
     float* bias_lds = reinterpret_cast<float*>(in_lds + 2 * IN_BYTES);      // conv2 bias, then conv1 bias
     uint32_t* tab_lds = reinterpret_cast<uint32_t*>(in_lds + 2 * IN_BYTES + 512);
 
-    struct TC { int tx, ty, b; };
-
-    // ---- conv2's fragment addresses and K loop: as conv_c64_persistent_kernel<4,0,3> ----
+    // ---- conv2's fragment addresses (its K loop: k_loop<4, 9>) ----
     uint32_t poff[9][2];
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-        for (int rw = 0; rw < 2; ++rw)
-            poff[tap][rw] = lds_addr(my_in) + (uint32_t)swz128((2 * wave + rw) * HALO_W + p + (tap / 3) * HALO_W + (tap % 3), g);
-    const uint32_t wbase0 = lds_addr(w_lds) + (uint32_t)swz128(p, g), wbase1 = wbase0 ^ 64u;
-    const uint32_t wbase0h = wbase0 + 57344u, wbase1h = wbase1 + 57344u;
+    pixel_frag_offsets<3, HALO_W>(poff, my_in, wave, g, p);
+    const uint32_t wbase0 = weight_frag_base(w_lds, g, p);
 
     f32x4 acc[4][4];
     const uint32_t bias_addr = lds_addr(bias_lds) + (uint32_t)(g * 64);
-    auto compute_tile = [&]() {
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) acc[0][ct] = __builtin_bit_cast(f32x4, lds_read_b128_asm(bias_addr + ct * 16));
-        lds_wait<0>();
-#pragma unroll
-        for (int pg = 1; pg < 4; ++pg)
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) acc[pg][ct] = acc[0][ct];
-        constexpr int NSTEPS = 18, PER = 8;
-        bf16x8 pf[3][4], wf[3][4];
-        auto load_one = [&](int step, int slot, int j) {
-            const int tap = step >> 1;
-            if (j < 4) {
-                pf[slot][j] = (step & 1) ? lds_read_b128_asm_off_x64(poff[tap][j >> 1], (j & 1) * 2048)
-                                         : lds_read_b128_asm_off(poff[tap][j >> 1], (j & 1) * 2048);
-            } else {
-                const int woff = (tap * WROWS + (j - 4) * 16) * 128;
-                wf[slot][j - 4] = woff < 57344 ? lds_read_b128_asm_off((step & 1) ? wbase1 : wbase0, woff)
-                                               : lds_read_b128_asm_off((step & 1) ? wbase1h : wbase0h, woff - 57344);
-            }
-        };
-#pragma unroll
-        for (int j = 0; j < PER; ++j) load_one(0, 0, j);
-#pragma unroll
-        for (int j = 0; j < PER; ++j) load_one(1, 1, j);
-#pragma unroll
-        for (int step = 0; step < NSTEPS; ++step) {
-            const int cur = step % 3;
-            if (step + 1 < NSTEPS) lds_wait<PER>(); else lds_wait<0>();
-            __builtin_amdgcn_sched_barrier(0);
-            int rd = 0;
-#pragma unroll
-            for (int m = 0; m < 16; ++m) {
-                if (step + 2 < NSTEPS) {
-#pragma unroll
-                    for (int j = 0; j < PER; ++j)
-                        if (j == rd && j * 16 <= m * PER) { load_one(step + 2, (step + 2) % 3, j); ++rd; }
-                }
-                const int pg = m / 4, ct = m % 4;
-                acc[pg][ct] = mfma16x16x32(wf[cur][ct], pf[cur][pg], acc[pg][ct]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    };
 
     // ---- store phase: as conv_c64_persistent_kernel<4,0,3> with relu (8 stores per wave, out-of-image lanes to the sink) ----
     auto store_tile = [&](const TC& c) {
@@ -150,7 +89,7 @@ __global__ __launch_bounds__(512, 2) void conv12_fused_kernel(
                 pk[ct * 2 + 0] = relu_pack_bf16x2(acc[pg][ct][0], acc[pg][ct][1]);
                 pk[ct * 2 + 1] = relu_pack_bf16x2(acc[pg][ct][2], acc[pg][ct][3]);
             }
-            bf16_t* o = ok ? out + eoff : reinterpret_cast<bf16_t*>(c12_store_sink) + lane * 16;
+            bf16_t* o = ok ? out + eoff : reinterpret_cast<bf16_t*>(tup_store_sink) + lane * 16;
             *reinterpret_cast<u32x4*>(o) = u32x4{pk[0], pk[1], pk[2], pk[3]};
             *reinterpret_cast<u32x4*>(o + 8) = u32x4{pk[4], pk[5], pk[6], pk[7]};
         }
@@ -234,37 +173,13 @@ __global__ __launch_bounds__(512, 2) void conv12_fused_kernel(
         }
     };
 
-    int first, first0, stride, limit;
-    if ((gridDim.x & 7) == 0) {
-        const int per = gridDim.x >> 3, band = (total_tiles + 7) >> 3, start = (blockIdx.x & 7) * band;
-        limit = min(total_tiles, start + band);
-        first0 = start + (blockIdx.x >> 3);
-        first = first0 + grp * per;
-        stride = 2 * per;
-    } else {
-        limit = total_tiles;
-        first0 = blockIdx.x;
-        first = first0 + grp * gridDim.x;
-        stride = 2 * gridDim.x;
-    }
-    const int my_count = first < limit ? (limit - first + stride - 1) / stride : 0;
-    const int cnt0 = first0 < limit ? (limit - first0 + stride - 1) / stride : 0;
-    const int nphases = 2 * cnt0 + 1;
-    TC c_first;
-    { const int t = first / tilesX; c_first.tx = first - t * tilesX; c_first.ty = t % tilesY; c_first.b = t / tilesY; }
-    const int step_x = stride % tilesX, step_y = (stride / tilesX) % tilesY, step_b = stride / (tilesX * tilesY);
-    auto advance = [&](TC& c) {
-        c.tx += step_x;
-        if (c.tx >= tilesX) { c.tx -= tilesX; ++c.ty; }
-        c.ty += step_y; c.b += step_b;
-        if (c.ty >= tilesY) { c.ty -= tilesY; ++c.b; }
-    };
+    const TileWalk walk(total_tiles, tilesX, tilesY, grp, true);
+    const int my_count = walk.my_count, nphases = walk.nphases;
+    const TC c_first = walk.first;
 
-    for (int idx = threadIdx.x; idx < WCHUNKS; idx += 512) {
-        const int row = idx >> 3, c = idx & 7;
-        *reinterpret_cast<u32x4*>(w_lds + swz128(row, c)) = *reinterpret_cast<const u32x4*>(wp + (size_t)idx * 8);
-    }
-    if (threadIdx.x < 128) bias_lds[threadIdx.x] = threadIdx.x < 64 ? bias[threadIdx.x] : b1[threadIdx.x - 64];   // [g][ct][e] = channel order
+    stage_weights<4, 9>(w_lds, wp);
+    // both biases in one pass ([g][ct][e] = channel order; stage_bias would be a second load and store for conv1's)
+    if (threadIdx.x < 128) bias_lds[threadIdx.x] = threadIdx.x < 64 ? bias[threadIdx.x] : b1[threadIdx.x - 64];
     if (threadIdx.x < 64) {
         // slot table of lane group g: words 0..4 = byte offsets of pixel slots S0..S4 = (dy, dx) below, words 8..11 = the
         // v_perm selectors of fragment words 0..3.  X = {S_i channel 2, S_i+1 channel 0}, Y = {channel 1, channel 2} of one
@@ -288,14 +203,14 @@ __global__ __launch_bounds__(512, 2) void conv12_fused_kernel(
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();
     TC c_done = c_first, c_next = c_first;
-    if (grp == 0) advance(c_next);
+    if (grp == 0) walk.advance(c_next);
 
     // phase ph: group (ph & 1) runs the K loop of its tile ph >> 1; the other group issues its next tile's conv1 loads, stores
     // its previous tile and builds the next tile's halo image in its (now idle) buffer.  One workgroup barrier per phase.
     for (int ph = 0; ph < nphases; ++ph) {
         const int k = ph >> 1;
         if ((ph & 1) == grp) {
-            if (k < my_count) compute_tile();
+            if (k < my_count) k_loop<4, 9>(acc, poff, wbase0, bias_addr);
         } else {
             const int done = grp == 0 ? k : k - 1;
             const int nxt = done + 1;
@@ -318,7 +233,7 @@ __global__ __launch_bounds__(512, 2) void conv12_fused_kernel(
                 store_tile(c_done);
             }
             c_done = c_next;
-            advance(c_next);
+            walk.advance(c_next);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();

@@ -14,7 +14,7 @@
 // iteration writes whole 128-B NHWC pixels of the shuffled image -- the shuffle is free).
 // MFMA operands: A = weights (rows = cout), B = pixels (cols), v_mfma_f32_16x16x32_bf16,
 // so a lane ends up with 16 consecutive output channels of one pixel (32-B stores).
-#include "common.h"
+#include "conv_pingpong.h"
 #include <stdlib.h>
 
 namespace {
@@ -248,10 +248,6 @@ __global__ __launch_bounds__(256, (CT <= 4 && KS == 3) ? 2 : 1) void conv3x3_c64
 //     40 % of the time when a single group did everything in sequence -- hide under it.
 // LDS: 9*8 KB + 2*43.5 KB = 160,768 B of the CU's 163,840 B.
 // ------------------------------------------------------------------------------------------------
-__device__ __attribute__((aligned(16))) unsigned int tup_zero_line[4] = {0u, 0u, 0u, 0u};
-// Store sink for lanes whose pixel is outside the image: keeps the number of store instructions per wave
-// fixed (the counted vmcnt below relies on it); never read.
-__device__ __attribute__((aligned(16))) unsigned int tup_store_sink[64 * 8];
 // Timing experiments (TUP_CONV_STAMPS=1, scripts/_conv_stamps.py): s_memtime of wave 0 of each group of workgroup 100
 // at the phase boundaries of the first phases.  [group][phase][0 = phase start, 1 = K loop end | DMA issued,
 // 2 = stores issued, 3 = vmcnt wait over, 4 = barrier passed]
@@ -266,8 +262,8 @@ __global__ __launch_bounds__(512, 2) void conv_c64_persistent_kernel(
 {
     constexpr int PADK = KS / 2, HALO_W = TW + KS - 1, HALO_H = TH + KS - 1, NPIX_HALO = HALO_H * HALO_W;
     constexpr int NTAPS = KS * KS;
-    constexpr int IN_BYTES = NPIX_HALO * 128, IN_CHUNKS = NPIX_HALO * 8;
-    constexpr int WROWS = CT * 16, WSLAB = WROWS * 128, WCHUNKS = NTAPS * WROWS * 8;
+    constexpr int IN_BYTES = NPIX_HALO * 128;
+    constexpr int WROWS = CT * 16, WSLAB = WROWS * 128;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* w_lds = smem;                              // [NTAPS][WROWS][128 B]
     char* in_lds = smem + NTAPS * WSLAB;             // [2 groups][IN_BYTES]
@@ -279,146 +275,18 @@ __global__ __launch_bounds__(512, 2) void conv_c64_persistent_kernel(
     const int total_tiles = tilesX * tilesY * B;
     char* my_in = in_lds + grp * IN_BYTES;
 
-    // Halo-image DMA.  The (pixel, chunk) -> source-offset map of a lane's pieces does not depend on the tile, so it
-    // is computed once (rel[]); an interior tile then costs one 64-bit add + one DMA per piece.  (The issuing group
-    // shares its SIMDs with the other group's MFMA stream and gets roughly one VALU issue per 12-18 cycles: the
-    // ~30 address instructions per piece of the general path made DMA issue 4.1 k cycles of a 12.5 k-cycle phase.)
-    constexpr int NPIECE = (IN_CHUNKS + 255) / 256;
-    int rel[NPIECE];
-#pragma unroll
-    for (int it = 0; it < NPIECE; ++it) {
-        const int idx = min(it * 256 + tid, IN_CHUNKS - 1);
-        const int q = idx >> 3, c = (idx & 7) ^ ((q >> 1) & 7);
-        const int yy = q / HALO_W, xx = q - yy * HALO_W;
-        rel[it] = ((yy - PADK) * W + (xx - PADK)) * 128 + c * 16;
-    }
-    constexpr bool LAST_PARTIAL = (IN_CHUNKS % 256) != 0;
-    const bool last_ok = (NPIECE - 1) * 256 + tid < IN_CHUNKS;
-    // Tile coordinates are carried, not decoded: a tile index -> (tx, ty, b) decode is two integer divisions = ~30 VALU
-    // instructions each even for a wave-uniform value, twice per phase, and every VALU instruction of the idle wave group costs the
-    // other group's K loop ~5 cycles of MFMA issue.  A group's tiles advance by a fixed stride: one carry chain per phase.
-    struct TC { int tx, ty, b; };
-    auto prefetch_tile = [&](const TC& c) {
-        const int tx = c.tx, ty = c.ty, b = c.b;
-        const int ty0 = ty * TH, tx0 = tx * TW;
-        const char* xb = reinterpret_cast<const char*>(x + (size_t)b * H * W * 64);
-        if (ty0 >= PADK && ty0 + TH + PADK <= H && tx0 >= PADK && tx0 + TW + PADK <= W) {       // interior tile
-            const char* tb = xb + ((size_t)ty0 * W + tx0) * 128;
-#pragma unroll
-            for (int it = 0; it < NPIECE; ++it) {
-                if (LAST_PARTIAL && it == NPIECE - 1 && !last_ok) continue;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tb + rel[it]),
-                                                 (__attribute__((address_space(3))) void*)(my_in + (it * 256 + wave * 64) * 16), 16, 0, 0);
-            }
-            return;
-        }
-#pragma unroll 1
-        for (int base = 0; base < IN_CHUNKS; base += 256) {
-            const int idx = base + tid;                     // physical 16-B chunk of the LDS image
-            if (idx < IN_CHUNKS) {
-                const int q = idx >> 3, cphys = idx & 7;
-                const int c = cphys ^ ((q >> 1) & 7);       // logical chunk stored there (swizzle on the SOURCE side)
-                const int yy = q / HALO_W, xx = q - yy * HALO_W;
-                const int iy = ty0 - PADK + yy, ix = tx0 - PADK + xx;
-                const void* src = (iy >= 0 && iy < H && ix >= 0 && ix < W)
-                                      ? (const void*)(xb + ((size_t)(iy * W + ix) * 128 + c * 16)) : (const void*)tup_zero_line;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)(my_in + (base + wave * 64) * 16), 16, 0, 0);
-            }
-        }
-    };
-    auto stage_weights = [&](int nt) {
-        const bf16_t* wsrc = wp + (size_t)nt * NTAPS * WROWS * 64;
-        for (int idx = threadIdx.x; idx < WCHUNKS; idx += 512) {
-            const int row = idx >> 3, c = idx & 7;             // row = tap*WROWS + n_local
-            *reinterpret_cast<u32x4*>(w_lds + swz128(row, c)) = *reinterpret_cast<const u32x4*>(wsrc + (size_t)idx * 8);
-        }
-    };
+    const HaloDma<HALO_H, HALO_W, PADK> dma(W, tid);
+    auto prefetch_tile = [&](const TC& c) { dma.prefetch(x, c.b, c.ty * TH, c.tx * TW, H, W, my_in, tup_zero_line); };
 
-    // loop-invariant LDS byte offsets of this lane's fragments (kh = 0; kh = 1 is "^ 64")
-    // Fragment addresses = a few base registers + the ds_read immediate offset.  Pixel group pg = 2*row + half: the
-    // second half of a row is 16 pixels = 2048 B further and has the same swizzle phase ((q >> 1) & 7 is unchanged by
-    // q + 16), so the table holds the two rows of each tap (with this group's image base folded in; the image is
-    // 128-B aligned, so the kh = 1 form is still "^ 64").  Weights: row p of slab (tap, ct) = wbase + a constant.
+    // loop-invariant LDS byte offsets of this lane's fragments
     uint32_t poff[NTAPS][2];
-#pragma unroll
-    for (int tap = 0; tap < NTAPS; ++tap)
-#pragma unroll
-        for (int rw = 0; rw < 2; ++rw)
-            poff[tap][rw] = lds_addr(my_in) + (uint32_t)swz128((2 * wave + rw) * HALO_W + p + (tap / KS) * HALO_W + (tap % KS), g);
-    const uint32_t wbase0 = lds_addr(w_lds) + (uint32_t)swz128(p, g), wbase1 = wbase0 ^ 64u;
-    const uint32_t wbase0h = wbase0 + 57344u, wbase1h = wbase1 + 57344u;          // second window of the 16-bit offset
+    pixel_frag_offsets<KS, HALO_W>(poff, my_in, wave, g, p);
+    const uint32_t wbase0 = weight_frag_base(w_lds, g, p);
 
     f32x4 acc[4][CT];
     // this lane's bias values live in LDS ([g][ct][4] floats after the two input images), not in 4*CT registers
     float* bias_lds = reinterpret_cast<float*>(in_lds + 2 * IN_BYTES);
     const uint32_t bias_addr = lds_addr(bias_lds) + (uint32_t)(g * CT * 16);
-    // K loop: fragments are requested TWO K-steps ahead (3-slot ring).  With the other group's DMA landing in LDS and
-    // its epilogue on the same SIMDs a ds_read_b128 takes ~500 cycles (stamped); one step (16 MFMAs = 256 cycles)
-    // of distance left the loop waiting on LDS: 10.4 k cycles per tile instead of the 4.6 k its MFMAs need.
-    auto compute_tile = [&]() {
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) acc[0][ct] = __builtin_bit_cast(f32x4, lds_read_b128_asm(bias_addr + ct * 16));
-        lds_wait<0>();
-#pragma unroll
-        for (int pg = 1; pg < 4; ++pg)
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) acc[pg][ct] = acc[0][ct];      // bias rides in the accumulator
-        constexpr int NSTEPS = NTAPS * 2;
-        constexpr int PER = 4 + CT;                                         // ds_reads per K-step
-        bf16x8 pf[3][4], wf[3][CT];
-        auto load_frags = [&](int step, int slot) {
-            const int tap = step >> 1;
-#pragma unroll
-            for (int pg = 0; pg < 4; ++pg)
-                pf[slot][pg] = (step & 1) ? lds_read_b128_asm_off_x64(poff[tap][pg >> 1], (pg & 1) * 2048)
-                                          : lds_read_b128_asm_off(poff[tap][pg >> 1], (pg & 1) * 2048);
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                const int woff = (tap * WROWS + ct * 16) * 128;
-                wf[slot][ct] = woff < 57344 ? lds_read_b128_asm_off((step & 1) ? wbase1 : wbase0, woff)
-                                            : lds_read_b128_asm_off((step & 1) ? wbase1h : wbase0h, woff - 57344);
-            }
-        };
-        load_frags(0, 0);
-        load_frags(1, 1);
-        // the requests of step + 2 are spread over the step's MFMAs (one per NM / PER of them): issued as a block at the top
-        // of the step they cost the wave ~60 issue cycles per step in which its matrix pipe idles (conv2: 450 -> 425 us)
-        auto load_one = [&](int step, int slot, int j) {
-            const int tap = step >> 1;
-            if (j < 4) {
-                pf[slot][j] = (step & 1) ? lds_read_b128_asm_off_x64(poff[tap][j >> 1], (j & 1) * 2048)
-                                         : lds_read_b128_asm_off(poff[tap][j >> 1], (j & 1) * 2048);
-            } else {
-                const int ct = j - 4;
-                const int woff = (tap * WROWS + ct * 16) * 128;
-                wf[slot][ct] = woff < 57344 ? lds_read_b128_asm_off((step & 1) ? wbase1 : wbase0, woff)
-                                            : lds_read_b128_asm_off((step & 1) ? wbase1h : wbase0h, woff - 57344);
-            }
-        };
-#pragma unroll
-        for (int step = 0; step < NSTEPS; ++step) {
-            const int cur = step % 3;
-            if (step + 1 < NSTEPS) lds_wait<PER>(); else lds_wait<0>();
-            __builtin_amdgcn_sched_barrier(0);
-            constexpr int NM = 4 * CT;
-            int rd = 0;
-#pragma unroll
-            for (int m = 0; m < NM; ++m) {
-                if (step + 2 < NSTEPS) {
-#pragma unroll
-                    // request j goes out before MFMA m = floor(j NM / PER): every one of the PER requests is issued also when
-                    // the step has fewer MFMAs than requests (CT = 1: NM = 4, PER = 5; "j NM <= m PER" never issued the weight
-                    // fragment there); for CT = 4 (NM = 16, PER = 8) this is the same schedule, j = m / 2
-                    for (int j = 0; j < PER; ++j)
-                        if (j == rd && j * NM < (m + 1) * PER) { load_one(step + 2, (step + 2) % 3, j); ++rd; }
-                }
-                const int pg = m / CT, ct = m % CT;
-                acc[pg][ct] = mfma16x16x32(wf[cur][ct], pf[cur][pg], acc[pg][ct]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    };
 
     auto store_tile = [&](const TC& c, int nt) {
         const int tx = c.tx, ty = c.ty, b = c.b;
@@ -514,50 +382,19 @@ __global__ __launch_bounds__(512, 2) void conv_c64_persistent_kernel(
         }
     };
 
-    // tiles of this workgroup; group `grp` takes every second one.  XCD-contiguous bands (blockIdx & 7 = XCD, see
-    // bra_rows_persistent_kernel): neighbouring tiles' shared halo stays in one L2.
-    int first, first0, stride, limit;
-    if ((gridDim.x & 7) == 0 && !(stamps & 2)) {
-        const int per = gridDim.x >> 3, band = (total_tiles + 7) >> 3, start = (blockIdx.x & 7) * band;
-        limit = min(total_tiles, start + band);
-        first0 = start + (blockIdx.x >> 3);
-        first = first0 + grp * per;
-        stride = 2 * per;
-    } else {
-        limit = total_tiles;
-        first0 = blockIdx.x;
-        first = first0 + grp * gridDim.x;
-        stride = 2 * gridDim.x;
-    }
-    const int my_count = first < limit ? (limit - first + stride - 1) / stride : 0;
-    const int cnt0 = first0 < limit ? (limit - first0 + stride - 1) / stride : 0;   // group 0's count >= group 1's
-    const int nphases = 2 * cnt0 + 1;               // uniform for the whole workgroup
-    auto decode = [&](int tile) { TC c; c.tx = tile % tilesX; const int t = tile / tilesX; c.ty = t % tilesY; c.b = t / tilesY; return c; };
-    const TC c_first = decode(first);
-    const int step_x = stride % tilesX, step_y = (stride / tilesX) % tilesY, step_b = stride / (tilesX * tilesY);
-    auto advance = [&](TC& c) {                       // + stride tiles
-        c.tx += step_x;
-        if (c.tx >= tilesX) { c.tx -= tilesX; ++c.ty; }
-        c.ty += step_y; c.b += step_b;
-        if (c.ty >= tilesY) { c.ty -= tilesY; ++c.b; }
-    };
+    // tiles of this workgroup; group `grp` takes every second one
+    const TileWalk walk(total_tiles, tilesX, tilesY, grp, !(stamps & 2));
+    const int my_count = walk.my_count, nphases = walk.nphases;
+    const TC c_first = walk.first;
 
     for (int nt = 0; nt < ntiles; ++nt) {
-        stage_weights(nt);
-        if (threadIdx.x < 16 * CT) {                 // bias of this cout tile in the order the lanes read it: [g][ct][e]
-            const int gg = threadIdx.x / (4 * CT), ct = (threadIdx.x / 4) % CT, e = threadIdx.x & 3;
-            float bval = 0.f;
-            if (bias) {
-                if constexpr (OUT_MODE == OUT_NHWC_BF16) bval = bias[nt * 64 + gg * 16 + ct * 4 + e];
-                else { const int co = 16 * ct + 4 * gg + e; bval = co < cout_valid ? bias[co] : 0.f; }
-            }
-            bias_lds[threadIdx.x] = bval;
-        }
+        stage_weights<CT, NTAPS>(w_lds, wp + (size_t)nt * NTAPS * WROWS * 64);
+        stage_bias<CT, OUT_MODE != OUT_NHWC_BF16>(bias_lds, bias, nt, cout_valid);
         if (grp == 0 && my_count > 0) prefetch_tile(c_first);
         __syncthreads();            // weights + group 0's first tile visible (the barrier's vmcnt(0) retires the DMA)
         // c_done = the tile this group computed last (to be stored), c_next = the one to fetch next
         TC c_done = c_first, c_next = c_first;
-        if (grp == 0) advance(c_next);
+        if (grp == 0) walk.advance(c_next);
 
         // phase ph: group (ph & 1) runs the K loop of its tile k = ph >> 1; the other group stores its previous
         // tile and DMA-fetches its next one into its (now idle) buffer.  One workgroup barrier per phase.
@@ -567,7 +404,7 @@ __global__ __launch_bounds__(512, 2) void conv_c64_persistent_kernel(
             const int k = ph >> 1;
             stamp(ph, 0);
             if ((ph & 1) == grp) {
-                if (k < my_count && !(stamps & 16)) compute_tile();
+                if (k < my_count && !(stamps & 16)) k_loop<CT, NTAPS>(acc, poff, wbase0, bias_addr);
                 stamp(ph, 1);
             } else {
                 // group 0 is here on odd phases (just computed tile k, next is k+1); group 1 on even phases
@@ -591,7 +428,7 @@ __global__ __launch_bounds__(512, 2) void conv_c64_persistent_kernel(
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 }
                 c_done = c_next;                     // the tile just fetched is computed next and stored in this group's next idle phase
-                advance(c_next);
+                walk.advance(c_next);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             stamp(ph, 3);
@@ -640,8 +477,8 @@ int launch_persistent(const void* x, const void* wp, const float* bias, const vo
 // so a halo pixel is read five times (once per dy) and a K-step is 4 pixel + 4 weight fragments for 16 MFMAs.  The weight
 // rows are ordered so that lane (g, p) of the accumulators ends with sub-pixel g's three image channels x five dx (slot
 // s = tile*4 + e = ch*5 + dx) of halo column p: the dx sum is 4 + 4 DPP row shifts per output, no LDS round trip.
-// Tile = 8 rows x 28 output columns (halo image 12 x 32 pixels: two whole 16-pixel groups per row); the ping-pong / DMA
-// skeleton is the persistent kernel's.  LDS: 5*8 KB + 2*48 KB = 139,264 B.
+// Tile = 8 rows x 28 output columns (halo image 12 x 32 pixels: two whole 16-pixel groups per row); tile walk and halo DMA
+// are conv_pingpong.h's, the row-GEMM K loop is its own.  LDS: 5*8 KB + 2*48 KB = 139,264 B.
 // ------------------------------------------------------------------------------------------------
 constexpr int R5_TW = 28, R5_HW = 32, R5_HH = TH + 4, R5_NPIX = R5_HH * R5_HW, R5_IN_BYTES = R5_NPIX * 128;
 constexpr int R5_W_BYTES = 5 * 64 * 128;
@@ -659,41 +496,10 @@ __global__ __launch_bounds__(512, 2) void bra_rows_persistent_kernel(
     const int total_tiles = tilesX * tilesY * B;
     char* my_in = in_lds + grp * R5_IN_BYTES;
 
-    constexpr int IN_CHUNKS = R5_NPIX * 8, NPIECE = IN_CHUNKS / 256;          // 12 pieces exactly
-    static_assert(IN_CHUNKS % 256 == 0, "whole DMA pieces");
-    int rel[NPIECE];
-#pragma unroll
-    for (int it = 0; it < NPIECE; ++it) {
-        const int idx = it * 256 + tid;
-        const int q = idx >> 3, c = (idx & 7) ^ ((q >> 1) & 7);
-        const int yy = q / R5_HW, xx = q - yy * R5_HW;
-        rel[it] = ((yy - 2) * W + (xx - 2)) * 128 + c * 16;
-    }
-    struct TC { int tx, ty, b; };                    // tile coordinates are carried across phases, not decoded (conv_c64_persistent_kernel)
-    auto prefetch_tile = [&](const TC& c) {
-        const int tx = c.tx, ty = c.ty, b = c.b;
-        const int ty0 = ty * TH, tx0 = tx * R5_TW;
-        const char* xb = reinterpret_cast<const char*>(x + (size_t)b * H * W * 64);
-        if (ty0 >= 2 && ty0 + TH + 2 <= H && tx0 >= 2 && tx0 + R5_HW - 2 <= W) {          // interior tile
-            const char* tb = xb + ((size_t)ty0 * W + tx0) * 128;
-#pragma unroll
-            for (int it = 0; it < NPIECE; ++it)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tb + rel[it]),
-                                                 (__attribute__((address_space(3))) void*)(my_in + (it * 256 + wave * 64) * 16), 16, 0, 0);
-            return;
-        }
-#pragma unroll 1
-        for (int base = 0; base < IN_CHUNKS; base += 256) {
-            const int idx = base + tid;
-            const int q = idx >> 3, c = (idx & 7) ^ ((q >> 1) & 7);
-            const int yy = q / R5_HW, xx = q - yy * R5_HW;
-            const int iy = ty0 - 2 + yy, ix = tx0 - 2 + xx;
-            const void* src = (iy >= 0 && iy < H && ix >= 0 && ix < W)
-                                  ? (const void*)(xb + ((size_t)(iy * W + ix) * 128 + c * 16)) : (const void*)tup_zero_line;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(my_in + (base + wave * 64) * 16), 16, 0, 0);
-        }
-    };
+    using Dma = HaloDma<R5_HH, R5_HW, 2>;
+    static_assert(!Dma::LAST_PARTIAL && Dma::NPIECE == 12, "12 whole DMA pieces");
+    const Dma dma(W, tid);
+    auto prefetch_tile = [&](const TC& c) { dma.prefetch(x, c.b, c.ty * TH, c.tx * R5_TW, H, W, my_in, tup_zero_line); };
 
     // weights: LDS row (dy, tile t, r = 4*gg + e) <- tap (dy, dx), output co = ch*4 + gg of the 25-tap packing [25][16][64],
     // slot s = t*4 + e = ch*5 + dx (slot 15 is zero)
@@ -761,10 +567,6 @@ __global__ __launch_bounds__(512, 2) void bra_rows_persistent_kernel(
         }
     };
 
-    // acc += (v of lane p + n of the same 16-lane row, 0 past its end) / (v of lane p - n, 0 before its start): one
-    // v_add_f32 with a DPP source (hipcc keeps a v_mov_b32_dpp + v_add_f32 pair per term: 154 instead of 82 instructions, and
-    // every VALU instruction of this phase takes issue cycles from the other group's MFMA stream on the same SIMD)
-#define TUP_ADD_DPP(acc, v, ctrl) asm("v_add_f32_dpp %0, %1, %0 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(acc) : "v"(v))
     auto store_tile = [&](const TC& c) {
         const int tx = c.tx, ty = c.ty, b = c.b;
         const int Wr = W * 2, si = g >> 1, sj = g & 1;
@@ -797,44 +599,14 @@ __global__ __launch_bounds__(512, 2) void bra_rows_persistent_kernel(
             }
         }
     };
-#undef TUP_ADD_DPP
 
-    // Tiles of this workgroup.  Workgroups go to the eight XCDs round-robin (blockIdx & 7), each with its own L2: an XCD takes
-    // one contiguous eighth of the tile list and its 32 workgroups walk it side by side, so the halo a tile shares with its
-    // left / right neighbours (same moment) and with the tile row above (46 tiles earlier) is found in THAT L2 instead of
-    // crossing the fabric once per XCD (halo image / tile = 1.71: the DMA alone ran at the same 227 us with nothing else on).
-    int first, first0, stride, limit;
-    if ((gridDim.x & 7) == 0 && !(ablate & 8)) {
-        const int per = gridDim.x >> 3, band = (total_tiles + 7) >> 3, start = (blockIdx.x & 7) * band;
-        limit = min(total_tiles, start + band);
-        first0 = start + (blockIdx.x >> 3);
-        first = first0 + grp * per;
-        stride = 2 * per;
-    } else {
-        limit = total_tiles;
-        first0 = blockIdx.x;
-        first = first0 + grp * gridDim.x;
-        stride = 2 * gridDim.x;
-    }
-    const int my_count = first < limit ? (limit - first + stride - 1) / stride : 0;
-    const int cnt0 = first0 < limit ? (limit - first0 + stride - 1) / stride : 0;      // group 0's count >= group 1's
-    const int nphases = 2 * cnt0 + 1;               // uniform for the whole workgroup
-
-    TC c_done, c_next;
-    {
-        const int t = first / tilesX;
-        c_done.tx = first - t * tilesX; c_done.ty = t % tilesY; c_done.b = t / tilesY;
-        c_next = c_done;
-    }
-    const int step_x = stride % tilesX, step_y = (stride / tilesX) % tilesY, step_b = stride / (tilesX * tilesY);
-    auto advance = [&](TC& c) {                       // + stride tiles
-        c.tx += step_x;
-        if (c.tx >= tilesX) { c.tx -= tilesX; ++c.ty; }
-        c.ty += step_y; c.b += step_b;
-        if (c.ty >= tilesY) { c.ty -= tilesY; ++c.b; }
-    };
+    // Tiles of this workgroup, in XCD bands (xcd_band): with round-robin tiles the halo a tile shares with its neighbours crossed
+    // the fabric once per XCD (halo image / tile = 1.71: the DMA alone ran at the same 227 us with nothing else on).
+    const TileWalk walk(total_tiles, tilesX, tilesY, grp, !(ablate & 8));
+    const int my_count = walk.my_count, nphases = walk.nphases;
+    TC c_done = walk.first, c_next = walk.first;
     if (grp == 0 && my_count > 0) prefetch_tile(c_next);
-    if (grp == 0) advance(c_next);
+    if (grp == 0) walk.advance(c_next);
     __syncthreads();
     for (int ph = 0; ph < nphases; ++ph) {
         const int k = ph >> 1;
@@ -852,7 +624,7 @@ __global__ __launch_bounds__(512, 2) void bra_rows_persistent_kernel(
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             c_done = c_next;                         // the tile just fetched: computed next, stored in this group's next idle phase
-            advance(c_next);
+            walk.advance(c_next);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -894,42 +666,15 @@ __global__ __launch_bounds__(256, 3) void conv3_thin_rows_kernel(
     const int g = lane >> 4, p = lane & 15;
     const int total_tiles = tilesX * tilesY * B;
 
-    constexpr int IN_CHUNKS = T3_NPIX * 8, NPIECE = IN_CHUNKS / 256;         // 10 pieces exactly
-    static_assert(IN_CHUNKS % 256 == 0, "whole DMA pieces");
-    int rel[NPIECE];
-#pragma unroll
-    for (int it = 0; it < NPIECE; ++it) {
-        const int idx = it * 256 + tid;
-        const int q = idx >> 3, c = (idx & 7) ^ ((q >> 1) & 7);
-        const int yy = q / T3_HW, xx = q - yy * T3_HW;
-        rel[it] = ((yy - 1) * W + (xx - 1)) * 128 + c * 16;
-    }
+    using Dma = HaloDma<T3_HH, T3_HW, 1>;
+    static_assert(!Dma::LAST_PARTIAL && Dma::NPIECE == 10, "10 whole DMA pieces");
+    const Dma dma(W, tid);
     auto prefetch_tile = [&](int tile) {
         int t = tile;
         const int tx = t % tilesX; t /= tilesX;
         const int ty = t % tilesY;
         const int b = t / tilesY;
-        const int ty0 = ty * TH, tx0 = tx * T3_TW;
-        const char* xb = reinterpret_cast<const char*>(x + (size_t)b * H * W * 64);
-        if (ty0 >= 1 && ty0 + TH + 1 <= H && tx0 >= 1 && tx0 + T3_HW - 1 <= W) {          // interior tile
-            const char* tb = xb + ((size_t)ty0 * W + tx0) * 128;
-#pragma unroll
-            for (int it = 0; it < NPIECE; ++it)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tb + rel[it]),
-                                                 (__attribute__((address_space(3))) void*)(smem + (it * 256 + wave * 64) * 16), 16, 0, 0);
-            return;
-        }
-#pragma unroll 1
-        for (int base = 0; base < IN_CHUNKS; base += 256) {
-            const int idx = base + tid;
-            const int q = idx >> 3, c = (idx & 7) ^ ((q >> 1) & 7);
-            const int yy = q / T3_HW, xx = q - yy * T3_HW;
-            const int iy = ty0 - 1 + yy, ix = tx0 - 1 + xx;
-            const void* src = (iy >= 0 && iy < H && ix >= 0 && ix < W)
-                                  ? (const void*)(xb + ((size_t)(iy * W + ix) * 128 + c * 16)) : (const void*)tup_zero_line;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(smem + (base + wave * 64) * 16), 16, 0, 0);
-        }
+        dma.prefetch(x, b, ty * TH, tx * T3_TW, H, W, smem, tup_zero_line);
     };
 
     // weight fragments (A operand: lane (g, p) = row p = 4c + dx, channels 8g.. of K half kh) straight from the packed
@@ -972,7 +717,6 @@ __global__ __launch_bounds__(256, 3) void conv3_thin_rows_kernel(
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-#define TUP_ADD_DPP(a, v, ctrl) asm("v_add_f32_dpp %0, %1, %0 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(a) : "v"(v))
     auto store_tile = [&](int tile) {
         int t = tile;
         const int tx = t % tilesX; t /= tilesX;
@@ -993,18 +737,10 @@ __global__ __launch_bounds__(256, 3) void conv3_thin_rows_kernel(
             }
         }
     };
-#undef TUP_ADD_DPP
 
-    // tiles: XCD-contiguous bands as in bra_rows_persistent_kernel (blockIdx & 7 = XCD)
+    // tiles: XCD-contiguous bands (blockIdx & 7 = XCD)
     int first, stride, limit;
-    if ((gridDim.x & 7) == 0) {
-        const int per = gridDim.x >> 3, band = (total_tiles + 7) >> 3, start = (blockIdx.x & 7) * band;
-        limit = min(total_tiles, start + band);
-        first = start + (blockIdx.x >> 3);
-        stride = per;
-    } else {
-        limit = total_tiles; first = blockIdx.x; stride = gridDim.x;
-    }
+    xcd_band(total_tiles, true, first, stride, limit);
     if (first < limit) prefetch_tile(first);
     for (int tile = first; tile < limit; tile += stride) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

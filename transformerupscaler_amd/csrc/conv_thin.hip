@@ -9,7 +9,7 @@
 // These are HBM-bound: conv1 writes 128 B per pixel and reads 12 B; the planar kernels move a
 // handful of fp32 planes.  conv1 still uses MFMA (im2col K = 27 padded to 32, one K-step) so
 // the VALU never limits the store stream.
-#include "common.h"
+#include "conv_pingpong.h"
 #include <stdlib.h>
 
 namespace {
@@ -200,13 +200,8 @@ __global__ __launch_bounds__(256, TUP_CONV1_OCC) void conv3x3_c3_persistent_kern
     // tiles of this workgroup: XCD-contiguous bands (blockIdx & 7 = XCD): a 34-float halo row straddles two or three 128-B lines
     // that the tiles left and right of it read too -- with neighbouring tiles on one XCD its L2 serves them (round-robin tiles
     // fetched 269 MB for the 88 MB input)
-    int G = gridDim.x, t = blockIdx.x;
-    if ((gridDim.x & 7) == 0 && xcd_bands) {
-        const int band = (ntiles + 7) >> 3, start = (blockIdx.x & 7) * band;
-        ntiles = min(ntiles, start + band);
-        t = start + (blockIdx.x >> 3);
-        G = gridDim.x >> 3;
-    }
+    int G, t;
+    xcd_band(ntiles, xcd_bands != 0, t, G, ntiles);
     if (t < ntiles) load_tile(t, vA);
     if (t + G < ntiles) load_tile(t + G, vB);
     __syncthreads();                                        // zero fill done before the first staging stores

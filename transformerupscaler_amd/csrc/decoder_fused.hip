@@ -3,9 +3,10 @@
 //
 // decoder_conv2 is linear, so it is evaluated in scatter form:
 //     residual(q) = b + sum_{dy,dx} Z_{dy,dx}(q + (dy-1, dx-1)),      Z_{dy,dx}(p) = W2[:, :, dy, dx] . dec(p)
-// Each dec pixel needs only its 27 projections (9 taps x 3 channels).  The persistent ping-pong conv (conv3x3_c64.hip,
-// conv_c64_persistent_kernel<4,0,3>: its skeleton is copied here so that the file of the kernel conv2 and bench.py's roofline
-// run stays byte-for-byte unchanged) computes them in its epilogue, where dec(p) already sits in registers:
+// Each dec pixel needs only its 27 projections (9 taps x 3 channels).  The persistent ping-pong conv (conv_pingpong.h: tile walk,
+// halo DMA, K loop and staging are the ones conv_c64_persistent_kernel<4,0,3> uses; this kernel adds decoder_conv2's A fragments,
+// the store phase below and a phase loop that counts their loads and stores) computes them in its epilogue, where dec(p) already
+// sits in registers:
 //   * B operand = the epilogue's packed ReLU'd bf16 words: lane (g, p) holds channels 16g + 8s + j (j = 0..7) of pixel p in
 //     pk[4s .. 4s+3], i.e. a valid 16x16x32 B fragment per K-step s = 0, 1 with logical k = 8g + j.  The host packs the
 //     decoder_conv2 weight image with its columns permuted the same way (packing.pack_dec2_scatter), so no data moves.
@@ -23,19 +24,15 @@
 // dec pixels outside the image hold ReLU(bias), not conv2's zero padding, so edge tiles zero them before the second GEMM.
 // At scale 2 the only reader of residual is the streaming output tail, which adds the pieces itself in the same order as it reads
 // them (tup_decoder_fused_parts_fwd here, tail_stream.hip PARTS): the finishing kernel then does not run.
-#include "common.h"
+#include "conv_pingpong.h"
 
 namespace {
 
 constexpr int TH = 8, TW = 32, HALO_W = TW + 2, HALO_H = TH + 2, NPIX_HALO = HALO_H * HALO_W;
-constexpr int IN_BYTES = NPIX_HALO * 128, IN_CHUNKS = NPIX_HALO * 8;
-constexpr int WROWS = 64, WSLAB = WROWS * 128, WCHUNKS = 9 * WROWS * 8;
+constexpr int IN_BYTES = NPIX_HALO * 128;
+constexpr int WROWS = 64, WSLAB = WROWS * 128;
 constexpr size_t DEC_LDS = (size_t)9 * WSLAB + 2 * (size_t)IN_BYTES + 256;          // + bias
 static_assert(DEC_LDS <= 163840, "LDS budget");
-
-__device__ __attribute__((aligned(16))) unsigned int dec_zero_line[4] = {0u, 0u, 0u, 0u};
-
-#define TUP_ADD_DPP(a, v, ctrl) asm("v_add_f32_dpp %0, %1, %0 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(a) : "v"(v))
 
 __global__ __launch_bounds__(512, 2) void decoder_fused_kernel(
     const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp, const float* __restrict__ bias,
@@ -52,55 +49,14 @@ __global__ __launch_bounds__(512, 2) void decoder_fused_kernel(
     const int total_tiles = tilesX * tilesY * B;
     char* my_in = in_lds + grp * IN_BYTES;
 
-    // ---- halo-image DMA, weights, fragment addresses: as conv_c64_persistent_kernel ----
-    constexpr int NPIECE = (IN_CHUNKS + 255) / 256;
-    int rel[NPIECE];
-#pragma unroll
-    for (int it = 0; it < NPIECE; ++it) {
-        const int idx = min(it * 256 + tid, IN_CHUNKS - 1);
-        const int q = idx >> 3, c = (idx & 7) ^ ((q >> 1) & 7);
-        const int yy = q / HALO_W, xx = q - yy * HALO_W;
-        rel[it] = ((yy - 1) * W + (xx - 1)) * 128 + c * 16;
-    }
-    const bool last_ok = (NPIECE - 1) * 256 + tid < IN_CHUNKS;
-    struct TC { int tx, ty, b; };
-    auto prefetch_tile = [&](const TC& c) {
-        const int ty0 = c.ty * TH, tx0 = c.tx * TW;
-        const char* xb = reinterpret_cast<const char*>(x + (size_t)c.b * H * W * 64);
-        if (ty0 >= 1 && ty0 + TH + 1 <= H && tx0 >= 1 && tx0 + TW + 1 <= W) {           // interior tile
-            const char* tb = xb + ((size_t)ty0 * W + tx0) * 128;
-#pragma unroll
-            for (int it = 0; it < NPIECE; ++it) {
-                if (it == NPIECE - 1 && !last_ok) continue;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tb + rel[it]),
-                                                 (__attribute__((address_space(3))) void*)(my_in + (it * 256 + wave * 64) * 16), 16, 0, 0);
-            }
-            return;
-        }
-#pragma unroll 1
-        for (int base = 0; base < IN_CHUNKS; base += 256) {
-            const int idx = base + tid;
-            if (idx < IN_CHUNKS) {
-                const int q = idx >> 3, cphys = idx & 7;
-                const int c = cphys ^ ((q >> 1) & 7);
-                const int yy = q / HALO_W, xx = q - yy * HALO_W;
-                const int iy = ty0 - 1 + yy, ix = tx0 - 1 + xx;
-                const void* src = (iy >= 0 && iy < H && ix >= 0 && ix < W)
-                                      ? (const void*)(xb + ((size_t)(iy * W + ix) * 128 + c * 16)) : (const void*)dec_zero_line;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)(my_in + (base + wave * 64) * 16), 16, 0, 0);
-            }
-        }
-    };
+    using Dma = HaloDma<HALO_H, HALO_W, 1>;
+    constexpr int NPIECE = Dma::NPIECE;
+    const Dma dma(W, tid);
+    auto prefetch_tile = [&](const TC& c) { dma.prefetch(x, c.b, c.ty * TH, c.tx * TW, H, W, my_in, tup_zero_line); };
 
     uint32_t poff[9][2];
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-        for (int rw = 0; rw < 2; ++rw)
-            poff[tap][rw] = lds_addr(my_in) + (uint32_t)swz128((2 * wave + rw) * HALO_W + p + (tap / 3) * HALO_W + (tap % 3), g);
-    const uint32_t wbase0 = lds_addr(w_lds) + (uint32_t)swz128(p, g), wbase1 = wbase0 ^ 64u;
-    const uint32_t wbase0h = wbase0 + 57344u, wbase1h = wbase1 + 57344u;
+    pixel_frag_offsets<3, HALO_W>(poff, my_in, wave, g, p);
+    const uint32_t wbase0 = weight_frag_base(w_lds, g, p);
 
     f32x4 acc[4][4];
     float* bias_lds = reinterpret_cast<float*>(in_lds + 2 * IN_BYTES);
@@ -116,51 +72,6 @@ __global__ __launch_bounds__(512, 2) void decoder_fused_kernel(
             const bf16_t* base = wz + dy * 1024;
             asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(zf[dy][0]) : "v"(wz_voff), "s"(base));
             asm volatile("global_load_dwordx4 %0, %1, %2 offset:64" : "=v"(zf[dy][1]) : "v"(wz_voff), "s"(base));
-        }
-    };
-
-    auto compute_tile = [&]() {
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) acc[0][ct] = __builtin_bit_cast(f32x4, lds_read_b128_asm(bias_addr + ct * 16));
-        lds_wait<0>();
-#pragma unroll
-        for (int pg = 1; pg < 4; ++pg)
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) acc[pg][ct] = acc[0][ct];
-        constexpr int NSTEPS = 18, PER = 8;
-        bf16x8 pf[3][4], wf[3][4];
-        auto load_one = [&](int step, int slot, int j) {
-            const int tap = step >> 1;
-            if (j < 4) {
-                pf[slot][j] = (step & 1) ? lds_read_b128_asm_off_x64(poff[tap][j >> 1], (j & 1) * 2048)
-                                         : lds_read_b128_asm_off(poff[tap][j >> 1], (j & 1) * 2048);
-            } else {
-                const int woff = (tap * WROWS + (j - 4) * 16) * 128;
-                wf[slot][j - 4] = woff < 57344 ? lds_read_b128_asm_off((step & 1) ? wbase1 : wbase0, woff)
-                                               : lds_read_b128_asm_off((step & 1) ? wbase1h : wbase0h, woff - 57344);
-            }
-        };
-#pragma unroll
-        for (int j = 0; j < PER; ++j) load_one(0, 0, j);
-#pragma unroll
-        for (int j = 0; j < PER; ++j) load_one(1, 1, j);
-#pragma unroll
-        for (int step = 0; step < NSTEPS; ++step) {
-            const int cur = step % 3;
-            if (step + 1 < NSTEPS) lds_wait<PER>(); else lds_wait<0>();
-            __builtin_amdgcn_sched_barrier(0);
-            int rd = 0;
-#pragma unroll
-            for (int m = 0; m < 16; ++m) {
-                if (step + 2 < NSTEPS) {
-#pragma unroll
-                    for (int j = 0; j < PER; ++j)
-                        if (j == rd && j * 16 <= m * PER) { load_one(step + 2, (step + 2) % 3, j); ++rd; }
-                }
-                const int pg = m / 4, ct = m % 4;
-                acc[pg][ct] = mfma16x16x32(wf[cur][ct], pf[cur][pg], acc[pg][ct]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
         }
     };
 
@@ -250,49 +161,21 @@ __global__ __launch_bounds__(512, 2) void decoder_fused_kernel(
     };
     constexpr int NSTORES = 10;                       // store instructions per wave in store_tile
 
-    int first, first0, stride, limit;
-    if ((gridDim.x & 7) == 0) {
-        const int per = gridDim.x >> 3, band = (total_tiles + 7) >> 3, start = (blockIdx.x & 7) * band;
-        limit = min(total_tiles, start + band);
-        first0 = start + (blockIdx.x >> 3);
-        first = first0 + grp * per;
-        stride = 2 * per;
-    } else {
-        limit = total_tiles;
-        first0 = blockIdx.x;
-        first = first0 + grp * gridDim.x;
-        stride = 2 * gridDim.x;
-    }
-    const int my_count = first < limit ? (limit - first + stride - 1) / stride : 0;
-    const int cnt0 = first0 < limit ? (limit - first0 + stride - 1) / stride : 0;
-    const int nphases = 2 * cnt0 + 1;
-    TC c_first;
-    { const int t = first / tilesX; c_first.tx = first - t * tilesX; c_first.ty = t % tilesY; c_first.b = t / tilesY; }
-    const int step_x = stride % tilesX, step_y = (stride / tilesX) % tilesY, step_b = stride / (tilesX * tilesY);
-    auto advance = [&](TC& c) {
-        c.tx += step_x;
-        if (c.tx >= tilesX) { c.tx -= tilesX; ++c.ty; }
-        c.ty += step_y; c.b += step_b;
-        if (c.ty >= tilesY) { c.ty -= tilesY; ++c.b; }
-    };
+    const TileWalk walk(total_tiles, tilesX, tilesY, grp, true);
+    const int my_count = walk.my_count, nphases = walk.nphases;
+    const TC c_first = walk.first;
 
-    for (int idx = threadIdx.x; idx < WCHUNKS; idx += 512) {
-        const int row = idx >> 3, c = idx & 7;
-        *reinterpret_cast<u32x4*>(w_lds + swz128(row, c)) = *reinterpret_cast<const u32x4*>(wp + (size_t)idx * 8);
-    }
-    if (threadIdx.x < 64) {                          // [g][ct][e]
-        const int gg = threadIdx.x >> 4, ct = (threadIdx.x >> 2) & 3, e = threadIdx.x & 3;
-        bias_lds[threadIdx.x] = bias[gg * 16 + ct * 4 + e];
-    }
+    stage_weights<4, 9>(w_lds, wp);
+    stage_bias<4, false>(bias_lds, bias, 0, 64);
     if (grp == 0 && my_count > 0) prefetch_tile(c_first);
     __syncthreads();
     TC c_done = c_first, c_next = c_first;
-    if (grp == 0) advance(c_next);
+    if (grp == 0) walk.advance(c_next);
 
     for (int ph = 0; ph < nphases; ++ph) {
         const int k = ph >> 1;
         if ((ph & 1) == grp) {
-            if (k < my_count) compute_tile();
+            if (k < my_count) k_loop<4, 9>(acc, poff, wbase0, bias_addr);
         } else {
             const int done = grp == 0 ? k : k - 1;
             const int nxt = done + 1;
@@ -311,7 +194,7 @@ __global__ __launch_bounds__(512, 2) void decoder_fused_kernel(
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             c_done = c_next;
-            advance(c_next);
+            walk.advance(c_next);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
