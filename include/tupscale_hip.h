@@ -427,6 +427,27 @@ int tup_u8hwc_to_f32chw(const void* src, float* dst, int B, int H, int W, int sw
  * in inference.py:123-124): src fp32 [B][3][H][W] -> dst u8 [B][H][W][3], truncating.  swap_rb = 1: BGR output. */
 int tup_f32chw_to_u8hwc(const float* src, void* dst, int B, int H, int W, int swap_rb, void* stream);
 
+/* NV12 video frames (YUV 4:2:0, 8 bit; no counterpart in the reference, which reads RGB files and screen grabs).
+ * Layout: y u8 [B][H][W]; uv u8 [B][H/2][W/2][2] = (Cb, Cr) pairs.  Each plane has its own row pitch and batch stride IN BYTES
+ * (pitch >= W), so a pitched decoder surface, or the usual single allocation [B][3H/2][pitch] with Y on top and UV below, is
+ * passed as it is.  matrix: 0 = BT.601, 1 = BT.709; full_range: 0 = Y 16..235 / chroma 16..240, 1 = 0..255.
+ * Chroma siting "left" (the H.264 / HEVC default): sample (j, i) sits at luma column 2i, halfway between luma rows 2j and 2j+1.
+ * Both directions are integer arithmetic on bytes and bit-exact with the definition in DESIGN.md section 3 ("NV12 frames"):
+ *   decode  chroma upsampled without intermediate rounding (vertical C[j-1] + 3 C[j] | 3 C[j] + C[j+1], horizontal 2 v[i] |
+ *           v[i] + v[i+1], indices clamped to the plane), 16.16 matrix, R = clip8((cy (Y - yoff) + 32768 + rv cr) >> 16), ...;
+ *           dst fp32 [B][3][H][W] = byte / 255, i.e. exactly "convert to RGB24, then tup_u8hwc_to_f32chw";
+ *   encode  src fp32 [B][3][H][W] -> bytes as tup_f32chw_to_u8hwc makes them (truncating, NaN -> 0),
+ *           Y = clip8((ry R + gy G + by B + (yoff << 16) + 32768) >> 16), chroma from the [1 2 1] x [1 1] filter around
+ *           column 2i of rows 2j, 2j+1 (columns clamped to the image).  Bytes between W and the pitch are left untouched.
+ * One launch each, no allocation, synchronisation or host read (capturable into a hipGraph).  B <= 65535; an empty shape
+ * returns 0; odd H or W, a pitch below W, or an unknown matrix / full_range returns hipErrorInvalidValue before any launch. */
+int tup_nv12_to_f32chw(const void* y, const void* uv, long long y_batch_stride, int y_pitch,
+                       long long uv_batch_stride, int uv_pitch, float* dst,
+                       int B, int H, int W, int matrix, int full_range, void* stream);
+int tup_f32chw_to_nv12(const float* src, void* y, void* uv, long long y_batch_stride, int y_pitch,
+                       long long uv_batch_stride, int uv_pitch,
+                       int B, int H, int W, int matrix, int full_range, void* stream);
+
 /* ---- WindowTransformer plugin (models/WindowTransformer/model.py): the FastTransformer window
  * block at embedding width 128 / 8 heads ---- */
 

@@ -54,6 +54,9 @@ GUARDED = [
     # no counted vmcnt here, but the kernel lives on three waves per SIMD with every row's loads requested a row ahead: scratch reloads
     # queue behind those loads (seen in round 3).  All four instances (RESIZE x PARTS) sit at 133-152 registers of 168
     ("tail_stream.hip", ["tail_stream_r2_kernel"]),
+    # no counted hand-off: byte work at 13.5 B of memory traffic per pixel whose small per-lane tables (3 x 3 chroma pairs, 2 x 3 x 5
+    # quantised bytes) are indexed by unrolled loops; a build that indexes them dynamically puts them in scratch
+    ("image_io.hip", ["nv12_to_f32chw_kernel", "f32chw_to_nv12_kernel"]),
 ]
 # diagnostic template instantiations, never launched by the product path: fused_qkv_attn_kernel<PROJ, MLP, STAMPS = true>, the
 # timing ablations fused_mlp_v2_kernel<ABL != 0>

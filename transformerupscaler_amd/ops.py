@@ -1049,6 +1049,119 @@ def tensor_to_frames(x, bgr=False):
     return out
 
 
+# ---- NV12 video frames (YUV 4:2:0: what a decoder hands over and an encoder takes; definition in DESIGN 3, "NV12 frames") ----
+_NV12_MATRIX = {"bt601": 0, "bt709": 1}
+
+
+def _nv12_matrix(op, matrix):
+    if matrix not in _NV12_MATRIX:
+        raise ValueError(f"{op}: matrix must be 'bt601' or 'bt709', got {matrix!r}")
+    return _NV12_MATRIX[matrix]
+
+
+def _nv12_on_gpu(op, t, name):
+    if not t.is_cuda:
+        raise ValueError(f"{op}: {name} lives on {t.device}; the HIP path needs a GPU tensor (no CPU fallback)")
+    if t.device.index != _cur_dev():
+        # every launch goes to the CURRENT device's stream: a tensor of another device would be a wild pointer there
+        raise ValueError(f"{op}: {name} lives on {t.device} but the current device is cuda:{_cur_dev()}")
+
+
+def _nv12_plane(op, t, name, tail):
+    """A plane of an NV12 surface as (data_ptr, B, rows, row bytes, pitch, batch stride): uint8 on the current GPU, [B] + rows + `tail`
+    dimensions with the tail contiguous and one stride per row and per frame, which is what a slice of a pitched surface has."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        raise TypeError(f"{op}: {name} must be a uint8 tensor, got {getattr(t, 'dtype', type(t))}")
+    if t.dim() not in (1 + tail, 2 + tail):
+        raise ValueError(f"{op}: {name} must have {1 + tail} dimensions (one frame) or {2 + tail} (a batch), got shape {tuple(t.shape)}")
+    _nv12_on_gpu(op, t, name)
+    if t.dim() == 1 + tail:
+        t = t.unsqueeze(0)
+    B, rows = int(t.shape[0]), int(t.shape[1])
+    width = 1
+    for n in t.shape[2:]:
+        width *= int(n)
+    if tail == 2 and t.shape[3] != 2:
+        raise ValueError(f"{op}: {name} must end in (Cb, Cr) pairs [.., H/2, W/2, 2], got shape {tuple(t.shape)}")
+    st = t.stride()
+    inner = (st[2] == 1 or width <= 1) if tail == 1 else ((st[3] == 1 and st[2] == 2) or width <= 2)
+    if not inner:
+        raise ValueError(f"{op}: {name}: the innermost dimension{'s' if tail == 2 else ''} must be contiguous, got strides {tuple(st)}")
+    pitch = int(st[1]) if rows > 1 else width
+    if pitch < width or pitch >= 2 ** 31:
+        raise ValueError(f"{op}: {name}: row stride {pitch} must be at least the row's {width} bytes (and below 2^31)")
+    return t.data_ptr(), B, rows, width, pitch, (int(st[0]) if B > 1 else 0)
+
+
+def _nv12_geometry(op, y, uv):
+    yp, B, H, W, ypitch, ybs = _nv12_plane(op, y, "y", 1)
+    up, Bu, h2, w2x2, upitch, ubs = _nv12_plane(op, uv, "uv", 2)
+    if H % 2 or W % 2:
+        raise ValueError(f"{op}: y is {H} x {W}; NV12 needs an even height and width")
+    if (Bu, h2, w2x2) != (B, H // 2, W):
+        raise ValueError(f"{op}: uv must be [{B}][{H // 2}][{W // 2}][2] for a y of [{B}][{H}][{W}], got {tuple(uv.shape)}")
+    if B > 65535:
+        raise ValueError(f"{op}: {B} frames in one launch (at most 65535)")
+    return yp, up, ybs, ypitch, ubs, upitch, B, H, W
+
+
+def nv12_planes(buf, H, W):
+    """The (y, uv) views of single-buffer NV12 frames: buf uint8 [3H/2 or more][pitch] or [B][...][pitch] with the Y rows on top and
+    the rows of (Cb, Cr) pairs below them -> y [..][H][W], uv [..][H/2][W/2][2].  No copy; rows beyond 3H/2 and bytes beyond W are
+    padding."""
+    H, W = int(H), int(W)
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"nv12_planes: H = {H} and W = {W} must be even and at least 2")
+    if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8:
+        raise TypeError(f"nv12_planes: buf must be a uint8 tensor, got {getattr(buf, 'dtype', type(buf))}")
+    if buf.dim() not in (2, 3) or buf.shape[-2] < H + H // 2 or buf.shape[-1] < W:
+        raise ValueError(f"nv12_planes: buf must be [{H + H // 2}][>= {W}] (or a batch of those), got shape {tuple(buf.shape)}")
+    if buf.stride(-1) != 1:
+        raise ValueError(f"nv12_planes: buf: the innermost dimension must be contiguous, got strides {tuple(buf.stride())}")
+    return buf[..., :H, :W], buf[..., H:H + H // 2, :W].unflatten(-1, (W // 2, 2))
+
+
+def nv12_to_tensor(y, uv, matrix="bt709", full_range=False):
+    """NV12 frames on the GPU -> fp32 [B][3][H][W] RGB in [0, 1], bit-exact "convert to RGB24, then ToTensor" under the integer
+    definition of DESIGN 3.  y uint8 [B][H][W] (or [H][W]), uv uint8 [B][H/2][W/2][2] (or [H/2][W/2][2]) = (Cb, Cr), chroma sited
+    left; any views with contiguous rows and uniform row / batch strides, e.g. the two halves of `nv12_planes`."""
+    m = _nv12_matrix("nv12_to_tensor", matrix)
+    yp, up, ybs, ypitch, ubs, upitch, B, H, W = _nv12_geometry("nv12_to_tensor", y, uv)
+    out = torch.empty((B, 3, H, W), dtype=F32, device=y.device)
+    _lib.call("tup_nv12_to_f32chw", yp, up, ybs, ypitch, ubs, upitch, out.data_ptr(), B, H, W, m, int(bool(full_range)), _stream())
+    return out
+
+
+def tensor_to_nv12(x, matrix="bt709", full_range=False, out=None):
+    """fp32 [B][3][H][W] (or [3][H][W]) -> NV12 frames (y uint8 [B][H][W], uv uint8 [B][H/2][W/2][2]): bytes as `tensor_to_frames`
+    makes them, then the integer matrix and the [1 2 1] x [1 1] chroma filter of DESIGN 3.  out=(y, uv) writes into such views
+    (e.g. of a pitched surface; padding bytes are left alone)."""
+    m = _nv12_matrix("tensor_to_nv12", matrix)
+    if not isinstance(x, torch.Tensor) or x.dtype != F32:
+        raise TypeError(f"tensor_to_nv12: x must be a float32 tensor, got {getattr(x, 'dtype', type(x))}")
+    if x.dim() == 3:
+        x = x.unsqueeze(0)
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"tensor_to_nv12: x must be [B][3][H][W], got shape {tuple(x.shape)}")
+    B, _, H, W = (int(v) for v in x.shape)
+    if H % 2 or W % 2:
+        raise ValueError(f"tensor_to_nv12: x is {H} x {W}; NV12 needs an even height and width")
+    _nv12_on_gpu("tensor_to_nv12", x, "x")
+    xp = _chk(x, F32, None, "tensor_to_nv12: x")
+    if out is None:
+        y = torch.empty((B, H, W), dtype=torch.uint8, device=x.device)
+        uv = torch.empty((B, H // 2, W // 2, 2), dtype=torch.uint8, device=x.device)
+    else:
+        y, uv = out
+    yp, up, ybs, ypitch, ubs, upitch, Bo, Ho, Wo = _nv12_geometry("tensor_to_nv12: out", y, uv)
+    if (Bo, Ho, Wo) != (B, H, W):
+        raise ValueError(f"tensor_to_nv12: out is for [{Bo}][{Ho}][{Wo}] frames, x is [{B}][3][{H}][{W}]")
+    if B > 1 and (ybs < (H - 1) * ypitch + W or ubs < (H // 2 - 1) * upitch + W):
+        raise ValueError("tensor_to_nv12: out: the frames of a plane overlap (batch stride below one frame)")
+    _lib.call("tup_f32chw_to_nv12", xp, yp, up, ybs, ypitch, ubs, upitch, B, H, W, m, int(bool(full_range)), _stream())
+    return y, uv
+
+
 # ---- branch A in training through its composition (csrc/branch_a_train.hip), r = 2 ----
 def bra_compose(wu, bu, w3):
     """Composed weights of (Conv2d(64, 256, 3) + PixelShuffle(2) + Conv2d(64, 3, 3, bias=False)) in the kernels' layouts:
