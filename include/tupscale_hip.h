@@ -649,6 +649,23 @@ int tup_adam_step_ema(const void* segs, const int* chunks, int nchunks, const vo
 int tup_patch_pairs(const void* recs, int B, int P, int p, const int* xmin, const int* xsize, const int* k, int ksize,
                     float* hr, float* lr, void* stream);
 
+/* Training degradations of a whole batch in one launch (data.PatchSampler(degrade=...); csrc/degrade.hip).  in / out fp32
+ * [B][3][H][W], any H, W >= 1; recs: device array [B] of 32-byte records {int taps[4]; int noise_amp; uint32_t noise_seed; int quality;
+ * int flags}.  Per record, in integers, bit-exact against tests/_degrade_ref.py:
+ *   u = clip(floor(v * 255.0f + 0.5f), 0, 255), both operations rounded to fp32;
+ *   blur: 7 symmetric taps {k3 k2 k1 k0 k1 k2 k3} in 22-bit fixed point (k0 + 2 (k1 + k2 + k3) == 1 << 22), the horizontal pass and
+ *     then the vertical pass, each clip8((sum k u + (1 << 21)) >> 22), indices clamped to the image; {1 << 22, 0, 0, 0} is the identity;
+ *   noise: h = drop_hash(noise_seed, e), e = (y W + x) 3 + c, or y W + x with flags & 1; n = the sum of h's four bytes - 510;
+ *     u = clip(u + ((n noise_amp + (1 << 15)) >> 16), 0, 255); noise_amp = 0 is off;
+ *   JPEG round trip, quality in 1..100 (0 is off): baseline 4:4:4, Annex K tables scaled as jpeg_set_quality does, the image padded
+ *     to multiples of 8 by replication, libjpeg's 16-bit RGB <-> YCbCr and its slow integer DCT (jfdctint / jidctint) both ways,
+ *     quantised as sign(c) ((|c| + 4 t) / (8 t)); what Pillow's save(quality=q, subsampling=0) and open().convert("RGB") return;
+ *   out = (float)u / 255.0f.
+ * One workgroup per 32 x 32 tile and sample, everything between the load and the store in LDS; one writer per output element, no
+ * atomics, no workspace.  A quality outside 0..100 is treated as 0 and other flag bits are ignored: validate on the host.
+ * A null pointer, B, H or W <= 0, B > 65535, or out overlapping in (a tile reads its neighbours): hipErrorInvalidValue. */
+int tup_degrade_lr(const float* in, const void* recs, int B, int H, int W, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,12 @@ What differs from the reference driver:
   ``--patches_per_epoch`` sets the epoch length (default: the whole-frame dataset's).  Sample g of a run is a function of
   ``(--seed, g)`` alone, so resumed runs and ranks need no generator state.  ``--pairs`` does not apply; ResidualTransformer (fixed
   720x1280 input) cannot train on patches.  The ``--json`` record gains ``patch``.
+* ``--degrade`` (with ``--patch_size``) passes every LR patch through blur, noise and a JPEG round trip after the clean downscale
+  (``transformerupscaler_amd.data.DegradeSpec``, one ``ops.degrade`` launch per distinct scale; HR is untouched): with probability
+  0.5 a Gaussian blur of sigma 0.2-1.5 pixels, with 0.5 noise of sigma 1-10 in 8-bit units (grey in 0.4 of those cases), with 0.7
+  a 4:4:4 JPEG round trip at quality 30-95.  ``--degrade_blur LO,HI``, ``--degrade_noise LO,HI``, ``--degrade_jpeg LO,HI`` and
+  ``--degrade_prob PB,PN,PJ`` set the ranges and the three probabilities, and each implies ``--degrade``.  The record of sample g
+  is a function of ``(--seed, g)``, from a stream of its own.  The ``--json`` record gains ``degrade`` (the spec).
 * ``--ema_decay D`` keeps an exponential moving average of the weights inside the fused optimizer step (``--ema_warmup``: timm's
   warm-up of the decay); a step skipped by ``--skip_nonfinite`` does not move it.  Every checkpoint then also writes
   ``<checkpoint_dir>/ema/model_epoch_<N>.pth`` (the weight file's format: ``ab_test.py --checkpoint_dir_a .../ema`` loads it) and a
@@ -98,6 +104,11 @@ def build_parser():
     p.add_argument("--patch_scales", type=str, default="2,3,4,6", help="Scales the patches are drawn from (with --patch_size)")
     p.add_argument("--no_augment", action="store_true", help="No flip / rotate variants of the patches (with --patch_size)")
     p.add_argument("--patches_per_epoch", type=int, default=None, help="Samples per epoch with --patch_size (default: the dataset's)")
+    p.add_argument("--degrade", action="store_true", help="Degrade the LR patches: blur, noise, JPEG round trip (with --patch_size)")
+    p.add_argument("--degrade_blur", type=str, default=None, help="Blur sigma range LO,HI in pixels, at most 3 (default 0.2,1.5; implies --degrade)")
+    p.add_argument("--degrade_noise", type=str, default=None, help="Noise sigma range LO,HI in 8-bit units (default 1,10; implies --degrade)")
+    p.add_argument("--degrade_jpeg", type=str, default=None, help="JPEG quality range LO,HI in 1..100 (default 30,95; implies --degrade)")
+    p.add_argument("--degrade_prob", type=str, default=None, help="Probabilities PB,PN,PJ of blur, noise, JPEG (default 0.5,0.5,0.7; implies --degrade)")
     p.add_argument("--ema_decay", type=float, default=None, help="Keep an exponential moving average of the weights with this decay")
     p.add_argument("--ema_warmup", action="store_true", help="Warm the EMA decay up: min(decay, (1 + n) / (10 + n)) (with --ema_decay)")
     p.add_argument("--val_dir", type=str, default=None, help="Directory of held-out images (.png) scored after an epoch")
@@ -142,7 +153,10 @@ def patch_options(args):
     if args.patch_size is None:
         if args.no_augment or args.patches_per_epoch is not None or args.patch_scales != "2,3,4,6":
             sys.exit("train.py: --patch_scales, --no_augment and --patches_per_epoch need --patch_size")
+        if degrade_requested(args):
+            sys.exit("train.py: --degrade, --degrade_blur, --degrade_noise, --degrade_jpeg and --degrade_prob need --patch_size")
         return None
+    degrade_options(args)
     if args.pairs:
         sys.exit("train.py: --pairs does not apply with --patch_size (patches are square: use --patch_scales)")
     if args.patch_size < 1:
@@ -163,6 +177,43 @@ def patch_options(args):
     if bad or not scales or len(set(scales)) != len(scales):
         sys.exit(f"train.py: --patch_scales {args.patch_scales!r}: --model {args.model} trains on distinct scales out of {list(valid)}")
     return args.patch_size, scales
+
+
+def degrade_requested(args):
+    return bool(args.degrade or args.degrade_blur or args.degrade_noise or args.degrade_jpeg or args.degrade_prob)
+
+
+def degrade_options(args):
+    """The `data.DegradeSpec` keywords of the --degrade* options (an option that is not given keeps the spec's default), None
+    without any of them.  Parsed and checked here, before anything touches the GPU; `patch_options` calls it."""
+    if not degrade_requested(args):
+        return None
+
+    def numbers(flag, text, count, kind):
+        try:
+            values = tuple(kind(v) for v in text.split(","))
+        except ValueError:
+            values = ()
+        if len(values) != count:
+            sys.exit(f"train.py: {flag} {text!r}: expected {count} {'integers' if kind is int else 'numbers'} separated by commas")
+        return values
+    kw = {}
+    if args.degrade_blur:
+        kw["blur_sigma"] = numbers("--degrade_blur", args.degrade_blur, 2, float)
+    if args.degrade_noise:
+        kw["noise_sigma"] = numbers("--degrade_noise", args.degrade_noise, 2, float)
+    if args.degrade_jpeg:
+        kw["jpeg_quality"] = numbers("--degrade_jpeg", args.degrade_jpeg, 2, int)
+    if args.degrade_prob:
+        kw["blur_prob"], kw["noise_prob"], kw["jpeg_prob"] = numbers("--degrade_prob", args.degrade_prob, 3, float)
+    from transformerupscaler_amd.data import DegradeSpec
+    try:
+        DegradeSpec(**kw)
+    except ValueError as e:
+        flag = {"blur_sigma": "--degrade_blur", "noise_sigma": "--degrade_noise", "jpeg_quality": "--degrade_jpeg"}
+        name = next((f for k, f in flag.items() if k in str(e)), "--degrade_prob")
+        sys.exit(f"train.py: {name}: {e}")
+    return kw
 
 
 def val_options(args):
@@ -197,12 +248,13 @@ def run(args):
     if args.batch_size < 1:
         sys.exit("train.py: --batch_size must be >= 1")
     patch = patch_options(args)
+    degrade_kw = degrade_options(args) if patch is not None else None
     validating = val_options(args)
     ema = args.ema_decay is not None
     import torch
 
     from transformerupscaler_amd import harness, ops
-    from transformerupscaler_amd.data import SCALE_PAIRS, PairDataset, PatchSampler, parse_pairs, sample_plan
+    from transformerupscaler_amd.data import SCALE_PAIRS, DegradeSpec, PairDataset, PatchSampler, parse_pairs, sample_plan
 
     val_pairs = None
     if validating:
@@ -276,7 +328,8 @@ def run(args):
         pairs = None
         try:
             dataset = PatchSampler(args.data_dir, patch=patch[0], scales=patch[1], augment=not args.no_augment, seed=args.seed,
-                                   samples_per_epoch=args.patches_per_epoch, cache_bytes=cache_bytes, device=device)
+                                   samples_per_epoch=args.patches_per_epoch, cache_bytes=cache_bytes, device=device,
+                                   degrade=None if degrade_kw is None else DegradeSpec(**degrade_kw))
         except ValueError as e:
             sys.exit(f"train.py: {e}")
     else:
@@ -287,7 +340,8 @@ def run(args):
         from transformerupscaler_amd.losses import QualityLoss
         criterion = QualityLoss(l1=args.l1, mse=args.mse, ssim=args.ssim)
     what = (f"{len(pairs)} scale pairs" if patch is None else
-            f"{patch[0]}x{patch[0]} patches at scales {list(patch[1])}" + ("" if dataset.augment else ", no augmentation"))
+            f"{patch[0]}x{patch[0]} patches at scales {list(patch[1])}" + ("" if dataset.augment else ", no augmentation")
+            + ("" if dataset.degrade is None else f", LR degraded by {dataset.degrade}"))
     say(f"{len(dataset)} samples from {len(dataset.files)} images, {what}; loss {'L1' if criterion is None else criterion}")
     if validating:
         say(f"Validation: {len(val_set)} samples from {len(val_set.files)} images of {args.val_dir}, {len(val_pairs)} scale pairs, "
@@ -301,6 +355,8 @@ def run(args):
     if patch is not None:
         record["patch"] = {"size": patch[0], "scales": list(patch[1]), "augment": dataset.augment,
                            "samples_per_epoch": dataset.samples_per_epoch}
+        if dataset.degrade is not None:
+            record["degrade"] = dataset.degrade.as_dict()
     if validating:
         record["val"] = []
     if args.keep_best:

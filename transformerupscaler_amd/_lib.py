@@ -80,6 +80,8 @@ SIGNATURES = {
     "tup_adam_step_ema": [P, P, I, P, P],
     # patch training samples (csrc/patch_pairs.hip)
     "tup_patch_pairs": [P, I, I, I, P, P, P, I, P, P, P],
+    # training degradations (csrc/degrade.hip)
+    "tup_degrade_lr": [P, P, I, I, I, P, P],
     "tup_l1_loss_partial": [P, P, P, c_longlong, I, P],
     "tup_l1_loss_bwd": [P, P, P, P, c_longlong, P],
     "tup_u8hwc_to_f32chw": [P, P, I, I, I, I, P],

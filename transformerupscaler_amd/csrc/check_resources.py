@@ -57,6 +57,8 @@ GUARDED = [
     # no counted hand-off: byte work at 13.5 B of memory traffic per pixel whose small per-lane tables (3 x 3 chroma pairs, 2 x 3 x 5
     # quantised bytes) are indexed by unrolled loops; a build that indexes them dynamically puts them in scratch
     ("image_io.hip", ["nv12_to_f32chw_kernel", "f32chw_to_nv12_kernel"]),
+    # no counted hand-off: four 8-point DCT passes hold 8 values a lane in unrolled arrays; a build that indexes them dynamically spills
+    ("degrade.hip", ["degrade_lr_kernel"]),
 ]
 # diagnostic template instantiations, never launched by the product path: fused_qkv_attn_kernel<PROJ, MLP, STAMPS = true>, the
 # timing ablations fused_mlp_v2_kernel<ABL != 0>

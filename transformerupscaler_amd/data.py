@@ -12,7 +12,8 @@ resizes per sample in DataLoader workers.  Only the local directory is read: the
 nothing here opens a connection.  The table and the sample plan are the ones `ab_test.py` evaluates on (that driver keeps its own statement of them; a test checks that the two agree).
 
 `PatchSampler` is the other way to train on the same directory: random square HR crops with the 8 flip / rotate variants and
-their Pillow-exact LR counterparts, a whole batch per scale in one ``ops.patch_pairs`` launch (csrc/patch_pairs.hip).
+their Pillow-exact LR counterparts, a whole batch per scale in one ``ops.patch_pairs`` launch (csrc/patch_pairs.hip).  With a
+`DegradeSpec` its LR patches also pass through blur, noise and a JPEG round trip (``ops.degrade``, csrc/degrade.hip).
 """
 from __future__ import annotations
 
@@ -153,6 +154,67 @@ PATCH_SCALES = (2, 3, 4, 6)
 MAX_PATCH_SCALE = 8          # the LDS window of csrc/patch_pairs.hip
 
 
+DEGRADE_STREAM = 0x44454752     # "DEGR": the third word of the seed of a sample's degradation stream
+
+
+class DegradeSpec:
+    """What `PatchSampler(degrade=...)` does to an LR patch after the clean downscale, BSRGAN / Real-ESRGAN style: with probability
+    `blur_prob` a Gaussian blur of sigma uniform in `blur_sigma` (pixels, at most 3.0: the kernel's radius is 3), with `noise_prob`
+    noise of standard deviation uniform in `noise_sigma` (8-bit units; with `grey_noise_prob` of those cases one value per pixel
+    instead of one per channel), with `jpeg_prob` a 4:4:4 JPEG round trip at a quality uniform over the integers of `jpeg_quality`.
+    The stages run in that order (``ops.degrade``).  Validated here; the defaults are the ones ``train.py --degrade`` uses."""
+
+    FIELDS = ("blur_prob", "blur_sigma", "noise_prob", "noise_sigma", "grey_noise_prob", "jpeg_prob", "jpeg_quality")
+
+    def __init__(self, blur_prob=0.5, blur_sigma=(0.2, 1.5), noise_prob=0.5, noise_sigma=(1.0, 10.0), grey_noise_prob=0.4,
+                 jpeg_prob=0.7, jpeg_quality=(30, 95)):
+        from . import ops
+        for name, v in (("blur_prob", blur_prob), ("noise_prob", noise_prob), ("grey_noise_prob", grey_noise_prob), ("jpeg_prob", jpeg_prob)):
+            try:
+                ok = 0.0 <= float(v) <= 1.0
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"DegradeSpec: {name} = {v!r} must be a probability in [0, 1]")
+            setattr(self, name, float(v))
+        max_noise = ops.DEGRADE_MAX_NOISE_AMP * 147.80054 / 65536
+        for name, v, top in (("blur_sigma", blur_sigma, ops.DEGRADE_MAX_BLUR_SIGMA), ("noise_sigma", noise_sigma, max_noise)):
+            try:
+                lo, hi = (float(t) for t in v)
+                ok = 0.0 <= lo <= hi <= top
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"DegradeSpec: {name} = {v!r} must be (lo, hi) with 0 <= lo <= hi <= {top:g}")
+            setattr(self, name, (lo, hi))
+        try:
+            lo, hi = (int(t) for t in jpeg_quality)
+            ok = (lo, hi) == tuple(jpeg_quality) and 1 <= lo <= hi <= 100
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"DegradeSpec: jpeg_quality = {jpeg_quality!r} must be integers (lo, hi) with 1 <= lo <= hi <= 100")
+        self.jpeg_quality = (lo, hi)
+
+    def as_dict(self):
+        return {k: (list(v) if isinstance(v, tuple) else v) for k, v in ((k, getattr(self, k)) for k in self.FIELDS)}
+
+    def __repr__(self):
+        return "DegradeSpec(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.FIELDS) + ")"
+
+    def draw(self, rng):
+        """One ``ops.degrade`` record from a numpy Generator.  Eight values are drawn whatever they decide (blur: coin, sigma; noise:
+        coin, sigma, grey coin, seed; JPEG: coin, quality), so one stage's setting never moves another's."""
+        from . import ops
+        blur_on, blur_sigma = rng.random() < self.blur_prob, float(rng.uniform(*self.blur_sigma))
+        noise_on, noise_sigma = rng.random() < self.noise_prob, float(rng.uniform(*self.noise_sigma))
+        grey, seed = rng.random() < self.grey_noise_prob, int(rng.integers(1 << 32))
+        jpeg_on, quality = rng.random() < self.jpeg_prob, int(rng.integers(self.jpeg_quality[0], self.jpeg_quality[1] + 1))
+        amp = ops.noise_amp(noise_sigma) if noise_on else 0
+        return (ops.blur_taps(blur_sigma) if blur_on else ops.DEGRADE_TAPS_OFF, amp, seed if amp else 0,
+                quality if jpeg_on else 0, ops.DEGRADE_GREY_NOISE if amp and grey else 0)
+
+
 class PatchSampler(FrameCache):
     """Random-crop training samples: ``draw(g)`` says what sample `g` is, ``batch(indices)`` builds a list of them on the GPU.
 
@@ -164,10 +226,13 @@ class PatchSampler(FrameCache):
 
     The sample itself is ``ops.patch_pairs``'s: HR = ToTensor of the transformed crop, LR = ToTensor of its Pillow BILINEAR resize to
     ``patch x patch``.  `samples_per_epoch` defaults to `PairDataset`'s length for the same directory, ``min(200, 10 * n_png)``, so
-    epochs, checkpoints and schedules count what they count on whole frames."""
+    epochs, checkpoints and schedules count what they count on whole frames.
+
+    With ``degrade=DegradeSpec(...)`` the LR patch then passes through ``ops.degrade`` under the record ``draw_degrade(g)``, drawn
+    from a stream of its own, ``default_rng([seed, g, DEGRADE_STREAM])``: ``draw(g)`` is what it is without it, and HR is untouched."""
 
     def __init__(self, image_dir, patch=96, scales=PATCH_SCALES, augment=True, seed=0, samples_per_epoch=None,
-                 cache_bytes=DEFAULT_CACHE_BYTES, device="cuda"):
+                 cache_bytes=DEFAULT_CACHE_BYTES, device="cuda", degrade=None):
         if not image_dir:
             raise ValueError("PatchSampler needs a directory of .png images (data_dir); the reference's online dataset is not built")
         if not os.path.isdir(image_dir):
@@ -197,6 +262,9 @@ class PatchSampler(FrameCache):
                                  f"{need} x {need} pixels (patch {self.patch} x scale {s})")
         self.augment = bool(augment)
         self.seed = int(seed)
+        if degrade is not None and not isinstance(degrade, DegradeSpec):
+            raise ValueError(f"PatchSampler: degrade = {degrade!r} must be a DegradeSpec or None")
+        self.degrade = degrade
         if samples_per_epoch is None:
             samples_per_epoch = len(sample_plan(len(self.files)))
         self.samples_per_epoch = int(samples_per_epoch)
@@ -224,10 +292,22 @@ class PatchSampler(FrameCache):
         op = int(rng.integers(8)) if self.augment else 0
         return image, scale, y0, x0, op
 
+    def draw_degrade(self, g):
+        """The ``ops.degrade`` record (taps, noise_amp, noise_seed, quality, flags) of global sample g; None without a spec."""
+        import numpy as np
+        g = int(g)
+        if g < 0:
+            raise IndexError(g)
+        if self.degrade is None:
+            return None
+        return self.degrade.draw(np.random.default_rng([self.seed, g, DEGRADE_STREAM]))
+
     def batch(self, indices):
         """(lr_list, hr_list) of the global samples `indices`, in that order: fp32 ``[3][patch][patch]`` and
-        ``[3][patch * scale][patch * scale]`` views of one batched output per distinct scale (one launch each)."""
+        ``[3][patch * scale][patch * scale]`` views of one batched output per distinct scale (one launch each, and one
+        ``ops.degrade`` launch each with a `degrade` spec)."""
         from . import ops
+        indices = list(indices)
         draws = [self.draw(g) for g in indices]
         by_scale = {}
         for pos, d in enumerate(draws):
@@ -237,6 +317,8 @@ class PatchSampler(FrameCache):
             frames = [self.frame(draws[pos][0]) for pos in members]
             boxes = [draws[pos][2:5] for pos in members]
             lr, hr = ops.patch_pairs(frames, boxes, self.patch, scale)
+            if self.degrade is not None:
+                lr = ops.degrade(lr, [self.draw_degrade(indices[pos]) for pos in members])
             for j, pos in enumerate(members):
                 lr_list[pos], hr_list[pos] = lr[j], hr[j]
         return lr_list, hr_list

@@ -1320,6 +1320,119 @@ def patch_pairs(frames, boxes, p, scale, out=None):
     return lr, hr
 
 
+# ---- training degradations: blur, noise and a JPEG round trip on bytes in one launch (csrc/degrade.hip) ----
+_DEGRADE_REC = struct.Struct("<iiiiiIii")       # DegradeRec: taps[4], noise_amp, noise_seed, quality, flags
+DEGRADE_PRECISION_BITS = 32 - 8 - 2             # Pillow's fixed point for 8-bit images
+DEGRADE_TAPS_OFF = (1 << DEGRADE_PRECISION_BITS, 0, 0, 0)
+DEGRADE_GREY_NOISE = 1                          # flags & 1: one noise value per pixel instead of one per channel
+DEGRADE_OFF = (DEGRADE_TAPS_OFF, 0, 0, 0, 0)    # the record that changes nothing but the quantisation to bytes
+DEGRADE_MAX_BLUR_SIGMA = 3.0                    # beyond it the radius-3 truncation is a box, not a Gaussian
+DEGRADE_MAX_NOISE_AMP = 1 << 20                 # 510 * amp + 2^15 stays inside 32 bits (sigma up to ~2300)
+_NOISE_UNIT = 147.80054                         # sqrt(4 * (256^2 - 1) / 12): the standard deviation of a sum of four uniform bytes
+_DEGRADE_STAGERS = {}
+
+
+def blur_taps(sigma):
+    """(k0, k1, k2, k3) of a Gaussian of `sigma` pixels truncated at radius 3, normalised in float64 and rounded to 22-bit fixed
+    point, the rounding residue added to k0 so that k0 + 2 (k1 + k2 + k3) == 1 << 22 exactly.  sigma = 0 is the identity."""
+    sigma = float(sigma)
+    if not 0.0 <= sigma <= DEGRADE_MAX_BLUR_SIGMA:
+        raise ValueError(f"blur_taps: sigma = {sigma} must be in [0, {DEGRADE_MAX_BLUR_SIGMA}]")
+    if sigma == 0.0:
+        return DEGRADE_TAPS_OFF
+    g = np.exp(-0.5 * (np.arange(4, dtype=np.float64) / sigma) ** 2)
+    g /= g[0] + 2.0 * g[1:].sum()
+    k = [int(round(float(v) * (1 << DEGRADE_PRECISION_BITS))) for v in g]
+    k[0] += (1 << DEGRADE_PRECISION_BITS) - (k[0] + 2 * sum(k[1:]))
+    return tuple(k)
+
+
+def noise_amp(sigma):
+    """The record's noise_amp for noise of standard deviation `sigma` in 8-bit units: round(sigma * 65536 / 147.80054)."""
+    sigma = float(sigma)
+    amp = int(round(sigma * 65536 / _NOISE_UNIT)) if sigma >= 0.0 else -1
+    if not 0 <= amp <= DEGRADE_MAX_NOISE_AMP:
+        raise ValueError(f"noise_amp: sigma = {sigma} must be in [0, {DEGRADE_MAX_NOISE_AMP * _NOISE_UNIT / 65536:.0f}]")
+    return amp
+
+
+def _degrade_record(i, rec):
+    """One record as the eight words of a DegradeRec; ValueError naming sample i."""
+    if hasattr(rec, "pack"):
+        rec = rec.pack()
+    try:
+        taps, amp, seed, quality, flags = rec
+        taps = tuple(taps)
+        words = taps + (amp, seed, quality, flags)
+        if len(taps) != 4 or any(int(v) != v for v in words):
+            raise TypeError
+        k0, k1, k2, k3, amp, seed, quality, flags = (int(v) for v in words)
+    except (TypeError, ValueError):
+        raise ValueError(f"degrade: sample {i}: record {rec!r} is not (taps[4], noise_amp, noise_seed, quality, flags) in integers") from None
+    if min(k0, k1, k2, k3) < 0 or k0 + 2 * (k1 + k2 + k3) != 1 << DEGRADE_PRECISION_BITS:
+        raise ValueError(f"degrade: sample {i}: taps {taps} must be non-negative with k0 + 2 (k1 + k2 + k3) == 1 << {DEGRADE_PRECISION_BITS}")
+    if not 0 <= amp <= DEGRADE_MAX_NOISE_AMP:
+        raise ValueError(f"degrade: sample {i}: noise_amp {amp} is outside [0, {DEGRADE_MAX_NOISE_AMP}]")
+    if not 0 <= seed < 1 << 32:
+        raise ValueError(f"degrade: sample {i}: noise_seed {seed} is not a 32-bit unsigned value")
+    if not 0 <= quality <= 100:
+        raise ValueError(f"degrade: sample {i}: quality {quality} is outside [0, 100] (0 switches the JPEG round trip off)")
+    if flags & ~DEGRADE_GREY_NOISE:
+        raise ValueError(f"degrade: sample {i}: unknown flag bits in {flags:#x}")
+    return k0, k1, k2, k3, amp, seed, quality, flags
+
+
+def _overlap(a, b):
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def degrade(x, records, out=None):
+    """Blur, noise and a JPEG round trip of a batch in ONE launch.  x: fp32 [B][3][H][W] in [0, 1] (what `patch_pairs` returns as
+    lr); records: B tuples (taps, noise_amp, noise_seed, quality, flags), or objects whose ``pack()`` returns one.  Per sample, in
+    integers and bit-exact against tests/_degrade_ref.py: u = clip(floor(v * 255 + .5)); a separable 7-tap blur with `taps` =
+    `blur_taps(sigma)`, rounded to bytes after each pass as Pillow's resampler does; noise of `noise_amp(sigma)` from a hash of
+    (noise_seed, element), one value per pixel with flags & DEGRADE_GREY_NOISE; what Pillow's ``save(format="JPEG", quality=q,
+    subsampling=0)`` and ``open().convert("RGB")`` give back (quality 0: off); result = u / 255.  `DEGRADE_OFF` switches every stage
+    off.  Returns fp32 [B][3][H][W]; `out` supplies it and must not overlap x.  Everything is validated on the host before anything
+    is uploaded: a bad record is a ValueError naming its sample."""
+    if not isinstance(x, torch.Tensor) or x.dtype != F32:
+        raise TypeError(f"degrade: x must be an fp32 tensor, got {getattr(x, 'dtype', type(x))}")
+    if x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():
+        raise ValueError(f"degrade: x must be contiguous [B][3][H][W], got {tuple(x.shape)}")
+    B, _, H, W = (int(v) for v in x.shape)
+    if H < 1 or W < 1:
+        raise ValueError(f"degrade: x has no pixels: {tuple(x.shape)}")
+    if B > 65535:
+        raise ValueError(f"degrade: {B} samples in one launch (at most 65535)")
+    records = list(records)
+    if len(records) != B:
+        raise ValueError(f"degrade: {B} samples but {len(records)} records")
+    words = [_degrade_record(i, rec) for i, rec in enumerate(records)]
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != F32:
+            raise TypeError(f"degrade: out must be an fp32 tensor, got {getattr(out, 'dtype', type(out))}")
+        if tuple(out.shape) != tuple(x.shape) or not out.is_contiguous():
+            raise ValueError(f"degrade: out must be contiguous {tuple(x.shape)}, got {tuple(out.shape)}")
+        if out.device != x.device:
+            raise RuntimeError(f"degrade: out lives on {out.device}, x on {x.device}")
+        if B and _overlap(x, out):
+            raise ValueError("degrade: out must not overlap x (a tile reads its neighbours' pixels)")
+    if not x.is_cuda or x.device.index != _cur_dev():
+        raise RuntimeError(f"degrade: x lives on {x.device}; it must be on the current GPU "
+                           f"cuda:{_cur_dev() if torch.cuda.is_available() else '?'} (no CPU fallback)")
+    if out is None:
+        out = torch.empty_like(x)
+    if B == 0:
+        return out
+    stager = _DEGRADE_STAGERS.get(x.device)
+    if stager is None:
+        stager = _DEGRADE_STAGERS[x.device] = _RecordStager(x.device)
+    table = stager.upload(b"".join(_DEGRADE_REC.pack(*w) for w in words))
+    _lib.call("tup_degrade_lr", x.data_ptr(), table.data_ptr(), B, H, W, out.data_ptr(), _stream())
+    return out
+
+
 # ---- WindowTransformer (SURVEY 8(f) rank 2): the patch GEMMs in window layout, without reflect padding ----
 def _wt_windows(H, W):
     """Windows down and across the floor(H/8) x floor(W/8) token grid."""
