@@ -666,6 +666,27 @@ int tup_patch_pairs(const void* recs, int B, int P, int p, const int* xmin, cons
  * A null pointer, B, H or W <= 0, B > 65535, or out overlapping in (a tile reads its neighbours): hipErrorInvalidValue. */
 int tup_degrade_lr(const float* in, const void* recs, int B, int H, int W, float* out, void* stream);
 
+/* Baseline JPEG (SOF0) of a whole batch on the GPU (ops.jpeg_encode; csrc/jpeg_encode.hip).  The file of image b is byte
+ * for byte what Pillow's save(format="JPEG", quality, subsampling, restart_marker_rows=restart_rows) writes: standard Huffman tables,
+ * a restart interval of restart_rows MCU rows; tests/_jpeg_ref.py states it in numpy.  subsampling: 0 = 4:4:4, 2 = 4:2:0.  Exactly
+ * one of frames_u8 (uint8 [B][H][W][3], RGB) and frames_f32 (fp32 [B][3][H][W], quantised as tup_f32chw_to_u8hwc does) is given.
+ * Three launches, each with a workgroup per (restart segment, image) or per image, all capturable, no host synchronisation:
+ *   tup_jpeg_sizes    sizes int32 [B][S] <- the bytes of every restart segment, stuffed zeros and closing marker included;
+ *   tup_jpeg_offsets  offsets int32 [B][S] <- header_len + the sizes before; lengths int32 [B] <- the file's length, or -1 where it
+ *                     exceeds `capacity`, the bytes of one image's row of `data`;
+ *   tup_jpeg_write    data uint8 [B][capacity] <- header (header_len bytes on the device, SOI .. SOS, built by the caller from the
+ *                     same parameters), scan and EOI of every image whose length is not -1; nothing is written past a row.
+ * S = tup_jpeg_segments(H, W, subsampling, restart_rows) (returns a count, not an error code), or -1 for what the encoder refuses:
+ * H or W outside 1..65535, another subsampling, restart_rows < 1, a restart interval above 65535 MCUs.  Those, a null pointer, both or
+ * neither frame pointers, B outside 1..65535, quality outside 1..100, S not the count above, capacity outside 0..2^31-1:
+ * hipErrorInvalidValue. */
+int tup_jpeg_segments(int H, int W, int subsampling, int restart_rows);
+int tup_jpeg_sizes(const void* frames_u8, const float* frames_f32, int B, int H, int W, int quality, int subsampling, int restart_rows,
+                   int* sizes, void* stream);
+int tup_jpeg_offsets(const int* sizes, int B, int S, int header_len, long long capacity, int* offsets, int* lengths, void* stream);
+int tup_jpeg_write(const void* frames_u8, const float* frames_f32, int B, int H, int W, int quality, int subsampling, int restart_rows,
+                   const void* header, int header_len, const int* offsets, const int* lengths, void* data, long long capacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,11 @@ SIGNATURES = {
     "tup_patch_pairs": [P, I, I, I, P, P, P, I, P, P, P],
     # training degradations (csrc/degrade.hip)
     "tup_degrade_lr": [P, P, I, I, I, P, P],
+    # baseline JPEG encoding (csrc/jpeg_encode.hip)
+    "tup_jpeg_segments": [I, I, I, I],
+    "tup_jpeg_sizes": [P, P, I, I, I, I, I, I, P, P],
+    "tup_jpeg_offsets": [P, I, I, I, c_longlong, P, P, P],
+    "tup_jpeg_write": [P, P, I, I, I, I, I, I, P, I, P, P, P, c_longlong, P],
     "tup_l1_loss_partial": [P, P, P, c_longlong, I, P],
     "tup_l1_loss_bwd": [P, P, P, P, c_longlong, P],
     "tup_u8hwc_to_f32chw": [P, P, I, I, I, I, P],

@@ -59,6 +59,9 @@ GUARDED = [
     ("image_io.hip", ["nv12_to_f32chw_kernel", "f32chw_to_nv12_kernel"]),
     # no counted hand-off: four 8-point DCT passes hold 8 values a lane in unrolled arrays; a build that indexes them dynamically spills
     ("degrade.hip", ["degrade_lr_kernel"]),
+    # no counted hand-off: the DCT passes hold 8 values a lane in unrolled arrays, and the coder's zigzag walk is a loop over LDS; scratch
+    # would put memory traffic into the one stage that bounds the kernel
+    ("jpeg_encode.hip", ["jpeg_segment_kernel", "jpeg_scan_kernel"]),
 ]
 # diagnostic template instantiations, never launched by the product path: fused_qkv_attn_kernel<PROJ, MLP, STAMPS = true>, the
 # timing ablations fused_mlp_v2_kernel<ABL != 0>

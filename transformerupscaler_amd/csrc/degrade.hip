@@ -25,6 +25,7 @@
 // Bound: its own instruction stream.  A batch of 64 patches of side 96 is 576 workgroups, 2.25 per CU and all resident at once, and
 // moves 14 MB: 19 us with every stage on, 12 us with every stage off, against 3 us for the bytes alone.
 #include "common.h"
+#include "jpeg_dct.h"      // colour conversion, forward DCT, tables and quantiser: shared with jpeg_encode.hip
 
 struct DegradeRec {
     int taps[4];
@@ -44,20 +45,7 @@ constexpr int DG_PRECISION_BITS = 32 - 8 - 2;      // Pillow's PRECISION_BITS fo
 constexpr int DG_THREADS = 256;
 constexpr int DG_QUADS = DG_TILE / 4;              // 4-byte groups of a tile row
 
-constexpr int F_0_298631336 = 2446, F_0_390180644 = 3196, F_0_541196100 = 4433, F_0_765366865 = 6270, F_0_899976223 = 7373,
-              F_1_175875602 = 9633, F_1_501321110 = 12299, F_1_847759065 = 15137, F_1_961570560 = 16069, F_2_053119869 = 16819,
-              F_2_562915447 = 20995, F_3_072711026 = 25172;
-constexpr int dg_fix(double x) { return (int)(x * 65536 + .5); }
-
-// Annex K, natural order [vertical frequency][horizontal frequency]
-__constant__ uint8_t dg_base[2][64] = {
-    {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
-     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
-    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
-     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
-
 TUP_DEVICE int dg_clip255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-TUP_DEVICE int dg_descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 // one output of a blur pass from its seven inputs, rounded to a byte as Pillow's resampler does
 TUP_DEVICE int dg_blur7(const int (&k)[4], int a0, int a1, int a2, int a3, int a4, int a5, int a6)
 {
@@ -66,29 +54,6 @@ TUP_DEVICE int dg_blur7(const int (&k)[4], int a0, int a1, int a2, int a3, int a
     // v_ashr_pk_u8_i32 and ORs the other two bytes of the dword on top of it as if the instruction had cleared bits 16-31 of its
     // destination; it leaves them as they were, and the stale bits came out in bytes 2 and 3 of every dword of the horizontal pass.
     return dg_clip255((int)opaque_copy((uint32_t)s));
-}
-
-// libjpeg's jfdctint.c, one pass over d[0..8): FIRST = the row pass (outputs scaled up by 4), else the column pass (scaled back)
-template <bool FIRST>
-TUP_DEVICE void dg_fdct8(int (&d)[8])
-{
-    constexpr int N = FIRST ? 11 : 15;
-    int t0 = d[0] + d[7], t7 = d[0] - d[7], t1 = d[1] + d[6], t6 = d[1] - d[6];
-    int t2 = d[2] + d[5], t5 = d[2] - d[5], t3 = d[3] + d[4], t4 = d[3] - d[4];
-    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-    d[0] = FIRST ? (t10 + t11) << 2 : dg_descale(t10 + t11, 2);
-    d[4] = FIRST ? (t10 - t11) << 2 : dg_descale(t10 - t11, 2);
-    int z1 = (t12 + t13) * F_0_541196100;
-    d[2] = dg_descale(z1 + t13 * F_0_765366865, N);
-    d[6] = dg_descale(z1 - t12 * F_1_847759065, N);
-    z1 = t4 + t7;
-    int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
-    const int z5 = (z3 + z4) * F_1_175875602;
-    t4 *= F_0_298631336; t5 *= F_2_053119869; t6 *= F_3_072711026; t7 *= F_1_501321110;
-    z1 *= -F_0_899976223; z2 *= -F_2_562915447;
-    z3 = z3 * -F_1_961570560 + z5; z4 = z4 * -F_0_390180644 + z5;
-    d[7] = dg_descale(t4 + z1 + z3, N); d[5] = dg_descale(t5 + z2 + z4, N);
-    d[3] = dg_descale(t6 + z2 + z3, N); d[1] = dg_descale(t7 + z1 + z4, N);
 }
 
 // libjpeg's jidctint.c, one pass: FIRST = the column pass (descale by 11), else the row pass (by 18)
@@ -133,10 +98,9 @@ __global__ __launch_bounds__(DG_THREADS) void degrade_lr_kernel(const float* __r
     const bool jpeg = rec.quality >= 1 && rec.quality <= 100;
 
     if (jpeg && tid < 128) {
-        const int s = rec.quality < 50 ? 5000 / rec.quality : 200 - 2 * rec.quality;
-        const int t = min(max(((int)dg_base[tid >> 6][tid & 63] * s + 50) / 100, 1), 255);
+        const int t = dg_quant_entry(rec.quality, tid >> 6, tid & 63);
         qt[tid >> 6][tid & 63] = t;
-        qr[tid >> 6][tid & 63] = 0xffffffffu / (uint32_t)(8 * t) + 1u;            // (for a power of two this is 2^32 / (8 t) itself: exact too)
+        qr[tid >> 6][tid & 63] = dg_quant_rcp(t);
     }
 
     // ---- 1. fp32 -> bytes, the tile and its halo; a coordinate outside the image reads the nearest pixel inside ----
@@ -218,9 +182,11 @@ __global__ __launch_bounds__(DG_THREADS) void degrade_lr_kernel(const float* __r
             const uint8_t* sp = win + min(y, th - 1) * DG_WS + min(x, tw - 1);
             const int R = sp[0], G = sp[DG_WIN * DG_WS], B = sp[2 * DG_WIN * DG_WS];
             int* d = pl + y * DG_PS + x;
-            d[0] = ((dg_fix(.299) * R + dg_fix(.587) * G + dg_fix(.114) * B + 32768) >> 16) - 128;
-            d[DG_TILE * DG_PS] = ((-dg_fix(.16874) * R - dg_fix(.33126) * G + dg_fix(.5) * B + (128 << 16) + 32767) >> 16) - 128;
-            d[2 * DG_TILE * DG_PS] = ((dg_fix(.5) * R - dg_fix(.41869) * G - dg_fix(.08131) * B + (128 << 16) + 32767) >> 16) - 128;
+            int Y, Cb, Cr;
+            dg_rgb_to_ycc(R, G, B, Y, Cb, Cr);
+            d[0] = Y - 128;
+            d[DG_TILE * DG_PS] = Cb - 128;
+            d[2 * DG_TILE * DG_PS] = Cr - 128;
         }
         __syncthreads();
 
@@ -251,11 +217,9 @@ __global__ __launch_bounds__(DG_THREADS) void degrade_lr_kernel(const float* __r
             dg_fdct8<false>(d);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                // sign(c) ((|c| + 4 t) / (8 t)) t.  n = |c| + 4 t < 2^16 and 8 t < 2^11, so with m = floor(2^32 / (8 t)) + 1 the high word
-                // of n m is the quotient: n m / 2^32 exceeds n / (8 t) by less than n / 2^32 < 1 / (8 t), too little to reach the next integer
+                // sign(c) ((|c| + 4 t) / (8 t)) t
                 const int tk = t[k * 8];
-                const uint32_t n = (uint32_t)abs(d[k]) + (uint32_t)(4 * tk);
-                const int q = (int)__umulhi(n, rcp[k * 8]) * tk;
+                const int q = dg_quant_div(d[k], tk, rcp[k * 8]) * tk;
                 d[k] = d[k] < 0 ? -q : q;
             }
             dg_idct8<true>(d);

@@ -84,8 +84,11 @@ def _bicubic_on(device, in_size, out_size):
     return _table(resize_taps.bicubic_taps, device, (in_size, out_size))
 
 
-def _pil_taps_on(device, in_size, out_size):
-    return _table(resize_taps.pil_bilinear_coeffs, device, (in_size, out_size))
+_PIL_COEFFS = {"bilinear": resize_taps.pil_bilinear_coeffs, "bicubic": resize_taps.pil_bicubic_coeffs}
+
+
+def _pil_taps_on(device, in_size, out_size, resample="bilinear"):
+    return _table(_PIL_COEFFS[resample], device, (in_size, out_size))
 
 
 # ---- zero pool: the backward pass needs ~130 small zero-initialised fp32 buffers per step (atomically accumulated weight /
@@ -1199,10 +1202,14 @@ def bra_backward(g, ui, feat, comp, wu, bu, w3):
     return dfeat, dwu, dbu, dw3, G, Gb
 
 
-def resize_frames(frames_u8, size, to_tensor=False, bgr=False):
+def resize_frames(frames_u8, size, to_tensor=False, bgr=False, resample="bilinear"):
     """transforms.Resize(size) on uint8 frames [B][H][W][3] (or [H][W][3]) on the GPU, bit-exact with Pillow's BILINEAR resample
     of an RGB image (data_handling/data_class.py:61-71, inference.py:65-75).  to_tensor=False -> uint8 [B][h][w][3];
-    to_tensor=True -> fp32 [B][3][h][w] in [0, 1] (Resize + ToTensor in the same launches)."""
+    to_tensor=True -> fp32 [B][3][h][w] in [0, 1] (Resize + ToTensor in the same launches).  resample="bicubic" is Pillow's BICUBIC
+    (``Image.resize(size, Image.BICUBIC)``, the reference's baseline image, inference.py:83), bit-exact too: the same two kernels
+    with the tables of `resize_taps.pil_bicubic_coeffs`."""
+    if resample not in _PIL_COEFFS:
+        raise ValueError(f"resize_frames: resample must be 'bilinear' or 'bicubic', got {resample!r}")
     if frames_u8.dim() == 3:
         frames_u8 = frames_u8.unsqueeze(0)
     B, H, W, C = frames_u8.shape
@@ -1211,12 +1218,12 @@ def resize_frames(frames_u8, size, to_tensor=False, bgr=False):
     cur = frames_u8
     _chk(cur, torch.uint8, None, "frames")
     if w != W:                                            # Pillow: horizontal pass first, into a uint8 image
-        lo, n, k, ks = _pil_taps_on(cur.device, W, w)
+        lo, n, k, ks = _pil_taps_on(cur.device, W, w, resample)
         tmp = torch.empty((B, H, w, 3), dtype=torch.uint8, device=cur.device)
         _lib.call("tup_resize_u8_rows", cur.data_ptr(), tmp.data_ptr(), lo.data_ptr(), n.data_ptr(), k.data_ptr(), ks, B, H, W, w, _stream())
         cur = tmp
     if h != H:
-        lo, n, k, ks = _pil_taps_on(cur.device, H, h)
+        lo, n, k, ks = _pil_taps_on(cur.device, H, h, resample)
         out_u8 = None if to_tensor else torch.empty((B, h, w, 3), dtype=torch.uint8, device=cur.device)
         out_f = torch.empty((B, 3, h, w), dtype=F32, device=cur.device) if to_tensor else None
         _lib.call("tup_resize_u8_cols", cur.data_ptr(), None if out_u8 is None else out_u8.data_ptr(),
@@ -1431,6 +1438,159 @@ def degrade(x, records, out=None):
     table = stager.upload(b"".join(_DEGRADE_REC.pack(*w) for w in words))
     _lib.call("tup_degrade_lr", x.data_ptr(), table.data_ptr(), B, H, W, out.data_ptr(), _stream())
     return out
+
+
+# ---- baseline JPEG encoding of a batch (csrc/jpeg_encode.hip) ----
+JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+               35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+_JPEG_BASE = (
+    (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99),
+    (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32)
+# Annex K.3 - K.6 as a DHT segment carries them: (table class << 4 | id, codes of each length 1..16, symbols in code order)
+_JPEG_DHT = (
+    (0x00, (0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), tuple(range(12))),
+    (0x10, (0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d),
+     (0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
+      0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
+      0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
+      0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
+      0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
+      0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
+      0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa)),
+    (0x01, (0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), tuple(range(12))),
+    (0x11, (0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77),
+     (0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
+      0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
+      0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
+      0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
+      0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
+      0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
+      0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa)),
+)
+JPEG_CHUNK_BLOCKS = 96                           # 8 x 8 blocks a workgroup codes at a time: 16 MCUs of 4:2:0, 32 of 4:4:4
+_JPEG_SUBSAMPLING = {"4:4:4": 0, 0: 0, "4:2:0": 2, 2: 2}
+_jpeg_headers = {}
+
+
+def jpeg_quant_table(which, quality):
+    """The Annex K table (0 luma, 1 chroma) scaled to `quality` as jpeg_set_quality does, 64 values in natural order."""
+    s = 5000 // quality if quality < 50 else 200 - 2 * quality
+    return tuple(min(max((v * s + 50) // 100, 1), 255) for v in _JPEG_BASE[which])
+
+
+def _jpeg_params(H, W, quality, subsampling, restart_rows):
+    """(subsampling code, restart interval in MCUs, restart segments) after every check `jpeg_encode` makes on its parameters."""
+    if isinstance(subsampling, bool) or subsampling not in _JPEG_SUBSAMPLING:
+        raise ValueError(f"jpeg_encode: subsampling must be '4:4:4' / 0 or '4:2:0' / 2, got {subsampling!r}")
+    sub = _JPEG_SUBSAMPLING[subsampling]
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError(f"jpeg_encode: quality must be an integer in 1..100, got {quality!r}")
+    if isinstance(restart_rows, bool) or not isinstance(restart_rows, int) or restart_rows < 1:
+        raise ValueError(f"jpeg_encode: restart_rows must be an integer >= 1, got {restart_rows!r} (a file without restarts is not offered)")
+    if not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError(f"jpeg_encode: a JPEG image is 1..65535 pixels a side, got {H} x {W}")
+    m = 16 if sub == 2 else 8
+    mw, mh = (W + m - 1) // m, (H + m - 1) // m
+    if restart_rows * mw > 65535:
+        raise ValueError(f"jpeg_encode: restart_rows = {restart_rows} x {mw} MCUs a row is a restart interval above 65535")
+    return sub, restart_rows * mw, (mh + restart_rows - 1) // restart_rows
+
+
+def jpeg_header(H, W, quality=75, subsampling="4:2:0", restart_rows=1):
+    """The bytes before the scan, built from the parameters alone: SOI, APP0 (JFIF 1.01), DQT x 2, SOF0, DHT x 4, DRI, SOS."""
+    sub, interval, _ = _jpeg_params(H, W, quality, subsampling, restart_rows)
+    seg = lambda marker, payload: bytes([0xFF, marker]) + (len(payload) + 2).to_bytes(2, "big") + bytes(payload)
+    out = b"\xff\xd8" + seg(0xE0, b"JFIF\0" + bytes([1, 1, 0, 0, 1, 0, 1, 0, 0]))
+    for i in (0, 1):
+        t = jpeg_quant_table(i, quality)
+        out += seg(0xDB, bytes([i]) + bytes(t[k] for k in JPEG_ZIGZAG))
+    out += seg(0xC0, bytes([8]) + H.to_bytes(2, "big") + W.to_bytes(2, "big") + bytes([3, 1, 0x22 if sub == 2 else 0x11, 0, 2, 0x11, 1, 3, 0x11, 1]))
+    for ident, counts, symbols in _JPEG_DHT:
+        out += seg(0xC4, bytes([ident]) + bytes(counts) + bytes(symbols))
+    out += seg(0xDD, interval.to_bytes(2, "big"))
+    return out + seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
+
+
+def _jpeg_header_on(device, key):
+    k = (str(device),) + key
+    if k not in _jpeg_headers:
+        if len(_jpeg_headers) >= 64:
+            _jpeg_headers.clear()
+        _jpeg_headers[k] = torch.frombuffer(bytearray(jpeg_header(*key)), dtype=torch.uint8).to(device)
+    return _jpeg_headers[k]
+
+
+def jpeg_encode(frames, quality=75, subsampling="4:2:0", restart_rows=1, out=None):
+    """Baseline JPEG files of a batch, made on the GPU in three launches.  frames: uint8 [B][H][W][3] (or [H][W][3]) RGB, or fp32
+    [B][3][H][W] quantised as `tensor_to_frames` does, trunc(clamp(x * 255, 0, 255)), inside the first kernel.  The file of image b
+    is byte for byte what ``Image.fromarray(frame_b).save(buf, "JPEG", quality=quality, subsampling=subsampling,
+    restart_marker_rows=restart_rows)`` writes: standard Huffman tables, 4:2:0 ("4:2:0" / 2, Pillow's default) or 4:4:4 ("4:4:4" /
+    0), a restart marker every `restart_rows` MCU rows (the restart segments are what the GPU codes in parallel).
+    Returns (data uint8 [B][capacity], lengths int32 [B]); `jpeg_files` turns them into bytes.  out=None: the lengths are read back
+    once (the call's one host synchronisation) and `data` is allocated to the longest file.  out=(data, lengths): nothing
+    synchronises; an image longer than data's row gets length -1 and none of its bytes.  Everything is validated before any launch."""
+    if not isinstance(frames, torch.Tensor) or frames.dtype not in (torch.uint8, F32):
+        raise TypeError(f"jpeg_encode: frames must be a uint8 or float32 tensor, got {getattr(frames, 'dtype', type(frames))}")
+    if frames.dtype == torch.uint8:
+        if frames.dim() == 3:
+            frames = frames.unsqueeze(0)
+        if frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError(f"jpeg_encode: uint8 frames must be [B][H][W][3] or [H][W][3], got shape {tuple(frames.shape)}")
+        B, H, W = (int(v) for v in frames.shape[:3])
+    else:
+        if frames.dim() != 4 or frames.shape[1] != 3:
+            raise ValueError(f"jpeg_encode: float32 frames must be [B][3][H][W], got shape {tuple(frames.shape)}")
+        B, H, W = int(frames.shape[0]), int(frames.shape[2]), int(frames.shape[3])
+    if not 1 <= B <= 65535:
+        raise ValueError(f"jpeg_encode: {B} images in one call (1..65535)")
+    sub, _, S = _jpeg_params(H, W, quality, subsampling, restart_rows)
+    if not frames.is_contiguous():
+        raise ValueError("jpeg_encode: frames must be contiguous")
+    if out is not None:
+        data, lengths = out
+        if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 2 or data.shape[0] != B or not data.is_contiguous():
+            raise ValueError(f"jpeg_encode: out[0] must be a contiguous uint8 [{B}][capacity] tensor, got {getattr(data, 'dtype', type(data))} "
+                             f"{tuple(getattr(data, 'shape', ()))}")
+        if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,) or not lengths.is_contiguous():
+            raise ValueError(f"jpeg_encode: out[1] must be a contiguous int32 [{B}] tensor, got {getattr(lengths, 'dtype', type(lengths))} "
+                             f"{tuple(getattr(lengths, 'shape', ()))}")
+        if data.shape[1] >= 2 ** 31:
+            raise ValueError(f"jpeg_encode: out[0] has rows of {data.shape[1]} bytes (below 2^31)")
+    _nv12_on_gpu("jpeg_encode", frames, "frames")
+    if out is not None:
+        _nv12_on_gpu("jpeg_encode", data, "out[0]")
+        _nv12_on_gpu("jpeg_encode", lengths, "out[1]")
+    dev = frames.device
+    u8 = frames.data_ptr() if frames.dtype == torch.uint8 else None
+    f32 = frames.data_ptr() if frames.dtype == F32 else None
+    header = _jpeg_header_on(dev, (H, W, quality, sub, restart_rows))
+    work = torch.empty((2, B, S), dtype=torch.int32, device=dev)
+    if _lib.load().tup_jpeg_segments(H, W, sub, restart_rows) != S:
+        raise RuntimeError("jpeg_encode: the library counts other restart segments than the binding")
+    _lib.call("tup_jpeg_sizes", u8, f32, B, H, W, quality, sub, restart_rows, work[0].data_ptr(), _stream())
+    if out is None:
+        lengths = torch.empty((B,), dtype=torch.int32, device=dev)
+        _lib.call("tup_jpeg_offsets", work[0].data_ptr(), B, S, header.numel(), 2 ** 31 - 1, work[1].data_ptr(), lengths.data_ptr(), _stream())
+        host = lengths.cpu().tolist()                                   # the one synchronisation
+        if min(host) < 0:
+            raise RuntimeError("jpeg_encode: a file of 2 GiB or more")
+        data = torch.empty((B, max(host)), dtype=torch.uint8, device=dev)
+    else:
+        _lib.call("tup_jpeg_offsets", work[0].data_ptr(), B, S, header.numel(), int(data.shape[1]), work[1].data_ptr(), lengths.data_ptr(), _stream())
+    _lib.call("tup_jpeg_write", u8, f32, B, H, W, quality, sub, restart_rows, header.data_ptr(), header.numel(), work[1].data_ptr(),
+              lengths.data_ptr(), data.data_ptr(), int(data.shape[1]), _stream())
+    return data, lengths
+
+
+def jpeg_files(data, lengths):
+    """(data, lengths) of `jpeg_encode` -> a list of bytes, one file per image (one copy to the host).  An image that did not fit
+    (length -1) is an error."""
+    n = [int(v) for v in lengths.cpu().tolist()]
+    if any(v < 0 for v in n):
+        raise ValueError(f"jpeg_files: image {[i for i, v in enumerate(n) if v < 0][0]} did not fit its row of {data.shape[1]} bytes")
+    host = data.cpu().numpy()
+    return [host[i, :v].tobytes() for i, v in enumerate(n)]
 
 
 # ---- WindowTransformer (SURVEY 8(f) rank 2): the patch GEMMs in window layout, without reflect padding ----

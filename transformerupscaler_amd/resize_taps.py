@@ -111,14 +111,27 @@ def transpose_taps(idx: np.ndarray, w: np.ndarray, in_size: int):
 PIL_PRECISION_BITS = 32 - 8 - 2
 
 
-def pil_bilinear_coeffs(in_size: int, out_size: int):
-    """Pillow's coefficient tables for an 8-bit BILINEAR resample of one axis (libImaging/Resample.c precompute_coeffs +
-    normalize_coeffs_8bpc; the arithmetic behind transforms.Resize on a PIL image, reference data_handling/data_class.py:61-71):
-    (min int32 [out], size int32 [out], k int32 [out][ksize], ksize).  Weights are computed and normalised in double and rounded
-    half away from zero to 22 fractional bits, exactly as Pillow does."""
+def _pil_triangle(x: float) -> float:
+    x = abs(x)
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+def _pil_cubic(x: float) -> float:
+    """Pillow's bicubic_filter: the Keys kernel with a = -0.5."""
+    a = -0.5
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def _pil_coeffs(in_size: int, out_size: int, kernel, kernel_support: float):
+    """libImaging/Resample.c precompute_coeffs + normalize_coeffs_8bpc for one axis and one filter."""
     scale = in_size / out_size
     fscale = max(scale, 1.0)
-    support = 1.0 * fscale
+    support = kernel_support * fscale
     ksize = int(math.ceil(support)) * 2 + 1
     lo = np.zeros(out_size, np.int32)
     n = np.zeros(out_size, np.int32)
@@ -130,8 +143,7 @@ def pil_bilinear_coeffs(in_size: int, out_size: int):
         b = min(int(center + support + 0.5), in_size)
         ww = 0.0
         for x in range(b - a):
-            t = abs((x + a - center + 0.5) * inv)
-            w = 1.0 - t if t < 1.0 else 0.0
+            w = kernel((x + a - center + 0.5) * inv)
             kk[i, x] = w
             ww += w
         if ww != 0.0:
@@ -139,6 +151,20 @@ def pil_bilinear_coeffs(in_size: int, out_size: int):
         lo[i], n[i] = a, b - a
     ki = np.where(kk < 0, np.trunc(-0.5 + kk * (1 << PIL_PRECISION_BITS)), np.trunc(0.5 + kk * (1 << PIL_PRECISION_BITS)))
     return lo, n, np.ascontiguousarray(ki.astype(np.int32)), ksize
+
+
+def pil_bilinear_coeffs(in_size: int, out_size: int):
+    """Pillow's coefficient tables for an 8-bit BILINEAR resample of one axis (libImaging/Resample.c precompute_coeffs +
+    normalize_coeffs_8bpc; the arithmetic behind transforms.Resize on a PIL image, reference data_handling/data_class.py:61-71):
+    (min int32 [out], size int32 [out], k int32 [out][ksize], ksize).  Weights are computed and normalised in double and rounded
+    half away from zero to 22 fractional bits, exactly as Pillow does."""
+    return _pil_coeffs(in_size, out_size, _pil_triangle, 1.0)
+
+
+def pil_bicubic_coeffs(in_size: int, out_size: int):
+    """The same tables for Pillow's BICUBIC resample (a = -0.5, support 2; the reference's baseline image, inference.py:83): same
+    normalisation and rounding, negative lobes included, so the row / column kernels take them as they are."""
+    return _pil_coeffs(in_size, out_size, _pil_cubic, 2.0)
 
 
 def tail_fused_tables(in_h: int, in_w: int, out_h: int, out_w: int, tile_h: int, tile_w: int):
