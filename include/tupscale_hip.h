@@ -687,6 +687,36 @@ int tup_jpeg_offsets(const int* sizes, int B, int S, int header_len, long long c
 int tup_jpeg_write(const void* frames_u8, const float* frames_f32, int B, int H, int W, int quality, int subsampling, int restart_rows,
                    const void* header, int header_len, const int* offsets, const int* lengths, void* data, long long capacity, void* stream);
 
+/* Baseline JPEG (SOF0) files of a whole batch decoded on the GPU (ops.jpeg_decode; csrc/jpeg_decode.hip).  The pixels of
+ * image b are what Pillow's Image.open(file).convert("RGB") returns; tests/_jpeg_decode_ref.py states it in numpy.  The caller parses
+ * the marker segments and uploads
+ *   records  B x 1488 bytes, per image {int32 scan_off (a multiple of 16, into `scans`), int32 scan_len (the bytes between SOS and
+ *            EOI), uint8 td[4], ta[4] (each component's DC / AC Huffman table, 0 or 1), uint16 qt[3][64] (each component's
+ *            quantisation table, natural order), uint8 huff[4][272] (DC 0, DC 1, AC 0, AC 1 as DHT carries them: 16 counts, then
+ *            the symbols, zero filled)};
+ *   scans    scans_bytes bytes (at most 0x7fff0000), 16-byte aligned, each scan padded to a multiple of 16 bytes.
+ * All images share H, W, layout (0 = 4:4:4, 2 = 4:2:0, 4 = one component) and restart_interval in MCUs (0 = none).  Three launches,
+ * all capturable, no host synchronisation:
+ *   tup_jpeg_decode_index   segs int32 [B][S][8] <- the walker's state at the start of every segment (a restart interval, or an MCU
+ *                           row where the file has none: found by one serial walk per image); status int32 [B] <- 0, or non-zero for
+ *                           a scan that does not decode completely;
+ *   tup_jpeg_decode_blocks  workspace uint8 [B][ws_bytes] <- the Y (Cb, Cr) sample planes padded to whole MCUs, ws_bytes = their
+ *                           bytes for one image; status[b] <- non-zero where a segment's walk stops early;
+ *   tup_jpeg_decode_finish  exactly one of out_u8 (uint8 [B][H][W][3], RGB) and out_f32 (fp32 [B][3][H][W] = byte / 255) <- the
+ *                           pixels: fancy upsampling where 4:2:0, colour conversion, crop.
+ * Any bytes are safe: nothing is read outside an image's scan or written outside its workspace and output; the pixels of an image
+ * with a non-zero status are unspecified.  S = tup_jpeg_decode_segments(H, W, layout, restart_interval) (returns a count, not an
+ * error code), or -1 for what the decoder refuses: H or W outside 1..65535, another layout, an interval outside 0..65535.  Those, a
+ * null or misaligned pointer, both or neither outputs, B outside 1..65535, S or ws_bytes other than the geometry's:
+ * hipErrorInvalidValue. */
+int tup_jpeg_decode_segments(int H, int W, int layout, int restart_interval);
+int tup_jpeg_decode_index(const void* records, const void* scans, long long scans_bytes, int B, int H, int W, int layout,
+                          int restart_interval, int S, int* segs, int* status, void* stream);
+int tup_jpeg_decode_blocks(const void* records, const void* scans, long long scans_bytes, int B, int H, int W, int layout,
+                           int restart_interval, int S, const int* segs, int* status, void* workspace, long long ws_bytes, void* stream);
+int tup_jpeg_decode_finish(const void* workspace, long long ws_bytes, int B, int H, int W, int layout, void* out_u8, float* out_f32,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,8 @@ by the GPU JPEG encoder.
 
 What happens, in the reference's order (inference.py:64-146):
 
-1. the input (PNG or JPEG) is decoded once on the host by Pillow and uploaded as uint8;
+1. the input is decoded once: a baseline JPEG with restart markers on the GPU (``ops.jpeg_decode``), anything else (PNG, progressive
+   or restart-less JPEG) on the host by Pillow and uploaded as uint8;
 2. ``Resize(res_in)`` + ``ToTensor`` run on the GPU (``ops.resize_frames``, Pillow-exact BILINEAR; ``ops.frames_to_tensor``);
 3. ``--inp`` (the low-resolution input) and ``bicubic.jpg`` (``Image.resize(.., Image.BICUBIC)`` of it by ``--scale``, in the current
    directory as in the reference; ``ops.resize_frames(resample="bicubic")``, Pillow-exact) are encoded by ``ops.jpeg_encode``;
@@ -18,8 +19,8 @@ What happens, in the reference's order (inference.py:64-146):
 The files are what Pillow's ``save()`` writes for the same pixels at ``--quality`` / ``--subsampling`` (defaults 75 and 4:2:0, Pillow's
 own) with a restart marker after every MCU row; they decode to the same pixels as Pillow's files without restart markers.
 
-Scores, as the reference computes them, on the DECODED files (Pillow decodes the bytes just produced): SSIM and PSNR of ``--out``
-and of the upscaled ``--inp`` against the original, by ``transformerupscaler_amd.metrics`` (skimage's defaults: 7 x 7 uniform window,
+Scores, as the reference computes them, on the DECODED files (``ops.jpeg_decode`` decodes the bytes just produced, to Pillow's
+pixels): SSIM and PSNR of ``--out`` and of the upscaled ``--inp`` against the original, by ``transformerupscaler_amd.metrics`` (skimage's defaults: 7 x 7 uniform window,
 ``data_range`` = the full range).  The reference brings the original to the output's size, and the low-resolution input to the
 original's, with ``skimage.transform.resize``; scikit-image is not a dependency here, so both resizes are the project's GPU resize
 (``ops.resize_frames``, Pillow's BILINEAR, antialiased when shrinking).  The printed scores are therefore comparable with the
@@ -69,11 +70,29 @@ def build_parser():
     return p
 
 
-def decode_image(path_or_bytes, device):
-    """uint8 [H][W][3] RGB on the GPU: one host decode by Pillow."""
+def decode_image(path_or_bytes, device, gpu=True):
+    """uint8 [H][W][3] RGB on the GPU.  A baseline JPEG with restart markers (every file this driver writes) is decoded there by
+    ``ops.jpeg_decode``, whose pixels are Pillow's; everything else (PNG, progressive or restart-less JPEG, a damaged file), or
+    everything with gpu=False, is one host decode by Pillow and an upload."""
     import numpy as np
     import torch
     from PIL import Image
+    if gpu:
+        from transformerupscaler_amd import ops
+        data = path_or_bytes
+        if not isinstance(data, (bytes, bytearray)):
+            with open(data, "rb") as f:
+                data = f.read()
+        try:
+            fast = ops.jpeg_parse(data)["restart_interval"] > 0
+        except ValueError:
+            fast = False
+        if fast:
+            with torch.cuda.device(device):
+                frames, status = ops.jpeg_decode(data)
+            if int(status[0]) == 0:
+                return frames[0]
+        path_or_bytes = data
     src = io.BytesIO(path_or_bytes) if isinstance(path_or_bytes, (bytes, bytearray)) else path_or_bytes
     with Image.open(src) as im:
         arr = np.asarray(im.convert("RGB"))

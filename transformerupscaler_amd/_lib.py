@@ -87,6 +87,11 @@ SIGNATURES = {
     "tup_jpeg_sizes": [P, P, I, I, I, I, I, I, P, P],
     "tup_jpeg_offsets": [P, I, I, I, c_longlong, P, P, P],
     "tup_jpeg_write": [P, P, I, I, I, I, I, I, P, I, P, P, P, c_longlong, P],
+    # baseline JPEG decoding (csrc/jpeg_decode.hip)
+    "tup_jpeg_decode_segments": [I, I, I, I],
+    "tup_jpeg_decode_index": [P, P, c_longlong, I, I, I, I, I, I, P, P, P],
+    "tup_jpeg_decode_blocks": [P, P, c_longlong, I, I, I, I, I, I, P, P, P, c_longlong, P],
+    "tup_jpeg_decode_finish": [P, c_longlong, I, I, I, I, P, P, P],
     "tup_l1_loss_partial": [P, P, P, c_longlong, I, P],
     "tup_l1_loss_bwd": [P, P, P, P, c_longlong, P],
     "tup_u8hwc_to_f32chw": [P, P, I, I, I, I, P],

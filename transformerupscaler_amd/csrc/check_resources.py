@@ -62,6 +62,9 @@ GUARDED = [
     # no counted hand-off: the DCT passes hold 8 values a lane in unrolled arrays, and the coder's zigzag walk is a loop over LDS; scratch
     # would put memory traffic into the one stage that bounds the kernel
     ("jpeg_encode.hip", ["jpeg_segment_kernel", "jpeg_scan_kernel"]),
+    # no counted hand-off: the one lane that walks the Huffman codes bounds the decoder, and its reader state, predictors and the IDCT's
+    # 8 values a lane must stay in registers and LDS; scratch would put memory latency into every symbol
+    ("jpeg_decode.hip", ["jpeg_index_kernel", "jpeg_blocks_kernel", "jpeg_finish_kernel"]),
 ]
 # diagnostic template instantiations, never launched by the product path: fused_qkv_attn_kernel<PROJ, MLP, STAMPS = true>, the
 # timing ablations fused_mlp_v2_kernel<ABL != 0>

@@ -25,7 +25,7 @@
 // Bound: its own instruction stream.  A batch of 64 patches of side 96 is 576 workgroups, 2.25 per CU and all resident at once, and
 // moves 14 MB: 19 us with every stage on, 12 us with every stage off, against 3 us for the bytes alone.
 #include "common.h"
-#include "jpeg_dct.h"      // colour conversion, forward DCT, tables and quantiser: shared with jpeg_encode.hip
+#include "jpeg_dct.h"      // colour conversion, both DCTs, tables and quantiser: shared with jpeg_encode.hip and jpeg_decode.hip
 
 struct DegradeRec {
     int taps[4];
@@ -45,7 +45,6 @@ constexpr int DG_PRECISION_BITS = 32 - 8 - 2;      // Pillow's PRECISION_BITS fo
 constexpr int DG_THREADS = 256;
 constexpr int DG_QUADS = DG_TILE / 4;              // 4-byte groups of a tile row
 
-TUP_DEVICE int dg_clip255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 // one output of a blur pass from its seven inputs, rounded to a byte as Pillow's resampler does
 TUP_DEVICE int dg_blur7(const int (&k)[4], int a0, int a1, int a2, int a3, int a4, int a5, int a6)
 {
@@ -54,29 +53,6 @@ TUP_DEVICE int dg_blur7(const int (&k)[4], int a0, int a1, int a2, int a3, int a
     // v_ashr_pk_u8_i32 and ORs the other two bytes of the dword on top of it as if the instruction had cleared bits 16-31 of its
     // destination; it leaves them as they were, and the stale bits came out in bytes 2 and 3 of every dword of the horizontal pass.
     return dg_clip255((int)opaque_copy((uint32_t)s));
-}
-
-// libjpeg's jidctint.c, one pass: FIRST = the column pass (descale by 11), else the row pass (by 18)
-template <bool FIRST>
-TUP_DEVICE void dg_idct8(int (&d)[8])
-{
-    constexpr int N = FIRST ? 11 : 18;
-    int z1 = (d[2] + d[6]) * F_0_541196100;
-    int t2 = z1 - d[6] * F_1_847759065, t3 = z1 + d[2] * F_0_765366865;
-    int t0 = (d[0] + d[4]) << 13, t1 = (d[0] - d[4]) << 13;
-    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-    t0 = d[7]; t1 = d[5]; t2 = d[3]; t3 = d[1];
-    z1 = t0 + t3;
-    int z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3;
-    const int z5 = (z3 + z4) * F_1_175875602;
-    t0 *= F_0_298631336; t1 *= F_2_053119869; t2 *= F_3_072711026; t3 *= F_1_501321110;
-    z1 *= -F_0_899976223; z2 *= -F_2_562915447;
-    z3 = z3 * -F_1_961570560 + z5; z4 = z4 * -F_0_390180644 + z5;
-    t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
-    d[0] = dg_descale(t10 + t3, N); d[7] = dg_descale(t10 - t3, N);
-    d[1] = dg_descale(t11 + t2, N); d[6] = dg_descale(t11 - t2, N);
-    d[2] = dg_descale(t12 + t1, N); d[5] = dg_descale(t12 - t1, N);
-    d[3] = dg_descale(t13 + t0, N); d[4] = dg_descale(t13 - t0, N);
 }
 
 __global__ __launch_bounds__(DG_THREADS) void degrade_lr_kernel(const float* __restrict__ in, const DegradeRec* __restrict__ recs,

@@ -1,7 +1,7 @@
 // The front half of a baseline JPEG encoder as libjpeg computes it, shared by the training degradations (degrade.hip: a 4:4:4 round
 // trip on bytes) and the encoder (jpeg_encode.hip): the 16-bit RGB -> YCbCr conversion, the "slow integer" forward DCT (jfdctint.c),
-// the Annex K tables scaled to a quality, and the quantiser.  All in 32-bit integers; stated in numpy in tests/_degrade_ref.py and
-// pinned there to Pillow.
+// the Annex K tables scaled to a quality, and the quantiser; and the inverse DCT (jidctint.c) that degrade.hip and the decoder
+// (jpeg_decode.hip) share, and the workgroup scan of the two codecs.  All in 32-bit integers; stated in numpy in tests/_degrade_ref.py and pinned there to Pillow.
 #pragma once
 #include "common.h"
 
@@ -61,5 +61,52 @@ TUP_DEVICE void dg_fdct8(int (&d)[8])
     z3 = z3 * -F_1_961570560 + z5; z4 = z4 * -F_0_390180644 + z5;
     d[7] = dg_descale(t4 + z1 + z3, N); d[5] = dg_descale(t5 + z2 + z4, N);
     d[3] = dg_descale(t6 + z2 + z3, N); d[1] = dg_descale(t7 + z1 + z4, N);
+}
+
+TUP_DEVICE int dg_clip255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// libjpeg's jidctint.c, one pass: FIRST = the column pass (descale by 11), else the row pass (by 18)
+template <bool FIRST>
+TUP_DEVICE void dg_idct8(int (&d)[8])
+{
+    constexpr int N = FIRST ? 11 : 18;
+    int z1 = (d[2] + d[6]) * F_0_541196100;
+    int t2 = z1 - d[6] * F_1_847759065, t3 = z1 + d[2] * F_0_765366865;
+    int t0 = (d[0] + d[4]) << 13, t1 = (d[0] - d[4]) << 13;
+    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    t0 = d[7]; t1 = d[5]; t2 = d[3]; t3 = d[1];
+    z1 = t0 + t3;
+    int z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3;
+    const int z5 = (z3 + z4) * F_1_175875602;
+    t0 *= F_0_298631336; t1 *= F_2_053119869; t2 *= F_3_072711026; t3 *= F_1_501321110;
+    z1 *= -F_0_899976223; z2 *= -F_2_562915447;
+    z3 = z3 * -F_1_961570560 + z5; z4 = z4 * -F_0_390180644 + z5;
+    t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
+    d[0] = dg_descale(t10 + t3, N); d[7] = dg_descale(t10 - t3, N);
+    d[1] = dg_descale(t11 + t2, N); d[6] = dg_descale(t11 - t2, N);
+    d[2] = dg_descale(t12 + t1, N); d[5] = dg_descale(t12 - t1, N);
+    d[3] = dg_descale(t13 + t0, N); d[4] = dg_descale(t13 - t0, N);
+}
+
+constexpr int DG_SCAN_THREADS = 256;
+// exclusive sum over a workgroup of DG_SCAN_THREADS lanes (the encoder's and the decoder's); `total` = the sum of all.  Ends on a
+// barrier, so the buffer may be used again at once.
+TUP_DEVICE int dg_scan256(int v, int (&buf)[2][DG_SCAN_THREADS], int tid, int& total)
+{
+    buf[0][tid] = v;
+    __syncthreads();
+    int cur = 0;
+#pragma unroll
+    for (int d = 1; d < DG_SCAN_THREADS; d <<= 1) {
+        int x = buf[cur][tid];
+        if (tid >= d) x += buf[cur][tid - d];
+        buf[cur ^ 1][tid] = x;
+        cur ^= 1;
+        __syncthreads();
+    }
+    const int incl = buf[cur][tid];
+    total = buf[cur][DG_SCAN_THREADS - 1];
+    __syncthreads();
+    return incl - v;
 }
 }  // namespace

@@ -90,26 +90,6 @@ struct JpShared {
     uint8_t zz[64];
 };
 
-// exclusive sum over the workgroup; `total` = the sum of all.  Ends on a barrier, so the buffer may be used again at once.
-TUP_DEVICE int jp_scan(int v, int (&buf)[2][JP_THREADS], int tid, int& total)
-{
-    buf[0][tid] = v;
-    __syncthreads();
-    int cur = 0;
-#pragma unroll
-    for (int d = 1; d < JP_THREADS; d <<= 1) {
-        int x = buf[cur][tid];
-        if (tid >= d) x += buf[cur][tid - d];
-        buf[cur ^ 1][tid] = x;
-        cur ^= 1;
-        __syncthreads();
-    }
-    const int incl = buf[cur][tid];
-    total = buf[cur][JP_THREADS - 1];
-    __syncthreads();
-    return incl - v;
-}
-
 TUP_DEVICE int jp_to_u8(float x) { return (int)fminf(fmaxf(x * 255.0f, 0.0f), 255.0f); }      // tensor_to_frames' rule (image_io.hip)
 
 // one pixel as bytes; exactly one of u8 (HWC) and f32 (CHW) is set, both already at the image
@@ -281,7 +261,7 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_segment_kernel(const uint8_t*
             if (run) nbits += (int)(sh.ac[tab][0] >> 16);
         }
         int chunk_bits;
-        const int at = jp_scan(nbits, sh.scan, tid, chunk_bits);
+        const int at = dg_scan256(nbits, sh.scan, tid, chunk_bits);
         const int total = open_n + chunk_bits;
         const bool last = c0 + mpc >= m_end;
         for (int i = tid; i < ((total + 7 + 31) >> 5) + 1; i += JP_THREADS) sh.bits[i] = i == 0 ? open_bits << 24 : 0u;
@@ -320,7 +300,7 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_segment_kernel(const uint8_t*
         int ff = 0;
         for (int i = i0; i < i1; ++i) ff += ((sh.bits[i >> 2] >> (24 - 8 * (i & 3))) & 255u) == 255u;
         int ff_total;
-        const int ff_before = jp_scan(ff, sh.scan, tid, ff_total);
+        const int ff_before = dg_scan256(ff, sh.scan, tid, ff_total);
         if (WRITE) {
             long long o = seg_at + done + i0 + ff_before;
             for (int i = i0; i < i1; ++i) {
@@ -361,7 +341,7 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_scan_kernel(const int* __rest
         int total;
         const int v = s < S ? sizes[(size_t)b * S + s] : 0;
         // a tile's sum stays below 2^31 unless the file is beyond any capacity: then the length is -1 and the offsets are not used
-        const int before = jp_scan(v, buf, tid, total);
+        const int before = dg_scan256(v, buf, tid, total);
         if (s < S) offsets[(size_t)b * S + s] = (int)min(max(base + before, 0LL), 0x7fffffffLL);
         base = total < 0 ? capacity + 1 : min(base + total, capacity + 1);
     }

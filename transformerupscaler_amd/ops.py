@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import re
 import struct
 
 import numpy as np
@@ -1591,6 +1592,238 @@ def jpeg_files(data, lengths):
         raise ValueError(f"jpeg_files: image {[i for i, v in enumerate(n) if v < 0][0]} did not fit its row of {data.shape[1]} bytes")
     host = data.cpu().numpy()
     return [host[i, :v].tobytes() for i, v in enumerate(n)]
+
+
+# ---- baseline JPEG decoding of a batch (csrc/jpeg_decode.hip) ----
+_JPEG_LAYOUT = {"4:4:4": 0, "4:2:0": 2, "grey": 4}
+_JPEG_DEC_REC = struct.Struct("<ii4s4s384s1088s")          # JdImage: scan_off, scan_len, td[4], ta[4], qt[3][64] uint16, huff[4][272]
+_JPEG_SOF = {0xC1: "extended sequential (SOF1)", 0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "differential sequential (SOF5)",
+             0xC6: "differential progressive (SOF6)", 0xC7: "differential lossless (SOF7)", 0xC9: "arithmetic-coded sequential (SOF9)",
+             0xCA: "arithmetic-coded progressive (SOF10)", 0xCB: "arithmetic-coded lossless (SOF11)", 0xCD: "arithmetic-coded differential (SOF13)",
+             0xCE: "arithmetic-coded differential progressive (SOF14)", 0xCF: "arithmetic-coded differential lossless (SOF15)",
+             0xCC: "arithmetic coding conditioning (DAC)"}
+_JPEG_NEXT_MARKER = re.compile(rb"\xff[^\x00\xd0-\xd7\xff]")
+
+
+def jpeg_parse(data):
+    """The marker segments of a baseline JPEG file, walked on the host without a library: a dict of H, W, components (1 or 3),
+    subsampling ("4:4:4", "4:2:0" or "grey"), quant_tables {id: 64 values in natural order}, huffman_tables {(class, id): (the 16
+    counts, the symbols)} with class 0 = DC and 1 = AC, and per component component_ids, quant_selectors, dc_selectors,
+    ac_selectors; restart_interval in MCUs (0 = none) and scan = (first byte, end) of the entropy-coded data.  APPn and COM segments
+    are skipped.  Everything `jpeg_decode` does not decode is a ValueError that names the reason: any SOFn but SOF0, a precision other
+    than 8 bits, 16-bit quantisation tables, samplings other than the three above, four components, more than one scan or a scan
+    with Ss / Se / Ah / Al other than 0 / 63 / 0 / 0, an Adobe segment whose transform is not YCbCr, component ids libjpeg reads as
+    RGB, a table that is selected but missing, Huffman counts that are no prefix code, and a file that ends before SOS."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise TypeError(f"jpeg_parse: a file is bytes, got {type(data)}")
+    data = bytes(data)
+    if data[:2] != b"\xff\xd8":
+        raise ValueError("jpeg_parse: not a JPEG file (no SOI)")
+    n, i = len(data), 2
+    quant, huff, frame, interval, jfif, adobe = {}, {}, None, 0, False, None
+    while True:
+        if i + 4 > n:
+            raise ValueError("jpeg_parse: the file ends before SOS")
+        if data[i] != 0xFF:
+            raise ValueError(f"jpeg_parse: no marker at byte {i}")
+        m = data[i + 1]
+        if m == 0xFF:                                  # fill byte
+            i += 1
+            continue
+        if m == 0x01 or 0xD0 <= m <= 0xD8:             # markers without a length
+            i += 2
+            continue
+        if m == 0xD9:
+            raise ValueError("jpeg_parse: the file ends before SOS")
+        length = int.from_bytes(data[i + 2:i + 4], "big")
+        if length < 2 or i + 2 + length > n:
+            raise ValueError("jpeg_parse: the file ends before SOS (a marker segment is cut short)")
+        p = data[i + 4:i + 2 + length]
+        i += 2 + length
+        if m in _JPEG_SOF:
+            raise ValueError(f"jpeg_parse: {_JPEG_SOF[m]} is not decoded, only baseline (SOF0)")
+        if m == 0xC0:
+            if frame is not None:
+                raise ValueError("jpeg_parse: two frame headers")
+            if len(p) < 6 or len(p) != 6 + 3 * p[5]:
+                raise ValueError("jpeg_parse: SOF0 of the wrong length")
+            if p[0] != 8:
+                raise ValueError(f"jpeg_parse: {p[0]}-bit precision is not decoded, only 8-bit")
+            H, W = int.from_bytes(p[1:3], "big"), int.from_bytes(p[3:5], "big")
+            if H < 1 or W < 1:
+                raise ValueError(f"jpeg_parse: an image of {H} x {W}")
+            if p[5] == 4:
+                raise ValueError("jpeg_parse: four components (CMYK / YCCK) are not decoded")
+            if p[5] not in (1, 3):
+                raise ValueError(f"jpeg_parse: {p[5]} components are not decoded, only 1 or 3")
+            frame = (H, W, [(p[6 + 3 * c], p[7 + 3 * c], p[8 + 3 * c]) for c in range(p[5])])
+        elif m == 0xDB:
+            k = 0
+            while k < len(p):
+                if p[k] >> 4:
+                    raise ValueError("jpeg_parse: 16-bit quantisation tables are not decoded")
+                if (p[k] & 15) > 3 or k + 65 > len(p):
+                    raise ValueError("jpeg_parse: DQT of the wrong length or table number")
+                t = [0] * 64
+                for z in range(64):
+                    t[JPEG_ZIGZAG[z]] = p[k + 1 + z]
+                quant[p[k] & 15] = tuple(t)
+                k += 65
+        elif m == 0xC4:
+            k = 0
+            while k < len(p):
+                if k + 17 > len(p) or (p[k] >> 4) > 1 or (p[k] & 15) > 1:
+                    raise ValueError("jpeg_parse: DHT of the wrong length, class or table number (baseline has tables 0 and 1)")
+                counts = tuple(p[k + 1:k + 17])
+                code = 0
+                for bits, c in enumerate(counts, 1):
+                    code += c
+                    if code > (1 << bits):
+                        raise ValueError(f"jpeg_parse: a Huffman table is not a valid prefix code ({c} codes of {bits} bits are more than are left)")
+                    code <<= 1
+                total = sum(counts)
+                if total > 256 or k + 17 + total > len(p):
+                    raise ValueError("jpeg_parse: DHT of the wrong length")
+                huff[(p[k] >> 4, p[k] & 15)] = (counts, tuple(p[k + 17:k + 17 + total]))
+                k += 17 + total
+        elif m == 0xDD:
+            if len(p) != 2:
+                raise ValueError("jpeg_parse: DRI of the wrong length")
+            interval = int.from_bytes(p, "big")
+        elif m == 0xE0 and p[:5] == b"JFIF\0":
+            jfif = True
+        elif m == 0xEE and p[:5] == b"Adobe" and len(p) >= 12:
+            adobe = p[11]
+        elif m == 0xDA:
+            break
+    if frame is None:
+        raise ValueError("jpeg_parse: SOS before SOF0")
+    H, W, comps = frame
+    ns = p[0] if p else 0
+    if len(p) != 4 + 2 * ns:
+        raise ValueError("jpeg_parse: SOS of the wrong length")
+    if ns != len(comps) or [p[1 + 2 * c] for c in range(ns)] != [c[0] for c in comps]:
+        raise ValueError(f"jpeg_parse: more than one scan (the first holds {ns} of {len(comps)} components)")
+    if tuple(p[1 + 2 * ns:]) != (0, 63, 0):
+        raise ValueError(f"jpeg_parse: a scan with Ss, Se, Ah/Al = {tuple(p[1 + 2 * ns:])}, not 0, 63, 0")
+    ids = tuple(c[0] for c in comps)
+    if len(comps) == 3:
+        if adobe is not None and adobe != 1:
+            raise ValueError(f"jpeg_parse: Adobe transform {adobe} (not YCbCr) is not decoded")
+        if adobe is None and not jfif and ids == (0x52, 0x47, 0x42):
+            raise ValueError("jpeg_parse: component ids 'R', 'G', 'B' without JFIF (libjpeg reads them as RGB) are not decoded")
+        samp = tuple(c[1] for c in comps)
+        if samp == (0x11, 0x11, 0x11):
+            sub = "4:4:4"
+        elif samp == (0x22, 0x11, 0x11):
+            sub = "4:2:0"
+        else:
+            raise ValueError("jpeg_parse: sampling factors " + ", ".join(f"{s >> 4}x{s & 15}" for s in samp) + " are not decoded, only 4:4:4 and 4:2:0")
+    else:
+        sub = "grey"
+    dc, ac = tuple(p[2 + 2 * c] >> 4 for c in range(ns)), tuple(p[2 + 2 * c] & 15 for c in range(ns))
+    for c, (_, _, tq) in enumerate(comps):
+        if tq not in quant:
+            raise ValueError(f"jpeg_parse: missing quantisation table {tq}")
+        if dc[c] > 1 or ac[c] > 1:
+            raise ValueError("jpeg_parse: a Huffman table number above 1 (baseline has tables 0 and 1)")
+        if (0, dc[c]) not in huff or (1, ac[c]) not in huff:
+            raise ValueError(f"jpeg_parse: missing Huffman table (DC {dc[c]} or AC {ac[c]})")
+    nxt = _JPEG_NEXT_MARKER.search(data, i)
+    if nxt is not None and (data[nxt.start() + 1] in (0xDA, 0xC4, 0xDB, 0xDD) or 0xC0 <= data[nxt.start() + 1] <= 0xCF):
+        raise ValueError("jpeg_parse: more than one scan")
+    end = data.rfind(b"\xff\xd9", i)
+    return {"H": H, "W": W, "components": len(comps), "subsampling": sub, "quant_tables": quant, "huffman_tables": huff,
+            "component_ids": ids, "quant_selectors": tuple(c[2] for c in comps), "dc_selectors": dc, "ac_selectors": ac,
+            "restart_interval": interval, "scan": (i, end if end >= 0 else n)}
+
+
+def _jpeg_decode_geometry(H, W, layout, interval):
+    """(segments, workspace bytes per image): the twin of jd_geometry (csrc/jpeg_decode.hip)."""
+    m = 16 if layout == 2 else 8
+    mw, mh = (W + m - 1) // m, (H + m - 1) // m
+    S = (mw * mh + interval - 1) // interval if interval else mh
+    return S, mw * m * mh * m + (0 if layout == 4 else 2 * mw * 8 * mh * 8)
+
+
+def _jpeg_decode_record(info, data, scan_off):
+    """The 1488 bytes the kernels read about one image (struct JdImage)."""
+    nc = info["components"]
+    sel = lambda v: bytes(v) + bytes(4 - nc)
+    qt = b"".join(struct.pack("<64H", *info["quant_tables"][info["quant_selectors"][min(c, nc - 1)]]) for c in range(3))
+    spec = b""
+    for key in ((0, 0), (0, 1), (1, 0), (1, 1)):
+        counts, symbols = info["huffman_tables"].get(key, ((0,) * 16, ()))
+        spec += bytes(counts) + bytes(symbols) + bytes(256 - len(symbols))
+    start, end = info["scan"]
+    return _JPEG_DEC_REC.pack(scan_off, end - start, sel(info["dc_selectors"]), sel(info["ac_selectors"]), qt, spec)
+
+
+def jpeg_decode(files, to_tensor=False, out=None):
+    """Baseline JPEG files decoded on the GPU in three launches.  files: bytes, or a sequence of bytes whose images share H, W,
+    subsampling and restart interval (quantisation and Huffman tables are each image's own).  Returns (frames, status): frames uint8
+    [B][H][W][3] RGB, pixel for pixel ``np.asarray(Image.open(io.BytesIO(f)).convert("RGB"))`` (a one-component file gives R = G = B);
+    with to_tensor=True fp32 [B][3][H][W], bit-equal to `frames_to_tensor` of the uint8 result and written by the last kernel.
+    status int32 [B] on the device: 0 for a scan that decoded completely; otherwise the file is damaged and its pixels are
+    unspecified (the other images are unaffected).  out=: the caller's frames tensor.  One upload (the image records and the scans),
+    no read-back, no synchronisation.  Restart markers make a file fast: its intervals are walked in parallel; a file without them
+    costs one serial walk.  Everything is validated before any launch; what `jpeg_parse` refuses is refused here."""
+    if isinstance(files, (bytes, bytearray, memoryview)):
+        files = [files]
+    try:
+        files = list(files)
+    except TypeError:
+        raise TypeError(f"jpeg_decode: files must be bytes or a sequence of bytes, got {type(files)}") from None
+    B = len(files)
+    if not 1 <= B <= 65535:
+        raise ValueError(f"jpeg_decode: {B} images in one call (1..65535)")
+    if any(not isinstance(f, (bytes, bytearray, memoryview)) for f in files):
+        raise TypeError("jpeg_decode: files must be bytes or a sequence of bytes")
+    infos = [jpeg_parse(f) for f in files]
+    key = lambda s: (s["H"], s["W"], s["subsampling"], s["restart_interval"])
+    for b, s in enumerate(infos):
+        if key(s) != key(infos[0]):
+            raise ValueError(f"jpeg_decode: the images of a call share H, W, subsampling and restart interval; image 0 has {key(infos[0])}, "
+                             f"image {b} has {key(s)}")
+    H, W, sub, interval = key(infos[0])
+    layout = _JPEG_LAYOUT[sub]
+    shape, dtype = ((B, 3, H, W), F32) if to_tensor else ((B, H, W, 3), torch.uint8)
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"jpeg_decode: out must be a contiguous {dtype} tensor of shape {shape}, got {getattr(out, 'dtype', type(out))} "
+                             f"{tuple(getattr(out, 'shape', ()))}")
+        _nv12_on_gpu("jpeg_decode", out, "out")
+    elif not torch.cuda.is_available():
+        raise RuntimeError("jpeg_decode: the HIP path needs a GPU (no CPU fallback)")
+    S, ws = _jpeg_decode_geometry(H, W, layout, interval)
+    offs, at = [], B * _JPEG_DEC_REC.size                                 # records, then the scans, each at a multiple of 16
+    for s in infos:
+        offs.append(at)
+        at += (s["scan"][1] - s["scan"][0] + 15) & ~15
+    scans_bytes = at - B * _JPEG_DEC_REC.size
+    if scans_bytes > 0x7fff0000:
+        raise ValueError(f"jpeg_decode: {scans_bytes} bytes of scans in one call (below 2^31)")
+    lib = _lib.load()
+    if lib.tup_jpeg_decode_segments(H, W, layout, interval) != S:
+        raise RuntimeError("jpeg_decode: the library counts other segments than the binding")
+    host = bytearray(max(at, 16))
+    for b, (s, f) in enumerate(zip(infos, files)):
+        host[b * _JPEG_DEC_REC.size:(b + 1) * _JPEG_DEC_REC.size] = _jpeg_decode_record(s, f, offs[b] - B * _JPEG_DEC_REC.size)
+        host[offs[b]:offs[b] + s["scan"][1] - s["scan"][0]] = f[s["scan"][0]:s["scan"][1]]
+    dev = out.device if out is not None else torch.device("cuda", _cur_dev())
+    up = torch.frombuffer(host, dtype=torch.uint8).to(dev)                 # the one upload
+    segs = torch.empty((B, S, 8), dtype=torch.int32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    work = torch.empty((B, ws), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=dev)
+    records, scans = up.data_ptr(), up.data_ptr() + B * _JPEG_DEC_REC.size
+    _lib.call("tup_jpeg_decode_index", records, scans, scans_bytes, B, H, W, layout, interval, S, segs.data_ptr(), status.data_ptr(), _stream())
+    _lib.call("tup_jpeg_decode_blocks", records, scans, scans_bytes, B, H, W, layout, interval, S, segs.data_ptr(), status.data_ptr(),
+              work.data_ptr(), ws, _stream())
+    _lib.call("tup_jpeg_decode_finish", work.data_ptr(), ws, B, H, W, layout, None if to_tensor else out.data_ptr(),
+              out.data_ptr() if to_tensor else None, _stream())
+    return out, status
 
 
 # ---- WindowTransformer (SURVEY 8(f) rank 2): the patch GEMMs in window layout, without reflect padding ----
