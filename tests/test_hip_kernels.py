@@ -206,16 +206,18 @@ def test_gemm_wgrad_and_colsum(dev, M, NI, NJ, pd, qd):
     close(gb, bf(P).sum(0), 2e-3 * (M ** 0.5), 1e-3, "bias grad (fused)")
 
 
-def test_gemm_gelu_bwd_and_fp32_a(dev):
+@pytest.mark.parametrize("adtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("K", [192, 128])          # the panel kernel and the K-streaming one
+def test_gemm_gelu_bwd_and_fp32_a(dev, K, adtype):
     from transformerupscaler_amd import ops, packing
-    M, N, K = 192, 768, 192
+    M, N = 192, 768
     a, w, pre = rnd((M, K), 32), rnd((N, K), 33, 0.08), rnd((M, N), 34, 2.0)
     wp = packing.pack_linear(w).to(dev)
     prer = bf(pre).requires_grad_(True)
     torch.nn.functional.gelu(prer).backward(F.linear(bf(a), bf(w)))
-    got = ops.gemm_tokens(a.to(dev), wp, None, "gelu_bwd", aux=pre.to(torch.bfloat16).to(dev))      # fp32 A
+    got = ops.gemm_tokens(a.to(adtype).to(dev), wp, None, "gelu_bwd", aux=pre.to(torch.bfloat16).to(dev))
     close(got, prer.grad, 1e-2, 1e-2, "gelu bwd epilogue")
-    close(ops.gemm_tokens(a.to(dev), wp, None, "bf16"), F.linear(bf(a), bf(w)), 1e-2, 1e-2, "fp32 A, no bias")
+    close(ops.gemm_tokens(a.to(adtype).to(dev), wp, None, "bf16"), F.linear(bf(a), bf(w)), 1e-2, 1e-2, "fp32 / bf16 A, no bias")
 
 
 def test_layernorm_bwd(dev):

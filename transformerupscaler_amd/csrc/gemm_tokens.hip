@@ -14,7 +14,6 @@
 // Weight rows are pre-permuted on the host inside every 64-row group (row ct*16+4g+e holds
 // feature g*16+ct*4+e) to make that true.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -66,11 +65,23 @@ TUP_DEVICE TokPos token_of_row(int m, const GemmParams& p) {
     return t;
 }
 
-// Epilogue of one token row: the lane holds v[16] = features n0 + g*16 .. +15 of row m (accumulators), bvec = the
-// matching bias values.  Shared by the K-streaming kernel and the A-resident panel kernel.
+// 16 consecutive bf16 travel as eight 32-bit words in two u32x4: word q (of vector q >> 2) holds elements 2q (low half) and 2q + 1
+// (high half).  The word is picked at the place of use, (q < 4) ? lo[q & 3] : hi[q & 3]: behind a function the same expression
+// makes the compiler schedule the GELU-gradient and merge epilogues differently.
+TUP_DEVICE float bf16_even(uint32_t w) { return __builtin_bit_cast(float, w << 16); }
+TUP_DEVICE float bf16_odd(uint32_t w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
+TUP_DEVICE void store_bf16x16(bf16_t* o, const uint32_t* pk)
+{
+    *reinterpret_cast<u32x4*>(o) = u32x4{pk[0], pk[1], pk[2], pk[3]};
+    *reinterpret_cast<u32x4*>(o + 8) = u32x4{pk[4], pk[5], pk[6], pk[7]};
+}
+
+// The epilogues that read nothing, for one token row: the lane holds v[16] = features n0 + g*16 .. +15 of row m (accumulators),
+// bvec = the matching bias values.  Every kernel reaches them through epi_finish below.
 template <int EPI>
 TUP_DEVICE void gemm_store_row(const GemmParams& p, int m, int n0, int g, const float (&v)[16], const float (&bvec)[16])
 {
+    static_assert(EPI == E_BF16 || EPI == E_GELU_BF16 || EPI == E_PATCH_EMBED, "the reading epilogues live in epi_prefetch / epi_finish");
     const int nb = n0 + g * 16;
     if constexpr (EPI == E_BF16 || EPI == E_GELU_BF16) {
         uint32_t pk[8], ppre[8];
@@ -86,32 +97,10 @@ TUP_DEVICE void gemm_store_row(const GemmParams& p, int m, int n0, int g, const 
             pk[q] = pack_bf16x2(a, b);
         }
         if constexpr (EPI == E_GELU_BF16) {
-            if (p.skip) {
-                bf16_t* po = const_cast<bf16_t*>(p.skip) + (size_t)m * p.ldo + nb;
-                *reinterpret_cast<u32x4*>(po) = u32x4{ppre[0], ppre[1], ppre[2], ppre[3]};
-                *reinterpret_cast<u32x4*>(po + 8) = u32x4{ppre[4], ppre[5], ppre[6], ppre[7]};
-            }
+            if (p.skip) store_bf16x16(const_cast<bf16_t*>(p.skip) + (size_t)m * p.ldo + nb, ppre);
         }
-        bf16_t* o = (bf16_t*)p.out + (size_t)m * p.ldo + nb;
-        *reinterpret_cast<u32x4*>(o) = u32x4{pk[0], pk[1], pk[2], pk[3]};
-        *reinterpret_cast<u32x4*>(o + 8) = u32x4{pk[4], pk[5], pk[6], pk[7]};
-    } else if constexpr (EPI == E_RES_F32) {
-        float* o = (float*)p.out + (size_t)m * p.ldo + nb;
-        const float* rs = p.res + (size_t)m * p.ldo + nb;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 rv = *reinterpret_cast<const f32x4*>(rs + 4 * q);
-            f32x4 ov;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float t = v[4 * q + e] + bvec[4 * q + e];
-                if (p.drop_thresh)      // proj_drop / mlp Dropout (model.py:132,150): element index m*ldo + n
-                    t *= drop_scale(p.drop_seed, (uint32_t)m * (uint32_t)p.ldo + nb + 4 * q + e, p.drop_thresh, p.drop_inv_keep);
-                ov[e] = t + rv[e];
-            }
-            *reinterpret_cast<f32x4*>(o + 4 * q) = ov;
-        }
-    } else if constexpr (EPI == E_PATCH_EMBED) {
+        store_bf16x16((bf16_t*)p.out + (size_t)m * p.ldo + nb, pk);
+    } else {
         // zero-padded tokens are exact zeros (no bias): model.py:273-280
         const TokPos t = token_of_row(m, p);
         float* o = (float*)p.out + (size_t)m * p.ldo + nb;
@@ -127,48 +116,9 @@ TUP_DEVICE void gemm_store_row(const GemmParams& p, int m, int n0, int g, const 
             }
             *reinterpret_cast<f32x4*>(o + 4 * q) = ov;
         }
-    } else if constexpr (EPI == E_GELU_BWD) {
-        // out = acc * gelu'(pre), pre = saved fc1 output before the activation (model.py:148)
-        const bf16_t* pr = p.skip + (size_t)m * p.ldo + nb;
-        const u32x4 a0 = *reinterpret_cast<const u32x4*>(pr), a1 = *reinterpret_cast<const u32x4*>(pr + 8);
-        uint32_t pk[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const uint32_t sw = (q < 4) ? a0[q & 3] : a1[q & 3];
-            const float xa = __builtin_bit_cast(float, sw << 16), xb = __builtin_bit_cast(float, sw & 0xffff0000u);
-            pk[q] = pack_bf16x2(v[2 * q] * gelu_erf_grad(xa), v[2 * q + 1] * gelu_erf_grad(xb));
-        }
-        bf16_t* o = (bf16_t*)p.out + (size_t)m * p.ldo + nb;
-        *reinterpret_cast<u32x4*>(o) = u32x4{pk[0], pk[1], pk[2], pk[3]};
-        *reinterpret_cast<u32x4*>(o + 8) = u32x4{pk[4], pk[5], pk[6], pk[7]};
-    } else {  // E_UNEMBED: n tile = patch pixel (i, j); features = base channel o
-        const TokPos t = token_of_row(m, p);
-        const int pix = n0 >> 6, i = pix >> 3, j = pix & 7;
-        const int py = t.ty * 8 + i, px = t.tx * 8 + j;
-        if (!t.valid || py >= p.H || px >= p.W) return;
-        const size_t off = (((size_t)t.b * p.H + py) * p.W + px) * 64 + g * 16;
-        u32x4 s0 = {0u, 0u, 0u, 0u}, s1 = {0u, 0u, 0u, 0u};
-        if (p.skip) {
-            s0 = *reinterpret_cast<const u32x4*>(p.skip + off);
-            s1 = *reinterpret_cast<const u32x4*>(p.skip + off + 8);
-        }
-        uint32_t pk[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const uint32_t sw = (q < 4) ? s0[q & 3] : s1[q & 3];
-            const float sa = __builtin_bit_cast(float, sw << 16);
-            const float sb = __builtin_bit_cast(float, sw & 0xffff0000u);
-            pk[q] = pack_bf16x2(v[2 * q] + bvec[2 * q] + sa, v[2 * q + 1] + bvec[2 * q + 1] + sb);
-        }
-        bf16_t* o = (bf16_t*)p.out + off;
-        *reinterpret_cast<u32x4*>(o) = u32x4{pk[0], pk[1], pk[2], pk[3]};
-        *reinterpret_cast<u32x4*>(o + 8) = u32x4{pk[4], pk[5], pk[6], pk[7]};
     }
 }
 
-// The same epilogues split in two for the panel kernel: the operands an epilogue READS (residual row, skip pixels,
-// saved pre-activation) are requested before the K loop of the tile and consumed after it, so their HBM round trip
-// hides under the MFMAs instead of being paid between the K loop and the stores of every 64-column tile.
 // store sink for rows outside the output (keeps the number of store instructions per wave fixed); never read
 __device__ __attribute__((aligned(16))) unsigned int tup_gemm_sink[64 * 8];
 // 16-byte global loads the compiler does not track (no s_waitcnt of its own): the caller waits with a counted vmcnt and must
@@ -184,11 +134,32 @@ TUP_DEVICE u32x4 global_load_b128_async_16(const void* ptr) {
     return v;
 }
 
+// The epilogues that READ memory (residual row, skip pixels, saved pre-activation), stated once and in two halves: epi_prefetch
+// requests the operands, epi_finish consumes them and stores.  The panel kernel calls the first before the K loop of a tile and the
+// second after it, so the HBM round trip hides under the MFMAs instead of being paid between the K loop and the stores of every
+// 64-column tile; the K-streaming kernel and patch_embed_kernel call them back to back.
 struct EpiPre {
     u32x4 a[6];
     size_t off;          // E_UNEMBED: element offset of this lane's 16 channels
     bool ok;
 };
+
+// E_UNEMBED, two neighbouring channels: (acc + bias) + skip as one bf16 pair; sw = the pair of `skip` (0 without one).  The panel
+// kernel's counted-vmcnt tile loop states its own loads, waits and stores and takes only this arithmetic.
+TUP_DEVICE uint32_t unembed_pair(float va, float vb, float ba, float bb, uint32_t sw)
+{
+    return pack_bf16x2(va + ba + bf16_even(sw), vb + bb + bf16_odd(sw));
+}
+
+// E_UNEMBED / E_UNEMBED_MERGE: n tile = patch pixel (i, j), features = base channel o: where row m's pixel lies in the map, if it does
+TUP_DEVICE void unembed_pixel(const GemmParams& p, int m, int n0, int g, EpiPre& r)
+{
+    const TokPos t = token_of_row(m, p);
+    const int pix = n0 >> 6, i = pix >> 3, j = pix & 7;
+    const int py = t.ty * 8 + i, px = t.tx * 8 + j;
+    r.ok = t.valid && py < p.H && px < p.W;
+    r.off = (((size_t)t.b * p.H + py) * p.W + px) * 64 + g * 16;
+}
 
 template <int EPI>
 TUP_DEVICE EpiPre epi_prefetch(const GemmParams& p, int m, int n0, int g)
@@ -201,14 +172,11 @@ TUP_DEVICE EpiPre epi_prefetch(const GemmParams& p, int m, int n0, int g)
 #pragma unroll
         for (int q = 0; q < 4; ++q) r.a[q] = *reinterpret_cast<const u32x4*>(rs + 4 * q);
     } else if constexpr (EPI == E_GELU_BWD) {
+        // out = acc * gelu'(pre), pre = saved fc1 output before the activation (model.py:148)
         const bf16_t* pr = p.skip + (size_t)m * p.ldo + nb;
         r.a[0] = *reinterpret_cast<const u32x4*>(pr); r.a[1] = *reinterpret_cast<const u32x4*>(pr + 8);
     } else if constexpr (EPI == E_UNEMBED) {
-        const TokPos t = token_of_row(m, p);
-        const int pix = n0 >> 6, i = pix >> 3, j = pix & 7;
-        const int py = t.ty * 8 + i, px = t.tx * 8 + j;
-        r.ok = t.valid && py < p.H && px < p.W;
-        r.off = (((size_t)t.b * p.H + py) * p.W + px) * 64 + g * 16;
+        unembed_pixel(p, m, n0, g, r);
         r.a[0] = u32x4{0u, 0u, 0u, 0u}; r.a[1] = u32x4{0u, 0u, 0u, 0u};
         if (p.skip && r.ok) {
             r.a[0] = *reinterpret_cast<const u32x4*>(p.skip + r.off);
@@ -217,11 +185,7 @@ TUP_DEVICE EpiPre epi_prefetch(const GemmParams& p, int m, int n0, int g)
     } else if constexpr (EPI == E_UNEMBED_MERGE) {
         // training: the gradient merge at `feat` (model.py:264,268,308 fan-out + conv2's ReLU) in the epilogue of patch_embed's input
         // gradient: out = (acc + skip + skip2) * (relu_src > 0).  Every map is the UNPADDED H x W map (H, W multiples of 8).
-        const TokPos t = token_of_row(m, p);
-        const int pix = n0 >> 6, i = pix >> 3, j = pix & 7;
-        const int py = t.ty * 8 + i, px = t.tx * 8 + j;
-        r.ok = t.valid && py < p.H && px < p.W;
-        r.off = (((size_t)t.b * p.H + py) * p.W + px) * 64 + g * 16;
+        unembed_pixel(p, m, n0, g, r);
 #pragma unroll
         for (int q = 0; q < 6; ++q) r.a[q] = u32x4{0u, 0u, 0u, 0u};
         if (r.ok) {
@@ -246,7 +210,7 @@ TUP_DEVICE void epi_finish(const GemmParams& p, int m, int n0, int g, const floa
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float t = v[4 * q + e] + bvec[4 * q + e];
-                if (p.drop_thresh)
+                if (p.drop_thresh)      // proj_drop / mlp Dropout (model.py:132,150): element index m*ldo + n
                     t *= drop_scale(p.drop_seed, (uint32_t)m * (uint32_t)p.ldo + nb + 4 * q + e, p.drop_thresh, p.drop_inv_keep);
                 ov[e] = t + rv[e];
             }
@@ -257,25 +221,17 @@ TUP_DEVICE void epi_finish(const GemmParams& p, int m, int n0, int g, const floa
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const uint32_t sw = (q < 4) ? pre.a[0][q & 3] : pre.a[1][q & 3];
-            const float xa = __builtin_bit_cast(float, sw << 16), xb = __builtin_bit_cast(float, sw & 0xffff0000u);
+            const float xa = bf16_even(sw), xb = bf16_odd(sw);
             pk[q] = pack_bf16x2(v[2 * q] * gelu_erf_grad(xa), v[2 * q + 1] * gelu_erf_grad(xb));
         }
-        bf16_t* o = (bf16_t*)p.out + (size_t)m * p.ldo + nb;
-        *reinterpret_cast<u32x4*>(o) = u32x4{pk[0], pk[1], pk[2], pk[3]};
-        *reinterpret_cast<u32x4*>(o + 8) = u32x4{pk[4], pk[5], pk[6], pk[7]};
+        store_bf16x16((bf16_t*)p.out + (size_t)m * p.ldo + nb, pk);
     } else if constexpr (EPI == E_UNEMBED) {
         if (!pre.ok) return;
         uint32_t pk[8];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const uint32_t sw = (q < 4) ? pre.a[0][q & 3] : pre.a[1][q & 3];
-            const float sa = __builtin_bit_cast(float, sw << 16);
-            const float sb = __builtin_bit_cast(float, sw & 0xffff0000u);
-            pk[q] = pack_bf16x2(v[2 * q] + bvec[2 * q] + sa, v[2 * q + 1] + bvec[2 * q + 1] + sb);
-        }
-        bf16_t* o = (bf16_t*)p.out + pre.off;
-        *reinterpret_cast<u32x4*>(o) = u32x4{pk[0], pk[1], pk[2], pk[3]};
-        *reinterpret_cast<u32x4*>(o + 8) = u32x4{pk[4], pk[5], pk[6], pk[7]};
+        for (int q = 0; q < 8; ++q)          // epi_prefetch left zeros where there is no skip
+            pk[q] = unembed_pair(v[2 * q], v[2 * q + 1], bvec[2 * q], bvec[2 * q + 1], (q < 4) ? pre.a[0][q & 3] : pre.a[1][q & 3]);
+        store_bf16x16((bf16_t*)p.out + pre.off, pk);
     } else if constexpr (EPI == E_UNEMBED_MERGE) {
         if (!pre.ok) return;
         uint32_t pk[8];
@@ -284,16 +240,13 @@ TUP_DEVICE void epi_finish(const GemmParams& p, int m, int n0, int g, const floa
             const uint32_t s1 = (q < 4) ? pre.a[0][q & 3] : pre.a[1][q & 3], s2 = (q < 4) ? pre.a[2][q & 3] : pre.a[3][q & 3];
             const uint32_t mw = (q < 4) ? pre.a[4][q & 3] : pre.a[5][q & 3];
             // (a + b) + this GEMM's value, which stays fp32 here (feat_grad_combine_kernel read it back rounded to bf16)
-            float ra = __builtin_bit_cast(float, s1 << 16) + __builtin_bit_cast(float, s2 << 16);
-            float rb = __builtin_bit_cast(float, s1 & 0xffff0000u) + __builtin_bit_cast(float, s2 & 0xffff0000u);
+            float ra = bf16_even(s1) + bf16_even(s2), rb = bf16_odd(s1) + bf16_odd(s2);
             ra += v[2 * q]; rb += v[2 * q + 1];
-            if (!(__builtin_bit_cast(float, mw << 16) > 0.f)) ra = 0.f;
-            if (!(__builtin_bit_cast(float, mw & 0xffff0000u) > 0.f)) rb = 0.f;
+            if (!(bf16_even(mw) > 0.f)) ra = 0.f;
+            if (!(bf16_odd(mw) > 0.f)) rb = 0.f;
             pk[q] = pack_bf16x2(ra, rb);
         }
-        bf16_t* o = (bf16_t*)p.out + pre.off;
-        *reinterpret_cast<u32x4*>(o) = u32x4{pk[0], pk[1], pk[2], pk[3]};
-        *reinterpret_cast<u32x4*>(o + 8) = u32x4{pk[4], pk[5], pk[6], pk[7]};
+        store_bf16x16((bf16_t*)p.out + pre.off, pk);
     } else {
         gemm_store_row<EPI>(p, m, n0, g, v, bvec);          // nothing to read ahead
     }
@@ -309,6 +262,20 @@ TUP_DEVICE void gemm_load_bias(const GemmParams& p, int n0, int g, bool unembed,
 #pragma unroll
         for (int e = 0; e < 4; ++e) bvec[4 * q + e] = t[e];
     }
+}
+
+// A_PATCH gather: pixel (py, px) of a token's patch.  Beyond the H x W map it is reflected back (patch_embed, model.py:256-261) or,
+// without reflect, contributes zeros: returns false then (py = px = 0, so that an address formed anyway stays inside the map).
+TUP_DEVICE bool patch_gather_pixel(const GemmParams& p, int& py, int& px)
+{
+    if (p.reflect) {
+        if (py >= p.H) py = 2 * p.H - 2 - py;
+        if (px >= p.W) px = 2 * p.W - 2 - px;
+    } else if (py >= p.H || px >= p.W) {
+        py = 0; px = 0;
+        return false;
+    }
+    return true;
 }
 
 template <int AMODE, int EPI>
@@ -357,16 +324,11 @@ __global__ __launch_bounds__(256, 2) void gemm_tokens_kernel(const GemmParams p)
                 areg[2 * u] = avalid[u] ? *reinterpret_cast<const u32x4*>(s) : u32x4{0u, 0u, 0u, 0u};
                 areg[2 * u + 1] = avalid[u] ? *reinterpret_cast<const u32x4*>(s + 16) : u32x4{0u, 0u, 0u, 0u};
             } else {
-                // k chunk kc = patch pixel (i, j); reflect-pad rows/cols beyond the map (model.py:256-261)
+                // k chunk kc = patch pixel (i, j)
                 const int i = kc >> 3, j = kc & 7;
                 int py = apy[u] + i, px = apx[u] + j;
                 bool ok = avalid[u];
-                if (p.reflect) {
-                    if (py >= p.H) py = 2 * p.H - 2 - py;
-                    if (px >= p.W) px = 2 * p.W - 2 - px;
-                } else if (py >= p.H || px >= p.W) {
-                    ok = false; py = 0; px = 0;
-                }
+                if (!patch_gather_pixel(p, py, px)) ok = false;
                 const bf16_t* s = (const bf16_t*)p.A + (((size_t)abat[u] * p.H + py) * p.W + px) * 64 + achunk * 8;
                 areg[u] = ok ? *reinterpret_cast<const u32x4*>(s) : u32x4{0u, 0u, 0u, 0u};
             }
@@ -444,187 +406,23 @@ __global__ __launch_bounds__(256, 2) void gemm_tokens_kernel(const GemmParams p)
         for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[ct * 4 + e] = acc[tg][ct][e];
-        gemm_store_row<EPI>(p, m, n0, g, v, bvec);
+        epi_finish<EPI>(p, m, n0, g, v, bvec, epi_prefetch<EPI>(p, m, n0, g));
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// A-resident "panel" kernel for K = 192 (every Linear that reads the 192-wide token stream, and
-// patch_unembed): the [128][192] token tile is loaded ONCE per workgroup -- optionally through a fused
-// LayerNorm (A_LN) -- and stays in LDS while the workgroup walks all N/64 weight tiles, each streamed
-// global -> registers -> LDS one tile ahead.  The K-streaming kernel above pays a global-load round trip
-// per 16 MFMAs at K = 192 (3 iterations per output tile) and was latency-bound; here it is paid once
-// per 128 rows.  LDS: 48 KB (A) + 24 KB (W) -> two workgroups per CU.  Fragment reads are hand-pipelined.
+// A-resident "panel" kernel for K = 192 (every Linear that reads the 192-wide token stream, and patch_unembed): one workgroup =
+// 128 token rows, loaded ONCE -- optionally through a fused LayerNorm (A_LN) -- and kept while the workgroup walks all N/64 weight
+// tiles.  The K-streaming kernel above pays a global-load round trip per 16 MFMAs at K = 192 (3 iterations per output tile) and
+// was latency-bound; here it is paid once per 128 rows.
+// The token operand never touches LDS: each lane loads its 32 rows directly in MFMA B-fragment order (token 16tg+pl, channels
+// 32*step + 8g .. +8; A_LN: statistics by two cross-lane-group shuffles) and keeps the 12 bf16x8 fragments in registers for all
+// weight tiles.  LDS holds only the weight stream: two 24 KB buffers filled by LDS-DMA one tile ahead, ONE workgroup barrier per
+// tile.  K loop: weight fragments two K-steps ahead, immediate-offset reads.  Epilogue operands are requested before the K loop
+// (epi_prefetch).  48 KB of LDS, <= 256 VGPRs: two 4-wave workgroups per CU.
 // ------------------------------------------------------------------------------------------------
 constexpr int PK = 192, PBM = 128;
-constexpr int PA_BYTES = 3 * PBM * 128, PW_BYTES = 3 * 64 * 128;
-
-template <int AMODE, int EPI>
-__global__ __launch_bounds__(256, 2) void gemm_panel_kernel(const GemmParams p)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* a_lds = smem;
-    char* w_lds = smem + PA_BYTES;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int g = lane >> 4, pl = lane & 15;
-    const int m0 = blockIdx.x * PBM;
-    const int ntiles = p.N / 64;
-
-    u32x4 wreg[6];
-    auto load_w = [&](int nt) {
-#pragma unroll
-        for (int u = 0; u < 6; ++u) {
-            const int idx = tid + u * 256;                  // 1536 chunks: row = idx / 24, c = idx % 24
-            const int row = idx / 24, c = idx - row * 24;
-            wreg[u] = *reinterpret_cast<const u32x4*>(p.Wt + (size_t)(nt * 64 + row) * PK + c * 8);
-        }
-    };
-    auto store_w = [&]() {
-#pragma unroll
-        for (int u = 0; u < 6; ++u) {
-            const int idx = tid + u * 256;
-            const int row = idx / 24, c = idx - row * 24;
-            *reinterpret_cast<u32x4*>(w_lds + (c >> 3) * (64 * 128) + swz128(row, c & 7)) = wreg[u];
-        }
-    };
-    load_w(0);
-
-    // ---- A tile prologue ----
-    if constexpr (AMODE == A_LN) {
-        const int sub = tid & 15;
-        f32x4 gm[3], bt[3];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            gm[q] = *reinterpret_cast<const f32x4*>(p.ln_gamma + q * 64 + sub * 4);
-            bt[q] = *reinterpret_cast<const f32x4*>(p.ln_beta + q * 64 + sub * 4);
-        }
-#pragma unroll 2
-        for (int pass = 0; pass < PBM / 16; ++pass) {
-            const int r = pass * 16 + (tid >> 4);
-            const int m = min(m0 + r, p.M - 1);
-            f32x4 v[3];
-            float sum = 0.f;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                v[q] = *reinterpret_cast<const f32x4*>((const float*)p.A + (size_t)m * p.lda + q * 64 + sub * 4);
-                sum += v[q][0] + v[q][1] + v[q][2] + v[q][3];
-            }
-#pragma unroll
-            for (int o = 8; o >= 1; o >>= 1) sum += __shfl_xor(sum, o);
-            const float mean = sum * (1.0f / PK);
-            float ss = 0.f;
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { const float d = v[q][e] - mean; ss += d * d; }
-#pragma unroll
-            for (int o = 8; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
-            const float rstd = rsqrtf(ss * (1.0f / PK) + 1e-5f);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                float o4[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o4[e] = (v[q][e] - mean) * rstd * gm[q][e] + bt[q][e];
-                *reinterpret_cast<u32x2*>(a_lds + q * (PBM * 128) + swz128(r, sub >> 1) + (sub & 1) * 8) =
-                    u32x2{pack_bf16x2(o4[0], o4[1]), pack_bf16x2(o4[2], o4[3])};
-            }
-        }
-    } else {
-#pragma unroll 4
-        for (int u = 0; u < 12; ++u) {
-            const int idx = tid + u * 256;                  // 3072 chunks of 8 elements: row = idx / 24
-            const int row = idx / 24, c = idx - row * 24;
-            const int m = min(m0 + row, p.M - 1);
-            u32x4 v;
-            if constexpr (AMODE == A_BF16) {
-                v = *reinterpret_cast<const u32x4*>((const bf16_t*)p.A + (size_t)m * p.lda + c * 8);
-            } else {
-                const float* src = (const float*)p.A + (size_t)m * p.lda + c * 8;
-                const f32x4 lo = *reinterpret_cast<const f32x4*>(src), hi = *reinterpret_cast<const f32x4*>(src + 4);
-                v = u32x4{pack_bf16x2(lo[0], lo[1]), pack_bf16x2(lo[2], lo[3]), pack_bf16x2(hi[0], hi[1]), pack_bf16x2(hi[2], hi[3])};
-            }
-            *reinterpret_cast<u32x4*>(a_lds + (c >> 3) * (PBM * 128) + swz128(row, c & 7)) = v;
-        }
-    }
-
-    const uint32_t a_tok0 = lds_addr(a_lds) + (uint32_t)swz128(32 * wave + pl, g);
-    const uint32_t a_tok1 = lds_addr(a_lds) + (uint32_t)swz128(32 * wave + 16 + pl, g);
-    const uint32_t w_frag = lds_addr(w_lds) + (uint32_t)swz128(pl, g);
-
-    for (int nt = 0; nt < ntiles; ++nt) {
-        store_w();
-        __syncthreads();                        // W tile nt (and, first time, the A tile) visible
-        if (nt + 1 < ntiles) load_w(nt + 1);
-        // epilogue operands of THIS tile: requested now, consumed after the K loop
-        const int n0 = nt * 64;
-        float bvec[16];
-        gemm_load_bias(p, n0, g, EPI == E_UNEMBED, bvec);
-        EpiPre pre[2];
-#pragma unroll
-        for (int tg = 0; tg < 2; ++tg) pre[tg] = epi_prefetch<EPI>(p, min(m0 + 32 * wave + 16 * tg + pl, p.M - 1), n0, g);
-        __builtin_amdgcn_sched_barrier(0);
-        f32x4 acc[2][4];
-#pragma unroll
-        for (int tg = 0; tg < 2; ++tg)
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) acc[tg][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-        {
-            // fragments two K-steps ahead (3-slot ring), addresses = 3 base registers + immediate offsets: one step is
-            // 8 MFMAs = 128 cycles, the LDS round trip under load is several hundred (stamped in the conv kernel)
-            bf16x8 tf[3][2], wf[3][4];
-            auto ld = [&](int step, int slot) {
-                const int kc = step >> 1;
-                if (step & 1) {
-                    tf[slot][0] = lds_read_b128_asm_off_x64(a_tok0, kc * (PBM * 128));
-                    tf[slot][1] = lds_read_b128_asm_off_x64(a_tok1, kc * (PBM * 128));
-#pragma unroll
-                    for (int ct = 0; ct < 4; ++ct) wf[slot][ct] = lds_read_b128_asm_off_x64(w_frag, kc * (64 * 128) + ct * 2048);
-                } else {
-                    tf[slot][0] = lds_read_b128_asm_off(a_tok0, kc * (PBM * 128));
-                    tf[slot][1] = lds_read_b128_asm_off(a_tok1, kc * (PBM * 128));
-#pragma unroll
-                    for (int ct = 0; ct < 4; ++ct) wf[slot][ct] = lds_read_b128_asm_off(w_frag, kc * (64 * 128) + ct * 2048);
-                }
-            };
-            ld(0, 0);
-            ld(1, 1);
-#pragma unroll
-            for (int step = 0; step < 6; ++step) {
-                const int cur = step % 3;
-                if (step + 2 < 6) { ld(step + 2, (step + 2) % 3); lds_wait<12>(); }
-                else if (step + 1 < 6) { lds_wait<6>(); }
-                else { lds_wait<0>(); }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int tg = 0; tg < 2; ++tg)
-#pragma unroll
-                    for (int ct = 0; ct < 4; ++ct) acc[tg][ct] = mfma16x16x32(wf[cur][ct], tf[cur][tg], acc[tg][ct]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        __syncthreads();                        // everyone done reading W tile nt
-#pragma unroll
-        for (int tg = 0; tg < 2; ++tg) {
-            const int m = m0 + 32 * wave + 16 * tg + pl;
-            if (m >= p.M) continue;
-            float v[16];
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[ct * 4 + e] = acc[tg][ct][e];
-            epi_finish<EPI>(p, m, n0, g, v, bvec, pre[tg]);
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Panel kernel v2 (K = 192): the token operand never touches LDS.  Each lane loads its 32 rows directly in MFMA
-// B-fragment order (token 16tg+pl, channels 32*step + 8g .. +8; A_LN: statistics by two cross-lane-group shuffles) and
-// keeps the 12 bf16x8 fragments in registers for all N/64 weight tiles.  LDS holds only the weight stream: two 24 KB
-// buffers filled by LDS-DMA one tile ahead, ONE workgroup barrier per tile (v1: global -> registers -> ds_write, two
-// barriers).  K loop: weight fragments two K-steps ahead, immediate-offset reads.  Epilogue operands are requested
-// before the K loop (epi_prefetch).  48 KB of LDS, <= 256 VGPRs: two 4-wave workgroups per CU.
-// ------------------------------------------------------------------------------------------------
+constexpr int PW_BYTES = 3 * 64 * 128;
 // (Measured: the A_F32 / E_UNEMBED instance built for THREE workgroups per CU -- 168 registers, 17 of them spilled -- makes the forward
 // 0.2 ms slower, 4.12 vs 3.91 ms; two workgroups per CU it stays.)
 template <int AMODE, int EPI>
@@ -786,14 +584,12 @@ __global__ __launch_bounds__(256, 2) void gemm_panel2_kernel(const GemmParams p)
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     uint32_t sw = (q < 4) ? cur.a[tg][0][q & 3] : cur.a[tg][1][q & 3];
-                    if (!p.skip) sw = 0u;
+                    if (!p.skip) sw = 0u;                      // the loads then read `out`
                     const int ct = q >> 1, e = (q & 1) * 2;
-                    pk[q] = pack_bf16x2(acc[tg][ct][e] + bvec[2 * q] + __builtin_bit_cast(float, sw << 16),
-                                        acc[tg][ct][e + 1] + bvec[2 * q + 1] + __builtin_bit_cast(float, sw & 0xffff0000u));
+                    pk[q] = unembed_pair(acc[tg][ct][e], acc[tg][ct][e + 1], bvec[2 * q], bvec[2 * q + 1], sw);
                 }
                 bf16_t* o = cur.ok[tg] ? (bf16_t*)p.out + cur.off[tg] : reinterpret_cast<bf16_t*>(tup_gemm_sink) + lane * 16;
-                *reinterpret_cast<u32x4*>(o) = u32x4{pk[0], pk[1], pk[2], pk[3]};
-                *reinterpret_cast<u32x4*>(o + 8) = u32x4{pk[4], pk[5], pk[6], pk[7]};
+                store_bf16x16(o, pk);
             }
         };
         Ops A, B;
@@ -824,6 +620,9 @@ __global__ __launch_bounds__(256, 2) void gemm_panel2_kernel(const GemmParams p)
 #pragma unroll
             for (int ct = 0; ct < 4; ++ct) acc[tg][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
         {
+            // The same six K steps as in the E_UNEMBED tile loop above, written out a second time on purpose: as one function (or
+            // lambda) shared by both loops the K loop compiles the same, but hipcc then orders the patch_unembed epilogue after
+            // it differently and gemm_panel2_kernel<A_BF16, E_UNEMBED> measured 2 % slower (profiles/r13_gemm_tokens_refactor_ab.txt).
             const uint32_t wb = w_frag + (uint32_t)((nt & 1) * PW_BYTES);
             bf16x8 wf[3][4];
             auto ld = [&](int step, int slot) {
@@ -867,8 +666,8 @@ __global__ __launch_bounds__(256, 2) void gemm_panel2_kernel(const GemmParams p)
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
                         const uint32_t sw = (q < 4) ? pre[tg].a[0][q & 3] : pre[tg].a[1][q & 3];
-                        cs[2 * q] += __builtin_bit_cast(float, sw << 16);
-                        cs[2 * q + 1] += __builtin_bit_cast(float, sw & 0xffff0000u);
+                        cs[2 * q] += bf16_even(sw);
+                        cs[2 * q + 1] += bf16_odd(sw);
                     }
                 }
             }
@@ -900,15 +699,7 @@ int launch_panel(const GemmParams& p, hipStream_t s)
 {
     if (p.M <= 0) return 0;
     if (p.N % 64 != 0 || p.K != PK) return (int)hipErrorInvalidValue;
-    static const bool use_v1 = TUP_ENV_FLAG("TUP_GEMM_PANEL_V1");
-    if (!use_v1) {
-        gemm_panel2_kernel<AMODE, EPI><<<dim3((p.M + PBM - 1) / PBM), dim3(256), 2 * PW_BYTES, s>>>(p);
-        TUP_CHECK_LAUNCH();
-        return 0;
-    }
-    constexpr size_t lds = PA_BYTES + PW_BYTES;
-    TUP_SET_DYN_LDS((gemm_panel_kernel<AMODE, EPI>), lds);
-    gemm_panel_kernel<AMODE, EPI><<<dim3((p.M + PBM - 1) / PBM), dim3(256), lds, s>>>(p);
+    gemm_panel2_kernel<AMODE, EPI><<<dim3((p.M + PBM - 1) / PBM), dim3(256), 2 * PW_BYTES, s>>>(p);
     TUP_CHECK_LAUNCH();
     return 0;
 }
@@ -937,7 +728,7 @@ constexpr int PE_BM = 256, PE_A_BYTES = PE_BM * 128;
 __device__ __attribute__((aligned(16))) unsigned int tup_pe_zero_line[4] = {0u, 0u, 0u, 0u};
 
 // AMODE = A_PATCH (gathered patches) or A_BF16 (plain bf16 rows [M][lda]: the K = 576 / 768 Linear layers of the training
-// path with N = 192), EPI = any epilogue of gemm_store_row.
+// path with N = 192), EPI = any epilogue of epi_finish.
 template <int NT64, int AMODE, int EPI>
 __global__ __launch_bounds__(512, 2) void patch_embed_kernel(const GemmParams p)
 {
@@ -978,13 +769,7 @@ __global__ __launch_bounds__(512, 2) void patch_embed_kernel(const GemmParams p)
             const char* src;
             if constexpr (AMODE == A_PATCH) {
                 int py = tpy[u] + i, px = tpx[u] + j;
-                bool ok = tval[u];
-                if (p.reflect) {
-                    if (py >= p.H) py = 2 * p.H - 2 - py;
-                    if (px >= p.W) px = 2 * p.W - 2 - px;
-                } else if (py >= p.H || px >= p.W) {
-                    ok = false;
-                }
+                const bool ok = patch_gather_pixel(p, py, px) && tval[u];
                 src = ok ? (const char*)p.A + tokoff[u] + (size_t)(py * p.W + px) * 128 : (const char*)tup_pe_zero_line;
             } else {
                 src = tval[u] ? arow[u] + (size_t)kc * 128 : (const char*)tup_pe_zero_line;
@@ -1068,7 +853,7 @@ __global__ __launch_bounds__(512, 2) void patch_embed_kernel(const GemmParams p)
             for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[ct * 4 + e] = acc[tg][ng * 4 + ct][e];
-            gemm_store_row<EPI>(p, m, ng * 64, g, v, bvec);
+            epi_finish<EPI>(p, m, ng * 64, g, v, bvec, epi_prefetch<EPI>(p, m, ng * 64, g));
         }
     }
 }
@@ -1086,16 +871,55 @@ int launch_patch_embed(const GemmParams& p, hipStream_t s)
 
 int launch_patch_embed_any(const GemmParams& p, hipStream_t s)
 {
-    static const bool use_old = TUP_ENV_FLAG("TUP_PATCH_EMBED_V1");
     // the kernel keeps 32-bit byte offsets into the map: fine up to 4 GB of NHWC bf16 (B*H*W < 33.5 M pixels)
     const long long per_img = p.linear_tokens ? (long long)p.Ht * p.Wt_ : (long long)p.nWy * p.nWx * 64;
     const long long nimg = per_img > 0 ? p.M / per_img : 0;
     const bool fits = nimg * (long long)p.H * p.W * 128 < (1LL << 32);
-    if (!use_old && fits && p.K == 4096) {
+    if (fits && p.K == 4096) {
         if (p.N == 192) return launch_patch_embed<3>(p, s);
         if (p.N == 128) return launch_patch_embed<2>(p, s);
     }
-    return launch<A_PATCH, E_PATCH_EMBED>(p, s);
+    return launch<A_PATCH, E_PATCH_EMBED>(p, s);          // larger maps, other widths: the K-streaming kernel
+}
+
+// The (a_dtype, epilogue) table of tup_gemm_tokens_fwd, stated once for both launchers: PANEL = the panel kernel (K = 192), else
+// the K-streaming kernel.
+template <bool PANEL, int AMODE, int EPI>
+int launch_linear_as(const GemmParams& p, hipStream_t s)
+{
+    if constexpr (PANEL) return launch_panel<AMODE, EPI>(p, s);
+    else return launch<AMODE, EPI>(p, s);
+}
+
+template <bool PANEL>
+int launch_linear(int a_dtype, int epilogue, const GemmParams& p, hipStream_t s)
+{
+    if (a_dtype == 0) {
+        if (epilogue == 0) return launch_linear_as<PANEL, A_BF16, E_BF16>(p, s);
+        if (epilogue == 1) return launch_linear_as<PANEL, A_BF16, E_GELU_BF16>(p, s);
+        if (epilogue == 2) return launch_linear_as<PANEL, A_BF16, E_RES_F32>(p, s);
+        if (epilogue == 3) return launch_linear_as<PANEL, A_BF16, E_GELU_BWD>(p, s);
+    } else if (a_dtype == 1) {
+        if (epilogue == 0) return launch_linear_as<PANEL, A_F32, E_BF16>(p, s);
+        if (epilogue == 3) return launch_linear_as<PANEL, A_F32, E_GELU_BWD>(p, s);
+    }
+    return (int)hipErrorInvalidValue;
+}
+
+// Token-grid geometry of the patch entries over an H x W map.  Window layout (FastTransformer, WindowTransformer): the Ht x Wt_
+// grid is cut into 8 x 8 windows, token row m = ((b * nWy + wy) * nWx + wx) * 64 + position in the window, and the rows of a
+// partial window's missing tokens exist (token_of_row: !valid).  Linear layout (ResidualTransformer): a plain [B][H/8][W/8] grid.
+void window_geometry(GemmParams& p, int B, int H, int W, int Ht, int Wt_)
+{
+    p.H = H; p.W = W; p.Ht = Ht; p.Wt_ = Wt_;
+    p.nWy = (Ht + 7) / 8; p.nWx = (Wt_ + 7) / 8;
+    p.M = B * p.nWy * p.nWx * 64;
+}
+
+void linear_geometry(GemmParams& p, int B, int H, int W)
+{
+    p.H = H; p.W = W; p.Ht = H / 8; p.Wt_ = W / 8; p.linear_tokens = 1;
+    p.M = B * p.Ht * p.Wt_;
 }
 
 }  // namespace
@@ -1123,34 +947,12 @@ extern "C" int tup_gemm_tokens_fwd(const void* A, int a_dtype, int lda, const vo
     if ((epilogue == 1 || epilogue == 2) && !bias) return (int)hipErrorInvalidValue;
     if (epilogue == 2 && !res) return (int)hipErrorInvalidValue;
     if (epilogue == 3 && !aux) return (int)hipErrorInvalidValue;
-    static const bool use_panel = !TUP_ENV_FLAG("TUP_GEMM_NOPANEL");
-    if (K == PK && use_panel) {
-        if (a_dtype == 0) {
-            if (epilogue == 0) return launch_panel<A_BF16, E_BF16>(p, s);
-            if (epilogue == 1) return launch_panel<A_BF16, E_GELU_BF16>(p, s);
-            if (epilogue == 2) return launch_panel<A_BF16, E_RES_F32>(p, s);
-            if (epilogue == 3) return launch_panel<A_BF16, E_GELU_BWD>(p, s);
-        } else if (a_dtype == 1) {
-            if (epilogue == 0) return launch_panel<A_F32, E_BF16>(p, s);
-            if (epilogue == 3) return launch_panel<A_F32, E_GELU_BWD>(p, s);
-        }
-        return (int)hipErrorInvalidValue;
-    }
-    static const bool use_big = !TUP_ENV_FLAG("TUP_GEMM_NOBIG");
-    if (use_big && a_dtype == 0 && N == 192 && K > PK && K % 64 == 0 && M >= 4096) {       // long-K Linear layers onto the big tile
+    if (K == PK) return launch_linear<true>(a_dtype, epilogue, p, s);
+    if (a_dtype == 0 && N == 192 && K > PK && K % 64 == 0 && M >= 4096) {       // long-K Linear layers onto the big tile
         if (epilogue == 0) return launch_patch_embed<3, A_BF16, E_BF16>(p, s);
         if (epilogue == 2) return launch_patch_embed<3, A_BF16, E_RES_F32>(p, s);
     }
-    if (a_dtype == 0) {
-        if (epilogue == 0) return launch<A_BF16, E_BF16>(p, s);
-        if (epilogue == 1) return launch<A_BF16, E_GELU_BF16>(p, s);
-        if (epilogue == 2) return launch<A_BF16, E_RES_F32>(p, s);
-        if (epilogue == 3) return launch<A_BF16, E_GELU_BWD>(p, s);
-    } else if (a_dtype == 1) {
-        if (epilogue == 0) return launch<A_F32, E_BF16>(p, s);
-        if (epilogue == 3) return launch<A_F32, E_GELU_BWD>(p, s);
-    }
-    return (int)hipErrorInvalidValue;
+    return launch_linear<false>(a_dtype, epilogue, p, s);
 }
 
 // feat: [B][H][W][64] bf16.  Wt: [192][4096] bf16, k = (i*8+j)*64 + c.  x_out: fp32 [B*nWy*nWx*64][192]
@@ -1159,10 +961,9 @@ extern "C" int tup_patch_embed_fwd(const void* feat, const void* Wt, const float
                                    int B, int H, int W, void* stream)
 {
     GemmParams p{};
-    p.H = H; p.W = W; p.Ht = (H + 7) / 8; p.Wt_ = (W + 7) / 8;
-    p.nWy = (p.Ht + 7) / 8; p.nWx = (p.Wt_ + 7) / 8;
+    window_geometry(p, B, H, W, (H + 7) / 8, (W + 7) / 8);
     p.A = feat; p.Wt = (const bf16_t*)Wt; p.bias = bias; p.out = x_out; p.ldo = 192;
-    p.M = B * p.nWy * p.nWx * 64; p.N = 192; p.K = 4096; p.reflect = 1;
+    p.N = 192; p.K = 4096; p.reflect = 1;
     // reflect padding needs pad < dim (same constraint as F.pad(mode='reflect'))
     if ((p.Ht * 8 - H) >= H || (p.Wt_ * 8 - W) >= W) return (int)hipErrorInvalidValue;
     return launch_patch_embed_any(p, reinterpret_cast<hipStream_t>(stream));
@@ -1175,14 +976,11 @@ extern "C" int tup_patch_unembed_fwd(const void* x, int x_bf16, const void* Wt, 
                                      void* out, int B, int H, int W, void* stream)
 {
     GemmParams p{};
-    p.H = H; p.W = W; p.Ht = (H + 7) / 8; p.Wt_ = (W + 7) / 8;
-    p.nWy = (p.Ht + 7) / 8; p.nWx = (p.Wt_ + 7) / 8;
+    window_geometry(p, B, H, W, (H + 7) / 8, (W + 7) / 8);
     p.A = x; p.lda = 192; p.Wt = (const bf16_t*)Wt; p.bias = bias; p.out = out; p.skip = (const bf16_t*)skip;
-    p.M = B * p.nWy * p.nWx * 64; p.N = 4096; p.K = 192;
-    static const bool use_panel = !TUP_ENV_FLAG("TUP_GEMM_NOPANEL");
+    p.N = 4096; p.K = 192;
     if (x_bf16) return launch_panel<A_BF16, E_UNEMBED>(p, reinterpret_cast<hipStream_t>(stream));
-    if (use_panel) return launch_panel<A_F32, E_UNEMBED>(p, reinterpret_cast<hipStream_t>(stream));
-    return launch<A_F32, E_UNEMBED>(p, reinterpret_cast<hipStream_t>(stream));
+    return launch_panel<A_F32, E_UNEMBED>(p, reinterpret_cast<hipStream_t>(stream));
 }
 
 // LayerNorm fused into a Linear (norm1 -> attn.qkv, model.py:163 + :115): out bf16 [M][N] = LN(x) Wt^T + bias.
@@ -1203,10 +1001,9 @@ extern "C" int tup_ln_gemm_fwd(const float* x, const float* gamma, const float* 
 extern "C" int tup_patch_unembed_bwd(const void* gmap, const void* Wt, float* gx, int B, int H, int W, void* stream)
 {
     GemmParams p{};
-    p.H = H; p.W = W; p.Ht = (H + 7) / 8; p.Wt_ = (W + 7) / 8;
-    p.nWy = (p.Ht + 7) / 8; p.nWx = (p.Wt_ + 7) / 8;
+    window_geometry(p, B, H, W, (H + 7) / 8, (W + 7) / 8);
     p.A = gmap; p.Wt = (const bf16_t*)Wt; p.bias = nullptr; p.out = gx; p.ldo = 192;
-    p.M = B * p.nWy * p.nWx * 64; p.N = 192; p.K = 4096; p.reflect = 0;
+    p.N = 192; p.K = 4096; p.reflect = 0;
     return launch_patch_embed_any(p, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -1216,13 +1013,11 @@ extern "C" int tup_patch_unembed_bwd(const void* gmap, const void* Wt, float* gx
 extern "C" int tup_patch_embed_bwd(const float* gx, const void* Wt, void* gmap_pad, int B, int H, int W, void* stream)
 {
     GemmParams p{};
-    p.Ht = (H + 7) / 8; p.Wt_ = (W + 7) / 8; p.H = p.Ht * 8; p.W = p.Wt_ * 8;
-    p.nWy = (p.Ht + 7) / 8; p.nWx = (p.Wt_ + 7) / 8;
+    const int Ht = (H + 7) / 8, Wt_ = (W + 7) / 8;
+    window_geometry(p, B, Ht * 8, Wt_ * 8, Ht, Wt_);
     p.A = gx; p.lda = 192; p.Wt = (const bf16_t*)Wt; p.bias = nullptr; p.out = gmap_pad; p.skip = nullptr;
-    p.M = B * p.nWy * p.nWx * 64; p.N = 4096; p.K = 192;
-    static const bool use_panel = !TUP_ENV_FLAG("TUP_GEMM_NOPANEL");
-    if (use_panel) return launch_panel<A_F32, E_UNEMBED>(p, reinterpret_cast<hipStream_t>(stream));
-    return launch<A_F32, E_UNEMBED>(p, reinterpret_cast<hipStream_t>(stream));
+    p.N = 4096; p.K = 192;
+    return launch_panel<A_F32, E_UNEMBED>(p, reinterpret_cast<hipStream_t>(stream));
 }
 
 // patch_embed's input gradient with the gradient merge at `feat` in its epilogue (training, H and W multiples of 8 so that the
@@ -1236,11 +1031,10 @@ extern "C" int tup_patch_embed_bwd_merge(const float* gx, const void* Wt, const 
 {
     if (H % 8 || W % 8 || add1 == nullptr || relu_src == nullptr) return (int)hipErrorInvalidValue;
     GemmParams p{};
-    p.Ht = H / 8; p.Wt_ = W / 8; p.H = H; p.W = W;
-    p.nWy = (p.Ht + 7) / 8; p.nWx = (p.Wt_ + 7) / 8;
+    window_geometry(p, B, H, W, H / 8, W / 8);
     p.A = gx; p.lda = 192; p.Wt = (const bf16_t*)Wt; p.bias = nullptr; p.out = out;
     p.skip = (const bf16_t*)add1; p.skip2 = (const bf16_t*)add2; p.relu_src = (const bf16_t*)relu_src; p.skip_colsum = add1_colsum;
-    p.M = B * p.nWy * p.nWx * 64; p.N = 4096; p.K = 192;
+    p.N = 4096; p.K = 192;
     return launch_panel<A_F32, E_UNEMBED_MERGE>(p, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -1252,9 +1046,9 @@ extern "C" int tup_rt_patch_embed_fwd(const void* feat, const void* Wt, const fl
 {
     if (H % 8 || W % 8) return (int)hipErrorInvalidValue;
     GemmParams p{};
-    p.H = H; p.W = W; p.Ht = H / 8; p.Wt_ = W / 8; p.linear_tokens = 1; p.pos = pos; p.reflect = 0;
-    p.A = feat; p.Wt = (const bf16_t*)Wt; p.bias = bias; p.out = x_out; p.ldo = 128;
-    p.M = B * p.Ht * p.Wt_; p.N = 128; p.K = 4096;
+    linear_geometry(p, B, H, W);
+    p.A = feat; p.Wt = (const bf16_t*)Wt; p.bias = bias; p.out = x_out; p.ldo = 128; p.pos = pos; p.reflect = 0;
+    p.N = 128; p.K = 4096;
     return launch_patch_embed_any(p, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -1265,9 +1059,9 @@ extern "C" int tup_rt_patch_unembed_fwd(const float* x, const void* Wt, const fl
 {
     if (H % 8 || W % 8) return (int)hipErrorInvalidValue;
     GemmParams p{};
-    p.H = H; p.W = W; p.Ht = H / 8; p.Wt_ = W / 8; p.linear_tokens = 1;
+    linear_geometry(p, B, H, W);
     p.A = x; p.lda = 128; p.Wt = (const bf16_t*)Wt; p.bias = bias; p.out = out; p.skip = (const bf16_t*)skip;
-    p.M = B * p.Ht * p.Wt_; p.N = 4096; p.K = 128;
+    p.N = 4096; p.K = 128;
     return launch<A_F32, E_UNEMBED>(p, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -1280,10 +1074,9 @@ extern "C" int tup_wt_patch_embed_fwd(const void* feat, const void* Wt, const fl
 {
     if (N % 64 || H < 8 || W < 8) return (int)hipErrorInvalidValue;
     GemmParams p{};
-    p.H = H; p.W = W; p.Ht = H / 8; p.Wt_ = W / 8;
-    p.nWy = (p.Ht + 7) / 8; p.nWx = (p.Wt_ + 7) / 8; p.reflect = 0;
-    p.A = feat; p.Wt = (const bf16_t*)Wt; p.bias = bias; p.out = x_out; p.ldo = N;
-    p.M = B * p.nWy * p.nWx * 64; p.N = N; p.K = 4096;
+    window_geometry(p, B, H, W, H / 8, W / 8);
+    p.A = feat; p.Wt = (const bf16_t*)Wt; p.bias = bias; p.out = x_out; p.ldo = N; p.reflect = 0;
+    p.N = N; p.K = 4096;
     return launch_patch_embed_any(p, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -1294,9 +1087,8 @@ extern "C" int tup_wt_patch_unembed_fwd(const float* x, const void* Wt, const fl
 {
     if (K % 64 || Hs % 8 || Ws % 8) return (int)hipErrorInvalidValue;
     GemmParams p{};
-    p.H = Hs; p.W = Ws; p.Ht = Hs / 8; p.Wt_ = Ws / 8;
-    p.nWy = (p.Ht + 7) / 8; p.nWx = (p.Wt_ + 7) / 8;
+    window_geometry(p, B, Hs, Ws, Hs / 8, Ws / 8);
     p.A = x; p.lda = K; p.Wt = (const bf16_t*)Wt; p.bias = bias; p.out = out; p.skip = (const bf16_t*)skip;
-    p.M = B * p.nWy * p.nWx * 64; p.N = 4096; p.K = K;
+    p.N = 4096; p.K = K;
     return launch<A_F32, E_UNEMBED>(p, reinterpret_cast<hipStream_t>(stream));
 }
