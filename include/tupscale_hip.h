@@ -717,6 +717,29 @@ int tup_jpeg_decode_blocks(const void* records, const void* scans, long long sca
 int tup_jpeg_decode_finish(const void* workspace, long long ws_bytes, int B, int H, int W, int layout, void* out_u8, float* out_f32,
                            void* stream);
 
+/* PNG files (8-bit RGB, colour type 2, no interlace) of a whole batch made on the GPU (ops.png_encode; csrc/png_encode.hip).
+ * The filtered stream of an image, H * (1 + 3 W) bytes, is cut every block_bytes bytes (256..32768); each range is one deflate block
+ * on a byte boundary in an IDAT chunk of its own, which is what a workgroup codes.  Exactly one of frames_u8 (uint8 [B][H][W][3], RGB)
+ * and frames_f32 (fp32 [B][3][H][W], quantised as tup_f32chw_to_u8hwc does) is given.  filter: 0 none, 1 sub, 2 up, 3 average,
+ * 4 paeth for every row, 5 adaptive (the smallest sum of |residual| per row; `filters` is then tup_png_filters' output, otherwise unused).
+ *   tup_png_filters   filters uint8 [B][H] <- the filter of every row;
+ *   tup_png_sizes     sizes int32 [B][N] <- the bytes every block adds to the file (chunk framing included; the last block's count
+ *                     includes the Adler-32 chunk and IEND); partials int32 [B][N] <- the block's Adler-32 partial;
+ *   tup_png_offsets   offsets int32 [B][N] <- 33 + the sizes before; lengths int32 [B] <- the file's length, or -1 where it exceeds
+ *                     `capacity`, the bytes of one image's row of `data`; adlers int32 [B] <- the Adler-32 of the filtered stream;
+ *   tup_png_write     data uint8 [B][capacity] <- the whole file of every image whose length is not -1; nothing is written past a row.
+ * N = tup_png_blocks(H, W, block_bytes) (returns a count, not an error code), or -1 for what the encoder refuses: H or W below 1,
+ * H * (1 + 3 W) from 2^31, block_bytes outside 256..32768.  Those, a null pointer, both or neither of the inputs, B outside 1..65535, a
+ * filter outside 0..5 or a capacity outside 0..2^31 - 1 are hipErrorInvalidValue before any launch. */
+int tup_png_blocks(int H, int W, int block_bytes);
+int tup_png_filters(const void* frames_u8, const float* frames_f32, int B, int H, int W, void* filters, void* stream);
+int tup_png_sizes(const void* frames_u8, const float* frames_f32, int B, int H, int W, int filter, int block_bytes, const void* filters,
+                  int* sizes, int* partials, void* stream);
+int tup_png_offsets(const int* sizes, const int* partials, int B, int H, int W, int block_bytes, long long capacity, int* offsets,
+                    int* lengths, int* adlers, void* stream);
+int tup_png_write(const void* frames_u8, const float* frames_f32, int B, int H, int W, int filter, int block_bytes, const void* filters,
+                  const int* offsets, const int* lengths, const int* adlers, void* data, long long capacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

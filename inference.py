@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""One image in, an upscaled JPEG out, scored against the bicubic baseline (reference inference.py), with every image file written
-by the GPU JPEG encoder.
+"""One image in, an upscaled image out, scored against the bicubic baseline (reference inference.py), with every image file written
+by the GPU encoders: a PNG (lossless, ``ops.png_encode``) where the path ends in ``.png``, a JPEG (``ops.jpeg_encode``) otherwise.
 
     python inference.py --image_path images/training_set/image_0.png --model FastTransformer --res_in 720 --scale 3
 
@@ -16,7 +16,12 @@ What happens, in the reference's order (inference.py:64-146):
    the encoder's first kernel, so no uint8 frame is written in between.  (The reference's ``ToPILImage`` wraps values outside [0, 1]
    instead of clamping them; the models here clamp their output anyway.)
 
-The files are what Pillow's ``save()`` writes for the same pixels at ``--quality`` / ``--subsampling`` (defaults 75 and 4:2:0, Pillow's
+As in the reference, where ``Image.save(path)`` picks the format from the suffix, ``--inp x.png`` and ``--out y.png`` (any letter case)
+are PNG files: 8-bit RGB, adaptive filtering, coded by ``ops.png_encode``.  ``--quality`` and ``--subsampling`` do not apply
+to them, and nothing is decoded for their scores: a PNG holds exactly the uint8 frame that was encoded (``tensor_to_frames`` of the
+output for ``--out``), so that frame is scored.  ``bicubic.jpg`` stays a JPEG.
+
+The JPEG files are what Pillow's ``save()`` writes for the same pixels at ``--quality`` / ``--subsampling`` (defaults 75 and 4:2:0, Pillow's
 own) with a restart marker after every MCU row; they decode to the same pixels as Pillow's files without restart markers.
 
 Scores, as the reference computes them, on the DECODED files (``ops.jpeg_decode`` decodes the bytes just produced, to Pillow's
@@ -48,9 +53,10 @@ BICUBIC_PATH = "bicubic.jpg"        # inference.py:84
 
 def build_parser():
     p = argparse.ArgumentParser(
-        description="Inference script for the Transformer upscaler: one image in, an upscaled JPEG out, SSIM / PSNR against the bicubic "
-                    "baseline.  All image files are written by the GPU JPEG encoder (ops.jpeg_encode).  The scores are computed on the "
-                    "decoded files with transformerupscaler_amd.metrics; where the reference resizes with skimage.transform.resize, "
+        description="Inference script for the Transformer upscaler: one image in, an upscaled image out, SSIM / PSNR against the bicubic "
+                    "baseline.  All image files are written by the GPU encoders: a path that ends in .png gets a lossless PNG "
+                    "(ops.png_encode), any other a JPEG (ops.jpeg_encode).  The scores are computed on the decoded JPEG files, or on the "
+                    "frame a PNG was made from, with transformerupscaler_amd.metrics; where the reference resizes with skimage.transform.resize, "
                     "this driver uses the project's GPU resize (Pillow's BILINEAR), so the scores are comparable with the reference's, "
                     "not digit-for-digit equal.")
     p.add_argument("--image_path", type=str, default="images/training_set/image_100.jpg", help="Path to the input image file")
@@ -59,15 +65,20 @@ def build_parser():
                    help="Directory containing model checkpoints (default: models/{model}/checkpoints/)")
     p.add_argument("--scale", type=int, default=3, help="Output resolution scale (2, 3, 4, 6)")
     p.add_argument("--res_in", type=str, default=None, help="Input resolution key (None for no downscaling)")
-    p.add_argument("--inp", type=str, default="input.jpg", help="Output file path for the downscaled input image")
-    p.add_argument("--out", type=str, default="model.jpg", help="Output file path for the upscaled output image")
+    p.add_argument("--inp", type=str, default="input.jpg", help="Output file path for the downscaled input image (.png: a lossless PNG; otherwise JPEG)")
+    p.add_argument("--out", type=str, default="model.jpg", help="Output file path for the upscaled output image (.png: a lossless PNG; otherwise JPEG)")
     p.add_argument("--compile", action="store_true", help="Accepted for compatibility; no effect on the HIP path (reported)")
     p.add_argument("--quantize", action="store_true", help="Accepted for compatibility; no effect on the HIP path (reported)")
     p.add_argument("--no-checkpoint", dest="no_checkpoint", action="store_true", help="Load no checkpoint: run the model as constructed")
     p.add_argument("--json", type=str, default=None, help="Write the scores, sizes and file lengths to this path")
-    p.add_argument("--quality", type=int, default=75, help="JPEG quality 1..100 (default 75, Pillow's)")
-    p.add_argument("--subsampling", type=str, default="4:2:0", choices=("4:2:0", "4:4:4"), help="JPEG chroma subsampling (default 4:2:0, Pillow's)")
+    p.add_argument("--quality", type=int, default=75, help="JPEG quality 1..100 (default 75, Pillow's); ignored for .png files")
+    p.add_argument("--subsampling", type=str, default="4:2:0", choices=("4:2:0", "4:4:4"), help="JPEG chroma subsampling (default 4:2:0, Pillow's); ignored for .png files")
     return p
+
+
+def file_format(path):
+    """'png' for a path that ends in .png in any letter case, else 'jpeg' (what this driver writes for every other name)"""
+    return "png" if os.path.splitext(path)[1].lower() == ".png" else "jpeg"
 
 
 def decode_image(path_or_bytes, device, gpu=True):
@@ -137,7 +148,10 @@ def run(args, device="cuda"):
     jpeg = dict(quality=args.quality, subsampling=args.subsampling)
 
     def save(frames, path):
-        data = ops.jpeg_files(*ops.jpeg_encode(frames, **jpeg))[0]
+        if file_format(path) == "png":
+            data = ops.png_files(*ops.png_encode(frames))[0]
+        else:
+            data = ops.jpeg_files(*ops.jpeg_encode(frames, **jpeg))[0]
         with open(path, "wb") as f:
             f.write(data)
         return data
@@ -164,7 +178,10 @@ def run(args, device="cuda"):
     files["out"] = (args.out, save(output.contiguous(), args.out))
     print(f"Upscaled image saved to: {args.out}")
 
-    scores = score(original, decode_image(files["out"][1], device), decode_image(files["inp"][1], device))
+    # a PNG is lossless: its pixels are the uint8 frame it was made from, so nothing is decoded for it
+    out_u8 = ops.tensor_to_frames(output.contiguous())[0] if file_format(args.out) == "png" else decode_image(files["out"][1], device)
+    inp_u8 = lr_u8 if file_format(args.inp) == "png" else decode_image(files["inp"][1], device)
+    scores = score(original, out_u8, inp_u8)
     scores = {k: {m: float(v) for m, v in d.items()} for k, d in scores.items()}
     print(f"Bicubic Scores:\tSSIM: {scores['bicubic']['ssim']:.4f}, PSNR: {scores['bicubic']['psnr']:.2f} dB")
     print(f"Model Scores:\tSSIM: {scores['model']['ssim']:.4f}, PSNR: {scores['model']['psnr']:.2f} dB")
@@ -172,7 +189,7 @@ def run(args, device="cuda"):
     sizes = {"inp": [h, w], "bicubic": [h * args.scale, w * args.scale], "out": [int(output.shape[2]), int(output.shape[3])]}
     return {"model": args.model, "checkpoint": checkpoint, "scale": args.scale, "res_in": args.res_in, "n_params": n_params,
             "quality": args.quality, "subsampling": args.subsampling, "scores": scores,
-            "files": {k: {"path": p, "size": sizes[k], "bytes": len(d)} for k, (p, d) in files.items()}}
+            "files": {k: {"path": p, "format": file_format(p), "size": sizes[k], "bytes": len(d)} for k, (p, d) in files.items()}}
 
 
 def main(argv=None):

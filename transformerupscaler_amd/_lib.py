@@ -92,6 +92,12 @@ SIGNATURES = {
     "tup_jpeg_decode_index": [P, P, c_longlong, I, I, I, I, I, I, P, P, P],
     "tup_jpeg_decode_blocks": [P, P, c_longlong, I, I, I, I, I, I, P, P, P, c_longlong, P],
     "tup_jpeg_decode_finish": [P, c_longlong, I, I, I, I, P, P, P],
+    # PNG encoding (csrc/png_encode.hip)
+    "tup_png_blocks": [I, I, I],
+    "tup_png_filters": [P, P, I, I, I, P, P],
+    "tup_png_sizes": [P, P, I, I, I, I, I, P, P, P, P],
+    "tup_png_offsets": [P, P, I, I, I, I, c_longlong, P, P, P, P],
+    "tup_png_write": [P, P, I, I, I, I, I, P, P, P, P, P, c_longlong, P],
     "tup_l1_loss_partial": [P, P, P, c_longlong, I, P],
     "tup_l1_loss_bwd": [P, P, P, P, c_longlong, P],
     "tup_u8hwc_to_f32chw": [P, P, I, I, I, I, P],

@@ -65,6 +65,9 @@ GUARDED = [
     # no counted hand-off: the one lane that walks the Huffman codes bounds the decoder, and its reader state, predictors and the IDCT's
     # 8 values a lane must stay in registers and LDS; scratch would put memory latency into every symbol
     ("jpeg_decode.hip", ["jpeg_index_kernel", "jpeg_blocks_kernel", "jpeg_finish_kernel"]),
+    # no counted hand-off: the Huffman builder, the header's run-length coder and the byte walks index LDS arrays only; a build that moves
+    # one of them into a private array puts scratch latency into the one lane the whole workgroup waits for
+    ("png_encode.hip", ["png_filter_kernel", "png_block_kernel", "png_scan_kernel"]),
 ]
 # diagnostic template instantiations, never launched by the product path: fused_qkv_attn_kernel<PROJ, MLP, STAMPS = true>, the
 # timing ablations fused_mlp_v2_kernel<ABL != 0>

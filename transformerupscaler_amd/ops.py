@@ -1587,11 +1587,118 @@ def jpeg_encode(frames, quality=75, subsampling="4:2:0", restart_rows=1, out=Non
 def jpeg_files(data, lengths):
     """(data, lengths) of `jpeg_encode` -> a list of bytes, one file per image (one copy to the host).  An image that did not fit
     (length -1) is an error."""
+    return _files("jpeg_files", data, lengths)
+
+
+def _files(op, data, lengths):
     n = [int(v) for v in lengths.cpu().tolist()]
     if any(v < 0 for v in n):
-        raise ValueError(f"jpeg_files: image {[i for i, v in enumerate(n) if v < 0][0]} did not fit its row of {data.shape[1]} bytes")
+        raise ValueError(f"{op}: image {[i for i, v in enumerate(n) if v < 0][0]} did not fit its row of {data.shape[1]} bytes")
     host = data.cpu().numpy()
     return [host[i, :v].tobytes() for i, v in enumerate(n)]
+
+
+# ---- PNG encoding of a batch (csrc/png_encode.hip, csrc/png_deflate.h; DESIGN 7m) ----
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
+PNG_MIN_BLOCK, PNG_MAX_BLOCK = 256, 32768
+PNG_BLOCK_BYTES = 16384                          # the default range of the filtered stream one workgroup codes (DESIGN 7m has the measurement)
+
+
+def _png_params(op, H, W, block_bytes):
+    """the number of deflate blocks after every check on the geometry"""
+    if isinstance(block_bytes, bool) or not isinstance(block_bytes, int) or not PNG_MIN_BLOCK <= block_bytes <= PNG_MAX_BLOCK:
+        raise ValueError(f"{op}: block_bytes must be an integer in {PNG_MIN_BLOCK}..{PNG_MAX_BLOCK}, got {block_bytes!r}")
+    if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, int) or not isinstance(W, int) or H < 1 or W < 1:
+        raise ValueError(f"{op}: an image is at least 1 x 1, got {H!r} x {W!r}")
+    if H * (1 + 3 * W) >= 2 ** 31:
+        raise ValueError(f"{op}: {H} x {W} has a filtered stream of {H * (1 + 3 * W)} bytes (below 2^31)")
+    return -(-(H * (1 + 3 * W)) // block_bytes)
+
+
+def png_max_bytes(H, W, block_bytes=PNG_BLOCK_BYTES):
+    """The length of the file whose blocks are all stored: no file of `png_encode` for this geometry is longer, so rows of this many
+    bytes always fit (`out=`)."""
+    N = _png_params("png_max_bytes", H, W, block_bytes)
+    return 33 + 2 + H * (1 + 3 * W) + (12 + 5) * N + 16 + 12
+
+
+def png_encode(frames, filter="adaptive", block_bytes=PNG_BLOCK_BYTES, out=None):
+    """PNG files (8-bit RGB, no interlace) of a batch, made on the GPU.  frames: uint8 [B][H][W][3] (or [H][W][3]) RGB, or fp32
+    [B][3][H][W] quantised as `tensor_to_frames` does, trunc(clamp(x * 255, 0, 255)), inside the kernels.  filter: "adaptive" (per row,
+    the filter with the smallest sum of |residual|) or one of "none", "sub", "up", "average", "paeth" for every row.  The filtered
+    stream is cut every `block_bytes` bytes (256..32768) into deflate blocks (literals and runs, the shortest of stored / fixed /
+    dynamic Huffman), one IDAT chunk each; the file is byte for byte what tests/_png_ref.py states and does not depend on B or `out`.
+    Returns (data uint8 [B][capacity], lengths int32 [B]); `png_files` turns them into bytes.  out=None: the lengths are read back once
+    (the call's one host synchronisation) and `data` is allocated to the longest file.  out=(data, lengths): nothing synchronises; an
+    image longer than data's row gets length -1 and none of its bytes (`png_max_bytes` always fits).  Everything is validated before
+    any launch."""
+    if not isinstance(frames, torch.Tensor) or frames.dtype not in (torch.uint8, F32):
+        raise TypeError(f"png_encode: frames must be a uint8 or float32 tensor, got {getattr(frames, 'dtype', type(frames))}")
+    if frames.dtype == torch.uint8:
+        if frames.dim() == 3:
+            frames = frames.unsqueeze(0)
+        if frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError(f"png_encode: uint8 frames must be [B][H][W][3] or [H][W][3], got shape {tuple(frames.shape)}")
+        B, H, W = (int(v) for v in frames.shape[:3])
+    else:
+        if frames.dim() != 4 or frames.shape[1] != 3:
+            raise ValueError(f"png_encode: float32 frames must be [B][3][H][W], got shape {tuple(frames.shape)}")
+        B, H, W = int(frames.shape[0]), int(frames.shape[2]), int(frames.shape[3])
+    if not 1 <= B <= 65535:
+        raise ValueError(f"png_encode: {B} images in one call (1..65535)")
+    if not isinstance(filter, str) or filter not in PNG_FILTERS:
+        raise ValueError(f"png_encode: filter must be one of {', '.join(PNG_FILTERS)}, got {filter!r}")
+    ft = PNG_FILTERS[filter]
+    N = _png_params("png_encode", H, W, block_bytes)
+    if not frames.is_contiguous():
+        raise ValueError("png_encode: frames must be contiguous")
+    if out is not None:
+        data, lengths = out
+        if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 2 or data.shape[0] != B or not data.is_contiguous():
+            raise ValueError(f"png_encode: out[0] must be a contiguous uint8 [{B}][capacity] tensor, got {getattr(data, 'dtype', type(data))} "
+                             f"{tuple(getattr(data, 'shape', ()))}")
+        if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,) or not lengths.is_contiguous():
+            raise ValueError(f"png_encode: out[1] must be a contiguous int32 [{B}] tensor, got {getattr(lengths, 'dtype', type(lengths))} "
+                             f"{tuple(getattr(lengths, 'shape', ()))}")
+        if data.shape[1] >= 2 ** 31:
+            raise ValueError(f"png_encode: out[0] has rows of {data.shape[1]} bytes (below 2^31)")
+    _nv12_on_gpu("png_encode", frames, "frames")
+    if out is not None:
+        _nv12_on_gpu("png_encode", data, "out[0]")
+        _nv12_on_gpu("png_encode", lengths, "out[1]")
+    dev = frames.device
+    u8 = frames.data_ptr() if frames.dtype == torch.uint8 else None
+    f32 = frames.data_ptr() if frames.dtype == F32 else None
+    work = torch.empty((3, B, N), dtype=torch.int32, device=dev)            # sizes, offsets, Adler partials
+    adlers = torch.empty((B,), dtype=torch.int32, device=dev)
+    if _lib.load().tup_png_blocks(H, W, block_bytes) != N:
+        raise RuntimeError("png_encode: the library counts other blocks than the binding")
+    rows = None
+    if ft == PNG_FILTERS["adaptive"]:
+        rows = torch.empty((B, H), dtype=torch.uint8, device=dev)
+        _lib.call("tup_png_filters", u8, f32, B, H, W, rows.data_ptr(), _stream())
+    rows_ptr = rows.data_ptr() if rows is not None else None
+    _lib.call("tup_png_sizes", u8, f32, B, H, W, ft, block_bytes, rows_ptr, work[0].data_ptr(), work[2].data_ptr(), _stream())
+    if out is None:
+        lengths = torch.empty((B,), dtype=torch.int32, device=dev)
+        _lib.call("tup_png_offsets", work[0].data_ptr(), work[2].data_ptr(), B, H, W, block_bytes, 2 ** 31 - 1, work[1].data_ptr(),
+                  lengths.data_ptr(), adlers.data_ptr(), _stream())
+        host = lengths.cpu().tolist()                                   # the one synchronisation
+        if min(host) < 0:
+            raise RuntimeError("png_encode: a file of 2 GiB or more")
+        data = torch.empty((B, max(host)), dtype=torch.uint8, device=dev)
+    else:
+        _lib.call("tup_png_offsets", work[0].data_ptr(), work[2].data_ptr(), B, H, W, block_bytes, int(data.shape[1]), work[1].data_ptr(),
+                  lengths.data_ptr(), adlers.data_ptr(), _stream())
+    _lib.call("tup_png_write", u8, f32, B, H, W, ft, block_bytes, rows_ptr, work[1].data_ptr(), lengths.data_ptr(), adlers.data_ptr(),
+              data.data_ptr(), int(data.shape[1]), _stream())
+    return data, lengths
+
+
+def png_files(data, lengths):
+    """(data, lengths) of `png_encode` -> a list of bytes, one file per image (one copy to the host).  An image that did not fit
+    (length -1) is an error."""
+    return _files("png_files", data, lengths)
 
 
 # ---- baseline JPEG decoding of a batch (csrc/jpeg_decode.hip; DESIGN 7l) ----
