@@ -80,7 +80,11 @@ int tup_conv12_fused_fwd(const void* xc, const void* w1, const float* b1, const 
  * model.py:264-265 with no non-linearity between them, evaluated as one 5x5-tap conv with 3rr outputs
  * (exact algebra; the outermost HR pixel ring uses per-border weight variants because the reference
  * zero-pads the HR intermediate).  x bf16 NHWC [B][H][W][64]; wp bf16 [25][rows][64] (rows 16/32/112 for
- * r 2/3/6); bias fp32 [3rr]; wv bf16 [9][3rr][25][64]; bv fp32 [9][3rr]; out fp32 [B][3][H*r][W*r]. */
+ * r 2/3/6); bias fp32 [3rr]; wv bf16 [9][3rr][25][64]; bv fp32 [9][3rr]; out fp32 [B][3][H*r][W*r].
+ * wp / wv must come from a composition (packing.pack_branch_a, tup_bra_compose): output (si, sj)'s 5x5 kernel is then supported
+ * on a block of at most 4 x 4 taps.  At r = 2 (tap row 4 / 0 dead for si = 0 / 1, tap column 4 / 0 for sj = 0 / 1) and on the
+ * border ring of every r the kernels read only the taps inside each output's support and ignore anything in the other taps.
+ * At r = 2 out must be 8-byte aligned. */
 int tup_conv5x5_c64_planar_fwd(const void* x, const void* wp, const float* bias, const void* wv,
                                const float* bv, float* out, int B, int H, int W, int r, int relu, void* stream);
 

@@ -471,24 +471,33 @@ int launch_persistent(const void* x, const void* wp, const float* bias, const vo
 // ------------------------------------------------------------------------------------------------
 // Composed branch A at r = 2 (12 outputs) as a ROW GEMM.  The 25-tap form above (CT = 1, KS = 5) reads four pixel fragments
 // and one weight fragment from LDS for every four MFMAs -- each halo pixel 25 times -- and runs exactly at the LDS read rate
-// (1 MB per tile, 8 k cycles against 3.2 k of MFMA issue).  Here the five horizontal taps ride in the GEMM's N instead:
-//     part[y][x'][(c, dx)] = sum_dy sum_ci  in[y + dy][x'][ci] * w[dy][dx][c][ci]          K = 5 * 64, N = 60 (64 rows)
+// (1 MB per tile, 8 k cycles against 3.2 k of MFMA issue).  Here the horizontal taps ride in the GEMM's N instead:
+//     part[y][x'][(c, dx)] = sum_dy sum_ci  in[y + dy][x'][ci] * w[dy][dx][c][ci]
 //     out[y][x][c]         = sum_dx part[y][x + dx][(c, dx)]
-// so a halo pixel is read five times (once per dy) and a K-step is 4 pixel + 4 weight fragments for 16 MFMAs.  The weight
-// rows are ordered so that lane (g, p) of the accumulators ends with sub-pixel g's three image channels x five dx (slot
-// s = tile*4 + e = ch*5 + dx) of halo column p: the dx sum is 4 + 4 DPP row shifts per output, no LDS round trip.
+// so a halo pixel is read five times (once per dy).  Only the LIVE taps are visited: the composition (packing.compose_branch_a)
+// puts sub-pixel (si, sj)'s kernel on a 4 x 4 block of the 5 x 5 -- tap row 4 is zero for si = 0, row 0 for si = 1, column 4 for
+// sj = 0, column 0 for sj = 1 -- so each of the four 16-row weight tiles belongs to ONE sub-pixel t = si*2 + sj:
+//     row 4*ch + k of tile t  =  output ch*4 + t, tap column dx = k + sj        (rows 12..15 zero)
+// The K-steps of dy = 0 run the two si = 0 tiles only and those of dy = 4 the two si = 1 tiles: 6*16 + 4*8 = 128 MFMAs and
+// 6*8 + 4*6 = 72 fragment reads per wave and tile (the dense form: 160 and 80).  Lane (g, p) of the accumulators ends with image
+// channel g's four live dx of all four sub-pixels at halo column p (group 3 idles): the dx sum is 3-4 (+ 3-4 across the 16-column
+// seam) DPP row shifts per output, no LDS round trip, and the two sj of an HR row leave in one 8-byte store.
 // Tile = 8 rows x 28 output columns (halo image 12 x 32 pixels: two whole 16-pixel groups per row); tile walk and halo DMA
-// are conv_pingpong.h's, the row-GEMM K loop is its own.  LDS: 5*8 KB + 2*48 KB = 139,264 B.
+// are conv_pingpong.h's, the row-GEMM K loop is its own.  LDS: 16 slabs * 2 KB + 2*48 KB = 131,072 B.
 // ------------------------------------------------------------------------------------------------
 constexpr int R5_TW = 28, R5_HW = 32, R5_HH = TH + 4, R5_NPIX = R5_HH * R5_HW, R5_IN_BYTES = R5_NPIX * 128;
-constexpr int R5_W_BYTES = 5 * 64 * 128;
+constexpr int R5_NSLAB = 2 + 3 * 4 + 2, R5_W_BYTES = R5_NSLAB * 16 * 128;
+// weight slab (16 rows x 128 B) of tap row dy and tile t: dy = 0 holds tiles 0, 1; dy = 1..3 all four; dy = 4 tiles 2, 3
+constexpr int r5_slab(int dy, int t) { return dy == 0 ? t : (dy == 4 ? 12 + t : 2 + (dy - 1) * 4 + t); }
+constexpr int r5_ntiles(int dy) { return (dy == 0 || dy == 4) ? 2 : 4; }        // live tiles of a tap row ...
+constexpr int r5_tile0(int dy) { return dy == 4 ? 2 : 0; }                      // ... starting at this one
 
 __global__ __launch_bounds__(512, 2) void bra_rows_persistent_kernel(
     const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp, const float* __restrict__ bias,
     float* __restrict__ out, int B, int H, int W, int relu, int tilesX, int tilesY, int ablate)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* w_lds = smem;                              // [5 dy][64 rows][128 B]
+    char* w_lds = smem;                              // [16 slabs (dy, t)][16 rows][128 B]
     char* in_lds = smem + R5_W_BYTES;                // [2 groups][R5_IN_BYTES]
     const int grp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));      // scalar: tile bookkeeping on the SALU
     const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
@@ -501,49 +510,50 @@ __global__ __launch_bounds__(512, 2) void bra_rows_persistent_kernel(
     const Dma dma(W, tid);
     auto prefetch_tile = [&](const TC& c) { dma.prefetch(x, c.b, c.ty * TH, c.tx * R5_TW, H, W, my_in, tup_zero_line); };
 
-    // weights: LDS row (dy, tile t, r = 4*gg + e) <- tap (dy, dx), output co = ch*4 + gg of the 25-tap packing [25][16][64],
-    // slot s = t*4 + e = ch*5 + dx (slot 15 is zero)
-    for (int idx = threadIdx.x; idx < 5 * 64 * 8; idx += 512) {
+    // weights: LDS row 4*ch + k of slab (dy, t) <- tap (dy, dx = k + sj), output co = ch*4 + t of the 25-tap packing
+    // [25][16][64].  The dead taps of wp (tap row 4 / 0 of si = 0 / 1, tap column 4 / 0 of sj = 0 / 1) are never read.
+    for (int idx = threadIdx.x; idx < R5_NSLAB * 16 * 8; idx += 512) {
         const int row = idx >> 3, c = idx & 7;
-        const int dy = row >> 6, t = (row >> 4) & 3, r16 = row & 15;
-        const int gg = r16 >> 2, sl = t * 4 + (r16 & 3);
+        const int slab = row >> 4, r16 = row & 15;
+        const int dy = slab < 2 ? 0 : (slab < 14 ? 1 + ((slab - 2) >> 2) : 4);
+        const int t = slab < 2 ? slab : (slab < 14 ? (slab - 2) & 3 : slab - 12);
+        const int ch = r16 >> 2, dx = (r16 & 3) + (t & 1);
         u32x4 v = u32x4{0u, 0u, 0u, 0u};
-        if (sl < 15) {
-            const int ch = sl / 5, dx = sl - ch * 5;
-            v = *reinterpret_cast<const u32x4*>(wp + ((size_t)((dy * 5 + dx) * 16 + ch * 4 + gg)) * 64 + c * 8);
-        }
+        if (ch < 3) v = *reinterpret_cast<const u32x4*>(wp + ((size_t)((dy * 5 + dx) * 16 + ch * 4 + t)) * 64 + c * 8);
         *reinterpret_cast<u32x4*>(w_lds + swz128(row, c)) = v;
     }
-    float bch[3];                                    // this lane's sub-pixel g, channels 0..2
+    float bsp[4];                                    // this lane's image channel g, sub-pixels 0..3 (group 3 idles)
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) bch[ch] = bias ? bias[ch * 4 + g] : 0.f;
+    for (int t = 0; t < 4; ++t) bsp[t] = (bias && g < 3) ? bias[g * 4 + t] : 0.f;
 
-    // fragment addresses: the swizzle phase ((q >> 1) & 7) of pixel q = row*32 + cg*16 + p and of weight row dy*64 + t*16 + p
+    // fragment addresses: the swizzle phase ((q >> 1) & 7) of pixel q = row*32 + cg*16 + p and of weight row slab*16 + p
     // is (p >> 1) & 7 for both, so one base register each and everything else in the 16-bit immediate
     const uint32_t pbase = lds_addr(my_in) + (uint32_t)(2 * wave * R5_HW * 128) + (uint32_t)swz128(p, g);
     const uint32_t wbase = lds_addr(w_lds) + (uint32_t)swz128(p, g);
 
-    f32x4 acc[2][2][4];                              // [output row of the wave][16-column group][weight tile]
-    // K loop: 10 steps (dy, K half) of 8 fragments + 16 MFMAs, fragments requested two steps ahead (3-slot ring).  The requests
-    // of step + 2 are placed one after every second MFMA of the step: issued in a block at the top of the step they cost the
-    // wave ~60 cycles per step in which its matrix pipe idles, and with one wave per SIMD in a K loop nothing else fills it.
+    f32x4 acc[2][2][4];                              // [output row of the wave][16-column group][weight tile = sub-pixel]
+    // K loop: 10 steps (dy, K half) of 4 pixel + 2 or 4 weight fragments and 8 or 16 MFMAs, fragments requested two steps ahead
+    // (3-slot ring).  The requests of step + 2 are spread between the MFMA pairs of the step: issued in a block at the top of the
+    // step they cost the wave ~60 cycles per step in which its matrix pipe idles, and with one wave per SIMD in a K loop nothing
+    // else fills it.
     auto compute_tile = [&]() {
         constexpr int NSTEPS = 10;
         bf16x8 pf[3][4], wf[3][4];
-        auto load_frag = [&](int step, int slot, int j) {          // j = 0..3 pixel fragments (rw*2 + cg), 4..7 weight tiles
+        auto load_frag = [&](int step, int slot, int j) {          // j = 0..3 pixel fragments (rw*2 + cg), 4.. live weight tiles
             const int dy = step >> 1;
             if (j < 4) {
                 const int off = ((j >> 1) + dy) * (R5_HW * 128) + (j & 1) * 2048;
                 pf[slot][j] = (step & 1) ? lds_read_b128_asm_off_x64(pbase, off) : lds_read_b128_asm_off(pbase, off);
             } else {
-                const int off = dy * 8192 + (j - 4) * 2048;
+                const int off = r5_slab(dy, r5_tile0(dy) + j - 4) * 2048;
                 wf[slot][j - 4] = (step & 1) ? lds_read_b128_asm_off_x64(wbase, off) : lds_read_b128_asm_off(wbase, off);
             }
         };
+        auto nfrag = [](int step) { return 4 + r5_ntiles(step >> 1); };
 #pragma unroll
-        for (int j = 0; j < 8; ++j) load_frag(0, 0, j);
+        for (int j = 0; j < nfrag(0); ++j) load_frag(0, 0, j);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) load_frag(1, 1, j);
+        for (int j = 0; j < nfrag(1); ++j) load_frag(1, 1, j);
 #pragma unroll
         for (int rw = 0; rw < 2; ++rw)
 #pragma unroll
@@ -552,49 +562,67 @@ __global__ __launch_bounds__(512, 2) void bra_rows_persistent_kernel(
                 for (int t = 0; t < 4; ++t) acc[rw][cg][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int step = 0; step < NSTEPS; ++step) {
-            const int cur = step % 3;
-            if (step + 1 < NSTEPS) lds_wait<8>(); else lds_wait<0>();       // this step's fragments; the next step's may still fly
+            const int cur = step % 3, dy = step >> 1;
+            const int npair = 2 * r5_ntiles(dy), t00 = r5_tile0(dy);
+            const int nld = step + 2 < NSTEPS ? nfrag(step + 2) : 0;
+            // this step's fragments; the next step's may still fly
+            if (step + 1 >= NSTEPS) lds_wait<0>(); else if (nfrag(step + 1) == 8) lds_wait<8>(); else lds_wait<6>();
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                if (step + 2 < NSTEPS) load_frag(step + 2, (step + 2) % 3, j);
-                // MFMA pair j: pixel fragment i = j >> 1, weight tiles 2*(j & 1), +1
-                const int i = j >> 1, t0 = (j & 1) * 2;
-                acc[i >> 1][i & 1][t0] = mfma16x16x32(wf[cur][t0], pf[cur][i], acc[i >> 1][i & 1][t0]);
-                acc[i >> 1][i & 1][t0 + 1] = mfma16x16x32(wf[cur][t0 + 1], pf[cur][i], acc[i >> 1][i & 1][t0 + 1]);
+            for (int j = 0; j < npair; ++j) {
+#pragma unroll
+                for (int l = j * nld / npair; l < (j + 1) * nld / npair; ++l) load_frag(step + 2, (step + 2) % 3, l);
+                // MFMA pair j: pixel fragment i, two live weight tiles
+                const int i = npair == 8 ? (j >> 1) : j, w0 = npair == 8 ? (j & 1) * 2 : 0, t0 = t00 + w0;
+                acc[i >> 1][i & 1][t0] = mfma16x16x32(wf[cur][w0], pf[cur][i], acc[i >> 1][i & 1][t0]);
+                acc[i >> 1][i & 1][t0 + 1] = mfma16x16x32(wf[cur][w0 + 1], pf[cur][i], acc[i >> 1][i & 1][t0 + 1]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
     };
 
-    auto store_tile = [&](const TC& c) {
+    // RELU is a compile-time copy of `relu`: as a run-time value hipcc turns every output's clamp into v_max x, x + v_max 0 +
+    // v_cndmask (48 of the phase's vector instructions, all issued out of the other group's MFMA stream)
+    auto store_tile = [&](const TC& c, auto RELU) {
         const int tx = c.tx, ty = c.ty, b = c.b;
-        const int Wr = W * 2, si = g >> 1, sj = g & 1;
-        const int plane = 4 * H * W;                 // elements of one HR plane
-        float* outb = out + (size_t)b * 3 * plane;
+        const int Wr = W * 2;
+        float* outb = out + ((size_t)b * 3 + g) * 4 * H * W;                       // this lane's HR plane
+        // The idle group sits the phase out with its lanes switched off -- sent to the sink, a quarter of every store of every
+        // wave on the chip lands on the same 512 bytes, and the store leg alone takes 198 us instead of 157.  Groups 0..2 are
+        // in every wave, so each store below still issues once per wave.
+        if (g >= 3) return;
 #pragma unroll
         for (int rw = 0; rw < 2; ++rw) {
             const int oy = ty * TH + 2 * wave + rw;
 #pragma unroll
             for (int cg = 0; cg < 2; ++cg) {
                 const int xo = cg * 16 + p, ox = tx * R5_TW + xo;
-                const bool ok = oy < H && ox < W && xo < R5_TW;
-                // exactly 12 store instructions per wave and tile (the counted wait of the phase loop): lanes outside the tile /
-                // image go to the sink
-                float* o = ok ? outb + ((oy * 2 + si) * Wr + (ox * 2 + sj)) : reinterpret_cast<float*>(tup_store_sink) + lane;
-                const int pstep = ok ? plane : 0;
+                const bool ok = oy < H && ox < W;
+                // exactly 8 store instructions per wave and tile (the counted wait of the phase loop): lanes outside the image go
+                // to the sink, because a whole wave can be outside it.  The halo columns 28..31 (lanes p >= 12 of the second
+                // group, beside twelve live lanes in every wave) are switched off for the store alone: the DPP adds of lanes
+                // 8..11 read them, and a switched-off source lane reads as zero
+                float* o = ok ? outb + (oy * 2 * Wr + ox * 2) : reinterpret_cast<float*>(tup_store_sink) + 2 * lane;
+                const int rstep = ok ? Wr : 0;
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    auto part = [&](int c2, int dx) { const int sl = ch * 5 + dx; return acc[rw][c2][sl >> 2][sl & 3]; };
-                    float v = part(cg, 0) + bch[ch];
-                    TUP_ADD_DPP(v, part(cg, 1), "row_shl:1"); TUP_ADD_DPP(v, part(cg, 2), "row_shl:2");
-                    TUP_ADD_DPP(v, part(cg, 3), "row_shl:3"); TUP_ADD_DPP(v, part(cg, 4), "row_shl:4");
+                for (int si = 0; si < 2; ++si) {
+                    // dx ascending with the bias first, as the dense form summed them: sj = 0 has dx = k, sj = 1 has dx = k + 1
+                    const f32x4 &a0 = acc[rw][cg][si * 2], &a1 = acc[rw][cg][si * 2 + 1];
+                    float v0 = a0[0] + bsp[si * 2], v1 = bsp[si * 2 + 1];
+                    TUP_ADD_DPP(v0, a0[1], "row_shl:1"); TUP_ADD_DPP(v0, a0[2], "row_shl:2"); TUP_ADD_DPP(v0, a0[3], "row_shl:3");
+                    TUP_ADD_DPP(v1, a1[0], "row_shl:1"); TUP_ADD_DPP(v1, a1[1], "row_shl:2");
+                    TUP_ADD_DPP(v1, a1[2], "row_shl:3"); TUP_ADD_DPP(v1, a1[3], "row_shl:4");
                     if (cg == 0) {                   // halo columns 16..19 live in the next group's lanes 0..3
-                        TUP_ADD_DPP(v, part(1, 1), "row_shr:15"); TUP_ADD_DPP(v, part(1, 2), "row_shr:14");
-                        TUP_ADD_DPP(v, part(1, 3), "row_shr:13"); TUP_ADD_DPP(v, part(1, 4), "row_shr:12");
+                        const f32x4 &n0 = acc[rw][1][si * 2], &n1 = acc[rw][1][si * 2 + 1];
+                        TUP_ADD_DPP(v0, n0[1], "row_shr:15"); TUP_ADD_DPP(v0, n0[2], "row_shr:14"); TUP_ADD_DPP(v0, n0[3], "row_shr:13");
+                        TUP_ADD_DPP(v1, n1[0], "row_shr:15"); TUP_ADD_DPP(v1, n1[1], "row_shr:14");
+                        TUP_ADD_DPP(v1, n1[2], "row_shr:13"); TUP_ADD_DPP(v1, n1[3], "row_shr:12");
                     }
-                    if (relu) v = fmaxf(v, 0.f);
-                    o[ch * pstep] = v;
+                    if constexpr (decltype(RELU)::value) {           // = fmaxf(v, 0) without the canonicalising v_max v, v in front
+                        asm("v_max_f32 %0, 0, %0" : "+v"(v0));
+                        asm("v_max_f32 %0, 0, %0" : "+v"(v1));
+                    }
+                    if (cg == 0 || p < R5_TW - 16) *reinterpret_cast<f32x2*>(o + si * rstep) = f32x2{v0, v1};
                 }
             }
         }
@@ -617,9 +645,9 @@ __global__ __launch_bounds__(512, 2) void bra_rows_persistent_kernel(
             const int nxt = done + 1;
             if (nxt < my_count && !(ablate & 4)) prefetch_tile(c_next);
             if (done >= 0 && done < my_count && !(ablate & 2)) {
-                store_tile(c_done);
-                // the DMA (issued first) must have landed before the barrier, the 12 stores after it need not
-                asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+                if (relu) store_tile(c_done, std::true_type{}); else store_tile(c_done, std::false_type{});
+                // the DMA (issued first) must have landed before the barrier, the 8 stores after it need not
+                asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             } else {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
@@ -639,7 +667,7 @@ int launch_bra_rows(const void* x, const void* wp, const float* bias, float* out
     TUP_SET_DYN_LDS(bra_rows_persistent_kernel, lds);
     const int tilesX = (W + R5_TW - 1) / R5_TW, tilesY = (H + TH - 1) / TH;
     const long long nt = (long long)tilesX * tilesY * B;
-    if (nt > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    if (nt > 0x7fffffffLL || (reinterpret_cast<uintptr_t>(out) & 7)) return (int)hipErrorInvalidValue;     // 8-byte stores
     const int grid = (int)(nt < 256 ? nt : 256);                 // one workgroup per CU
     static const int ablate = TUP_ENV_INT("TUP_BRA_ABLATE", 0);     // timing experiments: 1 no K loop, 2 no stores, 4 no DMA
     bra_rows_persistent_kernel<<<dim3(grid), dim3(512), lds, s>>>((const bf16_t*)x, (const bf16_t*)wp, bias, out, B, H, W, relu, tilesX, tilesY, ablate);
@@ -767,17 +795,20 @@ int launch_thin_rows(const void* x, const void* wp, const float* bias, float* ou
 // Border fix-up of the composed branch-A conv (see tup_conv5x5_c64_planar_fwd): one wave per HR border
 // pixel recomputes it with the weight variant that leaves out the 64->3 conv's taps falling outside
 // the HR image (those see zero padding in the reference, not a virtual up-conv value).
+// The pixel, its variant and its live taps are the same for the whole wave: they are derived from a readfirstlane'd wave index and
+// blockIdx (image = blockIdx.y, no division by the ring length) with r a template constant, so that all of it runs on the scalar
+// unit -- the kernel is bound by the number of vector instructions its 64 k waves issue.
+template <int R>
 __global__ __launch_bounds__(256) void conv5x5_border_fix_kernel(
     const bf16_t* __restrict__ x, const bf16_t* __restrict__ wv, const float* __restrict__ bv,
-    float* __restrict__ out, int B, int H, int W, int r, int relu)
+    float* __restrict__ out, int B, int H, int W, int relu)
 {
+    constexpr int r = R, rr = r * r, nout = 3 * rr;
     const int lane = threadIdx.x & 63;
-    const int Hs = H * r, Ws = W * r, rr = r * r, nout = 3 * rr;
+    const int Hs = H * r, Ws = W * r;
     const int per_img = 2 * Ws + 2 * (Hs - 2);
-    const long long gid = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (gid >= (long long)per_img * B) return;
-    const int b = (int)(gid / per_img);
-    int k = (int)(gid - (long long)b * per_img);
+    int k = (int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (k >= per_img) return;
     int Y, X;
     if (k < Ws) { Y = 0; X = k; }
     else if (k < 2 * Ws) { Y = Hs - 1; X = k - Ws; }
@@ -786,42 +817,49 @@ __global__ __launch_bounds__(256) void conv5x5_border_fix_kernel(
     const int v = rowmode * 3 + colmode;
     const int y = Y / r, si = Y - y * r, xx0 = X / r, sj = X - xx0 * r;
     const int sp = si * r + sj;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-    // lane = (tap slot t = lane >> 3, channel chunk c8 = lane & 7): the 25 taps in four rounds of eight, every load 16 bytes (eight
-    // bf16 channels) and all 16 of them requested before the first use -- one global round trip per pixel.  (Round 2: the
-    // one-channel-per-lane form issued 100 two-byte loads in five dependent rounds and ran at 0.6 TB/s, 75 us for the ring.)
-    const int t8 = lane >> 3, c8 = lane & 7;
-    u32x4 fx[4], fw[4][3];
-    bool use[4];
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {          // one image per blockIdx.y (a loop only beyond 65,535 images)
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+        // The live taps of a ring pixel, in closed form and wave-uniform (the weights are not consulted).  The variant keeps the
+        // 64->3 conv's taps dy in [dlo, dhi] (rowmode 1 / 2 drops dy = 0 / 2); HR row Y + dy - 1 is LR row offset
+        // oy = floor((si + dy - 1) / r), whose up-conv taps cover tap rows oy + 1 .. oy + 3; the image keeps 2 - y <= ty <= H + 1 - y.
+        // Columns alike.  A ring pixel has rowmode != 0 (then si + dy - 1 stays within one LR row: tap rows 1..3, of which the image
+        // edge keeps two, by at most four columns) or colmode != 0 (at most four rows by two columns): never more than 8 live taps,
+        // for every r.  packing.compose_branch_a produces exactly this support; taps outside it are not read.
+        const int ylo = (si + (rowmode == 1 ? 1 : 0) - 1 + r) / r, yhi = (si + (rowmode == 2 ? 1 : 2) - 1 + r) / r + 2;   // = oy + 1, oy + 3
+        const int xlo = (sj + (colmode == 1 ? 1 : 0) - 1 + r) / r, xhi = (sj + (colmode == 2 ? 1 : 2) - 1 + r) / r + 2;
+        const int ty0 = max(ylo, 2 - y), tx0 = max(xlo, 2 - xx0);
+        const int ny = min(yhi, H + 1 - y) - ty0 + 1, nx = min(xhi, W + 1 - xx0) - tx0 + 1;         // both >= 1: tap (2, 2) is always live
+        // lane = (tap slot t8 = lane >> 3, channel chunk c8 = lane & 7): slot t8 takes tap (ty0 + t8 / nx, tx0 + t8 % nx) -- one round
+        // of eight slots, every load 16 bytes (eight bf16 channels) and all four requested before the first use: one global round
+        // trip per pixel.  (The dense form walked all 25 taps in four such rounds; round 2's one-channel-per-lane form issued 100
+        // two-byte loads in five dependent rounds and ran at 0.6 TB/s, 75 us for the ring.)
+        const int t8 = lane >> 3, c8 = lane & 7;
+        const int rcp = nx == 1 ? 32 : (nx == 2 ? 16 : (nx == 3 ? 11 : 8));          // t8 / nx = (t8 * ceil(32 / nx)) >> 5 for t8 < 8, nx <= 4
+        const int qy = (t8 * rcp) >> 5, ty = ty0 + qy, tx = tx0 + t8 - qy * nx;
+        const bool use = t8 < ny * nx;
+        const int tapc = use ? ty * 5 + tx : 12;                                     // idle slots load the centre tap: always in bounds
+        const int iyc = use ? y + ty - 2 : y, ixc = use ? xx0 + tx - 2 : xx0;
+        const u32x4 fx = *reinterpret_cast<const u32x4*>(x + (((size_t)b * H + iyc) * W + ixc) * 64 + c8 * 8);
+        const bf16_t* wb = wv + (((size_t)v * nout) * 25 + tapc) * 64 + c8 * 8;                                    // [v][n][tap][ci]
+        u32x4 fw[3];
 #pragma unroll
-    for (int rd = 0; rd < 4; ++rd) {
-        const int tap = rd * 8 + t8;
-        const int ty = tap / 5, tx = tap - ty * 5;
-        const int iy = y + ty - 2, ix = xx0 + tx - 2;
-        use[rd] = tap < 25 && iy >= 0 && iy < H && ix >= 0 && ix < W;
-        const int tapc = tap < 25 ? tap : 24, iyc = min(max(iy, 0), H - 1), ixc = min(max(ix, 0), W - 1);      // clamped: loads stay unconditional
-        fx[rd] = *reinterpret_cast<const u32x4*>(x + (((size_t)b * H + iyc) * W + ixc) * 64 + c8 * 8);
-        const bf16_t* wb = wv + (((size_t)v * nout) * 25 + tapc) * 64 + c8 * 8;                               // [v][n][tap][ci]
+        for (int c = 0; c < 3; ++c) fw[c] = *reinterpret_cast<const u32x4*>(wb + (size_t)(c * rr + sp) * 25 * 64);
+        if (use) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) fw[rd][c] = *reinterpret_cast<const u32x4*>(wb + (size_t)(c * rr + sp) * 25 * 64);
-    }
-#pragma unroll
-    for (int rd = 0; rd < 4; ++rd) {
-        if (!use[rd]) continue;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float xl = __builtin_bit_cast(float, fx[rd][q] << 16), xh = __builtin_bit_cast(float, fx[rd][q] & 0xffff0000u);
-            a0 = fmaf(xl, __builtin_bit_cast(float, fw[rd][0][q] << 16), a0); a0 = fmaf(xh, __builtin_bit_cast(float, fw[rd][0][q] & 0xffff0000u), a0);
-            a1 = fmaf(xl, __builtin_bit_cast(float, fw[rd][1][q] << 16), a1); a1 = fmaf(xh, __builtin_bit_cast(float, fw[rd][1][q] & 0xffff0000u), a1);
-            a2 = fmaf(xl, __builtin_bit_cast(float, fw[rd][2][q] << 16), a2); a2 = fmaf(xh, __builtin_bit_cast(float, fw[rd][2][q] & 0xffff0000u), a2);
+            for (int q = 0; q < 4; ++q) {
+                const float xl = __builtin_bit_cast(float, fx[q] << 16), xh = __builtin_bit_cast(float, fx[q] & 0xffff0000u);
+                a0 = fmaf(xl, __builtin_bit_cast(float, fw[0][q] << 16), a0); a0 = fmaf(xh, __builtin_bit_cast(float, fw[0][q] & 0xffff0000u), a0);
+                a1 = fmaf(xl, __builtin_bit_cast(float, fw[1][q] << 16), a1); a1 = fmaf(xh, __builtin_bit_cast(float, fw[1][q] & 0xffff0000u), a1);
+                a2 = fmaf(xl, __builtin_bit_cast(float, fw[2][q] << 16), a2); a2 = fmaf(xh, __builtin_bit_cast(float, fw[2][q] & 0xffff0000u), a2);
+            }
         }
-    }
 #pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { a0 += __shfl_xor(a0, o); a1 += __shfl_xor(a1, o); a2 += __shfl_xor(a2, o); }
-    if (lane < 3) {
-        float val = (lane == 0 ? a0 : (lane == 1 ? a1 : a2)) + bv[v * nout + lane * rr + sp];
-        if (relu) val = fmaxf(val, 0.f);
-        out[(((size_t)b * 3 + lane) * Hs + Y) * Ws + X] = val;
+        for (int o = 32; o >= 1; o >>= 1) { a0 += __shfl_xor(a0, o); a1 += __shfl_xor(a1, o); a2 += __shfl_xor(a2, o); }
+        if (lane < 3) {
+            float val = (lane == 0 ? a0 : (lane == 1 ? a1 : a2)) + bv[v * nout + lane * rr + sp];
+            if (relu) val = fmaxf(val, 0.f);
+            out[(((size_t)b * 3 + lane) * Hs + Y) * Ws + X] = val;
+        }
     }
 }
 
@@ -887,6 +925,11 @@ extern "C" int tup_conv3x3_c64_fwd(const void* x, const void* wp, const float* b
 // x bf16 NHWC [B][H][W][64]; wp bf16 [25][rows][64] (rows = 16/32/112 for r = 2/3/6, row n = c*r*r+si*r+sj);
 // bias fp32 [3rr]; wv bf16 [9][3rr][25][64], bv fp32 [9][3rr] (variant = rowmode*3+colmode, mode 0 interior,
 // 1 first row/col, 2 last row/col); out fp32 [B][3][H*r][W*r].
+// wp / wv must come from a composition (packing.pack_branch_a, tup_bra_compose): output (si, sj)'s kernel is supported on the tap
+// rows / columns floor((s + d - 1) / r) + 1 .. + 3 over the 64->3 conv's taps d the variant keeps.  The border ring (wv, every r)
+// and the r = 2 row GEMM (wp: tap row 4 / 0 dead for si = 0 / 1, tap column 4 / 0 for sj = 0 / 1) read only the taps inside each
+// output's support and ignore whatever the other taps hold; the dense r = 3 / 6 and A/B paths multiply through all 25.
+// r = 2: out must be 8-byte aligned (the two sj of an HR row leave in one store).
 extern "C" int tup_conv5x5_c64_planar_fwd(const void* x, const void* wp, const float* bias, const void* wv,
                                           const float* bv, float* out, int B, int H, int W, int r, int relu,
                                           void* stream)
@@ -919,9 +962,13 @@ extern "C" int tup_conv5x5_c64_planar_fwd(const void* x, const void* wp, const f
             (const bf16_t*)x, (const bf16_t*)wp, bias, nullptr, nullptr, out, H, W, 1, r, nout, relu, tilesX, tilesY, 1);
     }
     TUP_CHECK_LAUNCH();
-    const long long nborder = (long long)B * (2LL * W * r + 2LL * (H * r - 2));
-    conv5x5_border_fix_kernel<<<dim3((unsigned)((nborder + 3) / 4)), dim3(256), 0, s>>>(
-        (const bf16_t*)x, (const bf16_t*)wv, bv, out, B, H, W, r, relu);
+    const long long per_img = 2LL * W * r + 2LL * (H * r - 2);                  // HR ring pixels of one image, four to a workgroup
+    if (per_img > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    const dim3 ring_grid((unsigned)((per_img + 3) / 4), (unsigned)(B < 65535 ? B : 65535));
+    const bf16_t* xb = (const bf16_t*)x; const bf16_t* wvb = (const bf16_t*)wv;
+    if (r == 2) conv5x5_border_fix_kernel<2><<<ring_grid, dim3(256), 0, s>>>(xb, wvb, bv, out, B, H, W, relu);
+    else if (r == 3) conv5x5_border_fix_kernel<3><<<ring_grid, dim3(256), 0, s>>>(xb, wvb, bv, out, B, H, W, relu);
+    else conv5x5_border_fix_kernel<6><<<ring_grid, dim3(256), 0, s>>>(xb, wvb, bv, out, B, H, W, relu);
     TUP_CHECK_LAUNCH();
     return 0;
 }
