@@ -720,11 +720,18 @@ int launch(const GemmParams& p, hipStream_t s)
 // patch_embed (K = 4096 gathered from the NHWC map) as its own kernel: one workgroup = 8 waves = 256 tokens x ALL N/64
 // feature groups, so every 8x8 patch is fetched once (the generic 128 x 64 tile above reads it N/64 times through L2 and
 // runs 16 MFMAs per barrier).  One K-step = one patch pixel (64 channels): token tile 32 KB + weight tile N x 128 B, both
-// by LDS-DMA (swizzle and the reflect / zero padding on the source side) into a two-stage ring, one barrier per K-step;
+// by LDS-DMA (swizzle and the reflect / zero padding on the source side), one barrier per K-step;
 // a wave owns 32 tokens x N: per quarter K-step 2 token + 6 (4) weight fragments for 12 (8) MFMAs, fragments two quarter
 // steps ahead, immediate-offset reads.
+// The token tiles (HBM) run TWO K-steps ahead in a three-slot ring, the weight tiles (L2) one step ahead in a two-slot ring: step
+// kc waits for its own stage with a counted vmcnt that leaves the token pieces of stage kc + 1 in flight across the barrier (a raw
+// s_barrier: __syncthreads() would drain them), then issues the weights of kc + 1 and the tokens of kc + 2 into the two slots that
+// held step kc - 1, whose readers that barrier has just retired -- piece by piece between the step's MFMAs.  No wave of this kernel
+// ever waited for DMA data; what a step cost was the ISSUE of its 56 pieces into the CU's vector-memory path with the matrix pipes
+// idle, and a piece issued late in step kc needs the further step that the third token slot gives it.
 // ------------------------------------------------------------------------------------------------
-constexpr int PE_BM = 256, PE_A_BYTES = PE_BM * 128;
+constexpr int PE_BM = 256, PE_A_BYTES = PE_BM * 128, PE_A_SLOTS = 3, PE_W_SLOTS = 2;
+constexpr size_t pe_lds_bytes(int nt64) { return (size_t)PE_A_SLOTS * PE_A_BYTES + (size_t)PE_W_SLOTS * nt64 * 64 * 128; }
 __device__ __attribute__((aligned(16))) unsigned int tup_pe_zero_line[4] = {0u, 0u, 0u, 0u};
 
 // AMODE = A_PATCH (gathered patches) or A_BF16 (plain bf16 rows [M][lda]: the K = 576 / 768 Linear layers of the training
@@ -733,9 +740,9 @@ template <int NT64, int AMODE, int EPI>
 __global__ __launch_bounds__(512, 2) void patch_embed_kernel(const GemmParams p)
 {
     constexpr int NTILE = 4 * NT64;                        // 16-row weight tiles
-    constexpr int W_BYTES = NT64 * 64 * 128, STAGE = PE_A_BYTES + W_BYTES;
+    constexpr int W_BYTES = NT64 * 64 * 128, W_BASE = PE_A_SLOTS * PE_A_BYTES;
     constexpr int QN = NTILE / 2;                          // weight tiles per quarter step
-    extern __shared__ __attribute__((aligned(16))) char smem[];          // 2 x STAGE
+    extern __shared__ __attribute__((aligned(16))) char smem[];          // 3 token slots, then 2 weight slots (pe_lds_bytes)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, pl = lane & 15;
     const int m0 = blockIdx.x * PE_BM;
@@ -761,28 +768,48 @@ __global__ __launch_bounds__(512, 2) void patch_embed_kernel(const GemmParams p)
         }
     }
     const bf16_t* w_thr = p.Wt + (size_t)(tid >> 3) * p.K + dc * 8;
-    auto dma_stage = [&](int kc, int buf) {
-        char* dst = smem + buf * STAGE + wave * 1024;
+    // The zero line's address once, in scalar registers: named at its use, every piece re-read it through the GOT (s_load +
+    // s_waitcnt lgkmcnt(0)) inside a divergent branch -- no place for a piece that sits between two MFMAs.
+    const char* zero_line = (const char*)tup_pe_zero_line;
+    asm volatile("" : "+s"(zero_line));
+    const int refl_y = 2 * p.H - 2, refl_x = 2 * p.W - 2;
+    auto dma_token_piece = [&](int kc, int slot, int u) {  // 4 pieces per wave and stage: the count behind the loop's vmcnt(4)
+        char* dst = smem + slot * PE_A_BYTES + wave * 1024;
         const int i = kc >> 3, j = kc & 7;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const char* src;
-            if constexpr (AMODE == A_PATCH) {
-                int py = tpy[u] + i, px = tpx[u] + j;
-                const bool ok = patch_gather_pixel(p, py, px) && tval[u];
-                src = ok ? (const char*)p.A + tokoff[u] + (size_t)(py * p.W + px) * 128 : (const char*)tup_pe_zero_line;
-            } else {
-                src = tval[u] ? arow[u] + (size_t)kc * 128 : (const char*)tup_pe_zero_line;
-            }
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(dst + u * 8192), 16, 0, 0);
+        const char* src;
+        if constexpr (AMODE == A_PATCH) {
+            // patch_gather_pixel as selects (no branch per piece): beyond the map the pixel is reflected back, or, without
+            // reflect, the piece reads the zero line (the address formed from the reflected pixel is then not used)
+            int py = tpy[u] + i, px = tpx[u] + j;
+            const bool iy = py < p.H, ix = px < p.W;
+            py = iy ? py : refl_y - py;
+            px = ix ? px : refl_x - px;
+            const bool ok = tval[u] & (p.reflect != 0 || (iy & ix));
+            // 32-bit byte offset (launch_patch_embed_any checks that the map is below 4 GB; H, W < 2^24 with it)
+            const uint32_t off = tokoff[u] + (__umul24((unsigned)py, (unsigned)p.W) + (unsigned)px) * 128u;
+            src = ok ? (const char*)p.A + off : zero_line;
+        } else {
+            src = tval[u] ? arow[u] + (size_t)kc * 128 : zero_line;
         }
-#pragma unroll
-        for (int u = 0; u < NT64; ++u)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(w_thr + (size_t)u * 64 * p.K + kc * 64),
-                                             (__attribute__((address_space(3))) void*)(dst + PE_A_BYTES + u * 8192), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                         (__attribute__((address_space(3))) void*)(dst + u * 8192), 16, 0, 0);
     };
-    dma_stage(0, 0);
+    auto dma_weight_piece = [&](int kc, int slot, int u) {
+        char* dst = smem + W_BASE + slot * W_BYTES + wave * 1024;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(w_thr + (size_t)u * 64 * p.K + kc * 64),
+                                         (__attribute__((address_space(3))) void*)(dst + u * 8192), 16, 0, 0);
+    };
+    auto dma_tokens = [&](int kc, int slot) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) dma_token_piece(kc, slot, u);
+    };
+    auto dma_weights = [&](int kc, int slot) {
+#pragma unroll
+        for (int u = 0; u < NT64; ++u) dma_weight_piece(kc, slot, u);
+    };
+    dma_tokens(0, 0);
+    dma_weights(0, 0);
+    if (nk > 1) dma_tokens(1, 1);
 
     f32x4 acc[2][NTILE];
 #pragma unroll
@@ -792,24 +819,34 @@ __global__ __launch_bounds__(512, 2) void patch_embed_kernel(const GemmParams p)
 
     const uint32_t sbase = lds_addr(smem);
     const uint32_t a_off0 = (uint32_t)swz128(32 * wave + pl, g), a_off1 = (uint32_t)swz128(32 * wave + 16 + pl, g);
-    const uint32_t w_off = (uint32_t)(PE_A_BYTES + swz128(pl, g));
+    const uint32_t w_off = (uint32_t)(W_BASE + swz128(pl, g));
 
+    // The step's DMA pieces go out BETWEEN its MFMAs, not as a block behind the barrier: the CU's vector-memory path takes a piece
+    // (1 KB) every few hundred cycles while HBM is the limit, an issuing wave stalls on it, and with all eight waves issuing their
+    // seven pieces together the matrix pipes idled ~1,600 cycles of every 3,700-cycle step.  Order inside a wave as before (the
+    // weights of kc + 1 early in the step: they are read next step; then the tokens of kc + 2): the counted wait holds.
+    constexpr int TM = 4 * NTILE;                              // MFMAs per K-step and wave
+    auto piece_at = [](int pc) { return pc < NT64 ? 2 * pc : (pc - NT64 + 1) * TM / 5; };      // before which MFMA piece pc goes
+    int ts = 0;                                                // kc % 3: the token slot of stage kc
     for (int kc = 0; kc < nk; ++kc) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // own pieces of stage kc
-        __syncthreads();                                       // everyone's; everyone finished reading stage kc-1
-        if (kc + 1 < nk) dma_stage(kc + 1, (kc + 1) & 1);
-        __builtin_amdgcn_sched_barrier(0);
-        const uint32_t sb = sbase + (uint32_t)((kc & 1) * STAGE);
+        // own pieces of stage kc: vmcnt retires in order and the youngest group is the four token pieces of stage kc + 1
+        if (kc + 1 < nk) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                          // everyone's; everyone finished reading stage kc-1 (lds_wait<0> of q = 3)
+        const int ts2 = ts == 0 ? 2 : ts - 1;                  // (kc + 2) % 3 = (kc - 1) % 3
+        const bool has_w = kc + 1 < nk, has_t = kc + 2 < nk;
+        const uint32_t sa = sbase + (uint32_t)(ts * PE_A_BYTES), sw = sbase + (uint32_t)((kc & 1) * W_BYTES);
+        ts = ts == 2 ? 0 : ts + 1;
         // quarter steps q = 0..3: K half kh = q >> 1, weight tiles (q & 1)*QN .. +QN
         bf16x8 tf[3][2], wf[3][QN];
         auto ld1 = [&](int q, int slot, int j) {               // j = 0, 1: token fragments; 2..: weight tiles of the quarter
             const int nb = (q & 1) * QN;
             if (j < 2) {
-                const uint32_t a = sb + (j ? a_off1 : a_off0);
+                const uint32_t a = sa + (j ? a_off1 : a_off0);
                 tf[slot][j] = (q >> 1) ? lds_read_b128_asm_off_x64(a, 0) : lds_read_b128_asm_off(a, 0);
             } else {
-                wf[slot][j - 2] = (q >> 1) ? lds_read_b128_asm_off_x64(sb + w_off, (nb + j - 2) * 2048)
-                                           : lds_read_b128_asm_off(sb + w_off, (nb + j - 2) * 2048);
+                wf[slot][j - 2] = (q >> 1) ? lds_read_b128_asm_off_x64(sw + w_off, (nb + j - 2) * 2048)
+                                           : lds_read_b128_asm_off(sw + w_off, (nb + j - 2) * 2048);
             }
         };
         constexpr int PER = 2 + QN, NM = 2 * QN;
@@ -827,6 +864,12 @@ __global__ __launch_bounds__(512, 2) void patch_embed_kernel(const GemmParams p)
             int rd = 0;
 #pragma unroll
             for (int m = 0; m < NM; ++m) {
+#pragma unroll
+                for (int pc = 0; pc < NT64 + 4; ++pc)
+                    if (q * NM + m == piece_at(pc)) {
+                        if (pc < NT64) { if (has_w) dma_weight_piece(kc + 1, (kc + 1) & 1, pc); }
+                        else if (has_t) dma_token_piece(kc + 2, ts2, pc - NT64);
+                    }
                 if (q + 2 < 4) {
 #pragma unroll
                     for (int j = 0; j < PER; ++j)
@@ -862,7 +905,8 @@ template <int NT64, int AMODE = A_PATCH, int EPI = E_PATCH_EMBED>
 int launch_patch_embed(const GemmParams& p, hipStream_t s)
 {
     if (p.M <= 0) return 0;
-    constexpr size_t lds = 2 * (size_t)(PE_A_BYTES + NT64 * 64 * 128);
+    constexpr size_t lds = pe_lds_bytes(NT64);
+    static_assert(lds <= 163840, "LDS budget");
     TUP_SET_DYN_LDS((patch_embed_kernel<NT64, AMODE, EPI>), lds);
     patch_embed_kernel<NT64, AMODE, EPI><<<dim3((p.M + PE_BM - 1) / PE_BM), dim3(512), lds, s>>>(p);
     TUP_CHECK_LAUNCH();
@@ -874,7 +918,8 @@ int launch_patch_embed_any(const GemmParams& p, hipStream_t s)
     // the kernel keeps 32-bit byte offsets into the map: fine up to 4 GB of NHWC bf16 (B*H*W < 33.5 M pixels)
     const long long per_img = p.linear_tokens ? (long long)p.Ht * p.Wt_ : (long long)p.nWy * p.nWx * 64;
     const long long nimg = per_img > 0 ? p.M / per_img : 0;
-    const bool fits = nimg * (long long)p.H * p.W * 128 < (1LL << 32);
+    // (and forms a pixel index with a 24-bit multiply)
+    const bool fits = nimg * (long long)p.H * p.W * 128 < (1LL << 32) && p.H < (1 << 24) && p.W < (1 << 24);
     if (fits && p.K == 4096) {
         if (p.N == 192) return launch_patch_embed<3>(p, s);
         if (p.N == 128) return launch_patch_embed<2>(p, s);
