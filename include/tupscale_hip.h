@@ -134,10 +134,10 @@ int tup_tail_stream_r2_resize_parts_fwd(const float* part, const float* seamv, c
                                         const int* xmin, const int* xsize, const float* xw, int KX, const int* oxb, const int* oyb,
                                         int B, int H, int W, int Ho, int Wo, int sc, int band_h, int ext, int clamp01, void* stream);
 
-/* Where the four tup_tail_stream_r2_* entries take their 420 wave-uniform weights from: 0 = scalar loads straight from wfu_t / bfu /
- * wfc_t / bfc into scalar operands of the packed FMAs (the default; these four pointers must then be 16-byte aligned, or the entries
- * return hipErrorInvalidValue), 1 = an LDS image read through a vector-register ring (the form before; kept for same-box A/B runs).
- * Both give the same bits.  Process-wide.  Returns hipErrorInvalidValue for any other value. */
+/* Kept for ABI 15 only.  The four tup_tail_stream_r2_* entries take their 420 wave-uniform weights by scalar loads straight from
+ * wfu_t / bfu / wfc_t / bfc into scalar operands of the packed FMAs: these four pointers must be 16-byte aligned, or the entries
+ * return hipErrorInvalidValue.  This entry used to select an LDS image of the weights read through a vector-register ring (1)
+ * instead; that arm is gone.  0 is a no-op and returns 0; every other value, 1 included, returns hipErrorInvalidValue. */
 int tup_tail_stream_weight_source(int source);
 
 /* Inference fusion of the output tail (model.py:316-327): last final_upscale stage (Conv2d(3,3rr,3)+PixelShuffle),

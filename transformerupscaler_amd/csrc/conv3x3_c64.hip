@@ -349,22 +349,9 @@ __global__ __launch_bounds__(512, 2) void conv_c64_persistent_kernel(
                     *reinterpret_cast<u32x4*>(o + 8) = u32x4{pk[4], pk[5], pk[6], pk[7]};
                 }
             } else {
+                // thin output (the entry admits it with r = 1 only): rows 16ct+4g+reg are the real couts (< cout_valid), fp32 planar NCHW
                 if (!ok) continue;
                 float* o = reinterpret_cast<float*>(out);
-                const int rr = r * r, cimg = cout_valid / rr, Hr = H * r, Wr = W * r;
-                if (CT == 1 && r == 2) {
-                    // PixelShuffle(2) of a lane's four outputs (channel g, sub-pixels e = 2 si + sj): the two sj of a row are
-                    // adjacent in the HR plane, so they go out as one 8-byte store (16 lanes = 128 contiguous bytes)
-                    if (g < cimg) {
-                        float v[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = relu ? fmaxf(acc[pg][0][e], 0.f) : acc[pg][0][e];
-                        float* base = o + (((size_t)b * cimg + g) * Hr + oy * 2) * Wr + ox * 2;
-                        *reinterpret_cast<f32x2*>(base) = f32x2{v[0], v[1]};
-                        *reinterpret_cast<f32x2*>(base + Wr) = f32x2{v[2], v[3]};
-                    }
-                    continue;
-                }
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
@@ -373,9 +360,7 @@ __global__ __launch_bounds__(512, 2) void conv_c64_persistent_kernel(
                         if (co < cout_valid) {
                             float v = acc[pg][ct][e];
                             if (relu) v = fmaxf(v, 0.f);
-                            const int c = co / rr, sp = co - c * rr;
-                            const int si = sp / r, sj = sp - si * r;
-                            o[(((size_t)b * cimg + c) * Hr + (oy * r + si)) * Wr + (ox * r + sj)] = v;
+                            o[(((size_t)b * cout_valid + co) * H + oy) * W + ox] = v;
                         }
                     }
             }
@@ -469,9 +454,10 @@ int launch_persistent(const void* x, const void* wp, const float* bias, const vo
 }
 
 // ------------------------------------------------------------------------------------------------
-// Composed branch A at r = 2 (12 outputs) as a ROW GEMM.  The 25-tap form above (CT = 1, KS = 5) reads four pixel fragments
-// and one weight fragment from LDS for every four MFMAs -- each halo pixel 25 times -- and runs exactly at the LDS read rate
-// (1 MB per tile, 8 k cycles against 3.2 k of MFMA issue).  Here the horizontal taps ride in the GEMM's N instead:
+// Composed branch A at r = 2 (12 outputs) as a ROW GEMM.  A 25-tap form of the kernel above (CT = 1, KS = 5; rounds 1-2, since
+// removed) read four pixel fragments and one weight fragment from LDS for every four MFMAs -- each halo pixel 25 times -- and ran
+// exactly at the LDS read rate (1 MB per tile, 8 k cycles against 3.2 k of MFMA issue).  Here the horizontal taps ride in the
+// GEMM's N instead:
 //     part[y][x'][(c, dx)] = sum_dy sum_ci  in[y + dy][x'][ci] * w[dy][dx][c][ci]
 //     out[y][x][c]         = sum_dx part[y][x + dx][(c, dx)]
 // so a halo pixel is read five times (once per dy).  Only the LIVE taps are visited: the composition (packing.compose_branch_a)
@@ -889,8 +875,7 @@ extern "C" int tup_conv3x3_c64_fwd(const void* x, const void* wp, const float* b
         }
         if (out_mode == OUT_PLANAR_F32) {
             if (ntiles != 1 || r != 1 || cout_valid < 1 || cout_valid > 16 || add || mask) return (int)hipErrorInvalidValue;
-            static const bool thin_pingpong = TUP_ENV_FLAG("TUP_THIN_PINGPONG");      // A/B: the round 1-2 form
-            if (cout_valid <= 4 && !thin_pingpong) return launch_thin_rows(x, wp, bias, (float*)out, B, H, W, cout_valid, relu, s);
+            if (cout_valid <= 4) return launch_thin_rows(x, wp, bias, (float*)out, B, H, W, cout_valid, relu, s);
             return launch_persistent<1, OUT_PLANAR_F32, 3>(x, wp, bias, nullptr, nullptr, out, B, H, W, 1, 1, cout_valid, relu, s);
         }
         return (int)hipErrorInvalidValue;
@@ -928,7 +913,7 @@ extern "C" int tup_conv3x3_c64_fwd(const void* x, const void* wp, const float* b
 // wp / wv must come from a composition (packing.pack_branch_a, tup_bra_compose): output (si, sj)'s kernel is supported on the tap
 // rows / columns floor((s + d - 1) / r) + 1 .. + 3 over the 64->3 conv's taps d the variant keeps.  The border ring (wv, every r)
 // and the r = 2 row GEMM (wp: tap row 4 / 0 dead for si = 0 / 1, tap column 4 / 0 for sj = 0 / 1) read only the taps inside each
-// output's support and ignore whatever the other taps hold; the dense r = 3 / 6 and A/B paths multiply through all 25.
+// output's support and ignore whatever the other taps hold; the dense r = 3 / 6 kernels multiply through all 25.
 // r = 2: out must be 8-byte aligned (the two sj of an HR row leave in one store).
 extern "C" int tup_conv5x5_c64_planar_fwd(const void* x, const void* wp, const float* bias, const void* wv,
                                           const float* bv, float* out, int B, int H, int W, int r, int relu,
@@ -941,15 +926,9 @@ extern "C" int tup_conv5x5_c64_planar_fwd(const void* x, const void* wp, const f
     if (nblk > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int nout = 3 * r * r;
-    static const bool use_persistent5 = !TUP_ENV_FLAG("TUP_CONV_NONPERSISTENT");
-    static const bool use_taps25 = TUP_ENV_FLAG("TUP_BRA_TAPS25");       // A/B: the 25-tap form of round 1-2
-    if (r == 2 && use_persistent5) {
-        int e = use_taps25 ? launch_persistent<1, OUT_PLANAR_F32, 5>(x, wp, bias, nullptr, nullptr, out, B, H, W, 1, r, nout, relu, s)
-                           : launch_bra_rows(x, wp, bias, out, B, H, W, relu, s);
+    if (r == 2) {
+        const int e = launch_bra_rows(x, wp, bias, out, B, H, W, relu, s);
         if (e) return e;
-    } else if (r == 2) {
-        conv3x3_c64_kernel<1, OUT_PLANAR_F32, 5><<<dim3((unsigned)nblk), dim3(256), in_tile_bytes(5) + 2 * 16 * 128, s>>>(
-            (const bf16_t*)x, (const bf16_t*)wp, bias, nullptr, nullptr, out, H, W, 1, r, nout, relu, tilesX, tilesY, 1);
     } else if (r == 3) {
         const size_t lds = in_tile_bytes(5) + 2 * 32 * 128;
         TUP_SET_DYN_LDS((conv3x3_c64_kernel<2, OUT_PLANAR_F32, 5>), lds);

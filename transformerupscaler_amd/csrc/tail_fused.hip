@@ -329,22 +329,23 @@ extern "C" int tup_tail_fused_fwd(const float* x, const float* wfu, const float*
     const int nfu = 3 * r * r;
     const size_t lds = ((size_t)nfu * 28 + ((nfu + 1) & ~1) + 88 + 3 * (size_t)p.LH * p.LW + 3 * (size_t)(EH + 2) * (EW + 2) + 3 * (size_t)EH * EW + 2) * sizeof(float);
     if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-    // OCC = waves per SIMD the register allocator must allow: 4 (<= 128 VGPRs, 16 waves per CU) or 2
-    static const bool occ2 = TUP_ENV_FLAG("TUP_TAIL_OCC2");
-    static const bool occ3 = TUP_ENV_FLAG("TUP_TAIL_OCC3");        // 170 VGPRs: no spills, three workgroups per CU
     dim3 grid((Wo + OT_W - 1) / OT_W, (Ho + OT_H - 1) / OT_H, B);
 #define TUP_TAIL_LAUNCH(OCC, ST) do { \
         hipError_t e = hipFuncSetAttribute((const void*)tail_fused_kernel<OCC, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         if (e != hipSuccess) return (int)e; \
         tail_fused_kernel<OCC, ST><<<grid, dim3(NT), lds, reinterpret_cast<hipStream_t>(stream)>>>(p); } while (0)
+    // OCC = waves per SIMD the register allocator must allow.  The product runs 4 (<= 128 VGPRs, 16 waves per CU); the stamped
+    // instances and the occupancy experiments exist in the diagnostic build only
 #ifdef TUP_DIAG          // `make diag` only
+    static const bool occ2 = TUP_ENV_FLAG("TUP_TAIL_OCC2");
+    static const bool occ3 = TUP_ENV_FLAG("TUP_TAIL_OCC3");        // 170 VGPRs: no spills, three workgroups per CU
     if (stamps_on && occ2) TUP_TAIL_LAUNCH(2, true);      // spill-free stamps (the <4, true> build spills 143 VGPRs: its shares mislead)
     else if (stamps_on) TUP_TAIL_LAUNCH(4, true);
+    else if (occ2) TUP_TAIL_LAUNCH(2, false);
+    else if (occ3) TUP_TAIL_LAUNCH(3, false);
     else
 #endif
-    if (occ2) TUP_TAIL_LAUNCH(2, false);
-    else if (occ3) TUP_TAIL_LAUNCH(3, false);
-    else TUP_TAIL_LAUNCH(4, false);
+    TUP_TAIL_LAUNCH(4, false);
 #undef TUP_TAIL_LAUNCH
     TUP_CHECK_LAUNCH();
     return 0;

@@ -13,9 +13,9 @@
 // 28 k cycles).  Here a WAVE owns 64 consecutive LR columns (60 produce output, 2 + 2 are halo) and marches down the LR rows of
 // a band: a lane keeps its column's 3-row LR window and its 5-row t1 window in registers, gets its horizontal neighbours with
 // DPP wave shifts (v_mov_b32_dpp wave_shr:1 / wave_shl:1) and the 405 wave-uniform weights as scalar operands of its packed FMAs
-// (SW = true: scalar loads straight from the weight tensors into an asm-managed ring of 2 x 12 SGPRs; the kernel body describes the
-// ring and the LDS-broadcast arm SW = false that it replaces); per LR row and lane 324 + 324 FMAs, 3 + 6 loads (requested one row
-// ahead) and 6 stores; nothing is recomputed except two t1 rows per band.
+// (scalar loads straight from the weight tensors into an asm-managed ring of 2 x 12 SGPRs; the kernel body describes the ring);
+// per LR row and lane 324 + 324 FMAs, 3 + 6 loads (requested one row ahead) and 6 stores; nothing is recomputed except two t1
+// rows per band.
 // HBM sees x, upscaled_input and out once each: bound = HBM / VALU issue, about equal.
 //
 // PARTS = true: x is not in HBM as a finished plane.  The kernel takes the pieces that decoder_fused_kernel (decoder_fused.hip) leaves
@@ -29,7 +29,7 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) float f32x8;
 
 constexpr int TS_COLS = 60;         // output LR columns per wave (lanes 2..61)
-constexpr int TS_WBATCH = 1;        // SW: weight groups per batch of the scalar ring (one wait per batch; the ring holds two batches)
+constexpr int TS_WBATCH = 1;        // weight groups per batch of the scalar ring (one wait per batch; the ring holds two batches)
 constexpr int TS_BAND_MIN = 12;     // LR rows per band: chosen by the launcher (a multiple of 3: the register windows rotate with period 3)
 
 struct TailStreamParams {
@@ -72,9 +72,7 @@ TUP_DEVICE float from_right(float v) {    // lane l <- lane l + 1 (0 into lane 6
 
 // (the pointers are separate __restrict__ parameters: hipcc's own scalar loads inside the row loop stay scalar loads only while it can
 // prove that the kernel's own stores do not alias them)
-// SW = true: the weights are scalar operands (the form the launcher takes by default); SW = false: the LDS image + VGPR ring of the
-// rounds before, kept as the second arm of the same-box A/B (tup_tail_stream_weight_source) until a second box has confirmed the gain.
-template <bool RESIZE, bool PARTS, bool SW>
+template <bool RESIZE, bool PARTS>
 __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
     const float* __restrict__ x_arg, const float* __restrict__ wfu_arg, const float* __restrict__ bfu_arg,
     const float* __restrict__ wfc_arg, const float* __restrict__ bfc_arg, const float* __restrict__ ui_arg, float* __restrict__ out_arg,
@@ -84,26 +82,15 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
     // flight in 16-dword bursts and spill ~300 SGPRs through v_writelane / v_readlane (18 % of the loop's VALU issues).  The weight
     // stream of an iteration is 36 groups of 12 floats -- group g < 27 = tap g of the 3 -> 12 conv (12 outputs), group 27 + j = taps
     // 3j .. 3j+2 of the 3 -> 3 conv (4 floats each) -- and the biases bfu [12], bfc [3].
-    //  * SW: a group is one s_load_dwordx8 + one s_load_dwordx4 straight from the weight tensors into a ring of 2 x TS_WBATCH groups of
-    //    12 SGPRs, written as inline asm so that the ring is ours, not hipcc's; the packed FMAs take an SGPR pair as their weight
-    //    operand.  Scalar loads may return out of order, so the only wait is lgkmcnt(0): wait for batch k, request batch k + 1 into
-    //    the other half of the ring, compute batch k.  The biases stay in vector registers.  No LDS image, no barrier.
-    //  * !SW: the groups and the biases live in LDS and are read with same-address (broadcast, conflict-free) ds_read_b128 through a
-    //    hand-pipelined ring of 3 x 12 VGPRs (+ 16 for the biases); the reads are inline asm (hipcc would hoist all of them to the top
-    //    of the stage and spill 200 VGPRs); waits are counted by hand.  The only barrier of the kernel follows the copy.
-    __shared__ __attribute__((aligned(16))) float wl[SW ? 4 : 36 * 12 + 12 + 4];
+    // A group is one s_load_dwordx8 + one s_load_dwordx4 straight from the weight tensors into a ring of 2 x TS_WBATCH groups of
+    // 12 SGPRs, written as inline asm so that the ring is ours, not hipcc's; the packed FMAs take an SGPR pair as their weight
+    // operand.  Scalar loads may return out of order, so the only wait is lgkmcnt(0): wait for batch k, request batch k + 1 into
+    // the other half of the ring, compute batch k.  The biases stay in vector registers.  No LDS image of the weights, no barrier.
     __shared__ __attribute__((aligned(16))) float hb[RESIZE ? 4 : 1][3][128];          // RESIZE: one vertically filtered HR line per wave
     __shared__ __attribute__((aligned(16))) float xwl[RESIZE ? 4 : 1][2][64][4];       // RESIZE: the lanes' horizontal tap weights (per wave, pass, lane)
     // RESIZE: the last six HR rows of the sums (slot = HR row % 6 = 2 (LR row % 3) + i), per wave, channel and lane -- in LDS, not in 36
     // registers: a lane only ever reads what it wrote itself; an output row reads its (at most four) tap rows
     __shared__ __attribute__((aligned(16))) f32x2 vrl[RESIZE ? 4 : 1][6][3][64];
-    if constexpr (!SW) {
-        for (int i = threadIdx.x; i < 27 * 12; i += 256) wl[i] = wfu_arg[i];
-        if (threadIdx.x < 27 * 4) wl[324 + threadIdx.x] = wfc_arg[threadIdx.x];
-        if (threadIdx.x < 12) wl[432 + threadIdx.x] = bfu_arg[threadIdx.x];
-        if (threadIdx.x < 4) wl[444 + threadIdx.x] = threadIdx.x < 3 ? bfc_arg[threadIdx.x] : 0.f;
-        __syncthreads();
-    }
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
     if (wid >= p.B * p.nband * p.nstrip) return;
@@ -123,16 +110,15 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ui_arg), 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(out_arg, 0, 0x7fffffff, 0x00020000);
     const unsigned vx = xc * 4u, vu = xc * 8u;
-    // SW: per-channel lane offsets, so that a row's three channels share one wave-uniform row offset (vector registers are what this
-    // arm has to spare; scalar ones are what its weight ring lives in).  The launcher's 2^29-element limits cover the sums.
+    // per-channel lane offsets, so that a row's three channels share one wave-uniform row offset (vector registers are what the
+    // kernel has to spare; scalar ones are what its weight ring lives in).  The launcher's 2^29-element limits cover the sums.
+    // (The initialisers are overwritten at once; hipcc numbers the registers of the prologue after them.)
     unsigned vxc[3] = {vx, vx, vx}, vuc[3] = {vu, vu, vu};
-    if constexpr (SW) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            vxc[c] = vx + (unsigned)(c * H * W) * 4u;
-            vuc[c] = vu + (unsigned)(c * Hs * Ws) * 4u;
-            asm volatile("" : "+v"(vxc[c]), "+v"(vuc[c]));
-        }
+    for (int c = 0; c < 3; ++c) {
+        vxc[c] = vx + (unsigned)(c * H * W) * 4u;
+        vuc[c] = vu + (unsigned)(c * Hs * Ws) * 4u;
+        asm volatile("" : "+v"(vxc[c]), "+v"(vuc[c]));
     }
     // PARTS: seamv is addressed as part is (same shape).  A lane's column is fixed, so is its role at a 32-column tile edge of the
     // decoder: column 31 of a tile takes the next tile's column 0 (side 0), column 0 the previous tile's column 31 (side 1); the
@@ -153,7 +139,7 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             b2v[c] = p.b2[c];
-            if constexpr (SW) asm volatile("" : "+v"(b2v[c]));      // in a vector register (there is room; the scalar file is what the weight ring lives in)
+            asm volatile("" : "+v"(b2v[c]));      // in a vector register (there is room; the scalar file is what the weight ring lives in)
         }
     }
 
@@ -173,7 +159,7 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
     int oxl[2] = {0, 0}, xi[2] = {0, 0};
     bool hval[2] = {false, false};
     int oy = 0, oy_end = 0;
-    unsigned voc[2][3] = {{0u, 0u, 0u}, {0u, 0u, 0u}};       // SW: the lane offsets of the output columns per channel
+    unsigned voc[2][3] = {{0u, 0u, 0u}, {0u, 0u, 0u}};       // the lane offsets of the output columns per channel
     const int wv = threadIdx.x >> 6;
     if constexpr (RESIZE) {
         const int ox0 = p.oxb[strip], ox1 = p.oxb[strip + 1];
@@ -191,15 +177,13 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
             for (int t = 0; t < 4; ++t) wq4[t] = (hval[q] && t < p.KX) ? p.xw[oxl[q] * p.KX + t] : 0.f;
             *reinterpret_cast<f32x4*>(&xwl[wv][q][lane][0]) = wq4;
         }
-        if constexpr (SW) {
 #pragma unroll
-            for (int q = 0; q < 2; ++q)
+        for (int q = 0; q < 2; ++q)
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    voc[q][c] = (unsigned)oxl[q] * 4u + (unsigned)(c * p.Ho * p.Wo) * 4u;
-                    asm volatile("" : "+v"(voc[q][c]));
-                }
-        }
+            for (int c = 0; c < 3; ++c) {
+                voc[q][c] = (unsigned)oxl[q] * 4u + (unsigned)(c * p.Ho * p.Wo) * 4u;
+                asm volatile("" : "+v"(voc[q][c]));
+            }
         oy = p.oyb[band];
         oy_end = p.oyb[band + 1];
     }
@@ -207,24 +191,18 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
     float nyw[4] = {0.f, 0.f, 0.f, 0.f};
     auto fetch_row_taps = [&](int row) __attribute__((always_inline)) {
         const int rr = row < oy_end ? row : oy_end - 1;
-        if constexpr (SW) {
-            // hipcc cannot prove that the kernel's stores leave the tables alone and reads them with VECTOR loads (global_load_dword +
-            // v_readfirstlane behind a vmcnt(0) that also drains the next row's prefetch, one branch per tap for `a < KY`).  Here: six
-            // scalar loads and their wait in ONE statement (nothing of the weight ring is in flight where this is called, and the
-            // destinations are valid when the statement ends: no RULE to keep).  A tap index beyond KY re-reads the row's last tap:
-            // the emission masks every tap beyond the row's count (<= KY) to weight 0.
-            int off[4];
+        // hipcc cannot prove that the kernel's stores leave the tables alone and would read them with VECTOR loads (global_load_dword +
+        // v_readfirstlane behind a vmcnt(0) that also drains the next row's prefetch, one branch per tap for `a < KY`).  Here: six
+        // scalar loads and their wait in ONE statement (nothing of the weight ring is in flight where this is called, and the
+        // destinations are valid when the statement ends: no RULE to keep).  A tap index beyond KY re-reads the row's last tap:
+        // the emission masks every tap beyond the row's count (<= KY) to weight 0.
+        int off[4];
 #pragma unroll
-            for (int a = 0; a < 4; ++a) off[a] = (rr * p.KY + min(a, p.KY - 1)) * 4;
-            asm volatile("s_load_dword %0, %6, %9\n\ts_load_dword %1, %7, %9\n\ts_load_dword %2, %8, %10\n\ts_load_dword %3, %8, %11\n\t"
-                         "s_load_dword %4, %8, %12\n\ts_load_dword %5, %8, %13\n\ts_waitcnt lgkmcnt(0)"
-                         : "=&s"(nym), "=&s"(nyn), "=&s"(nyw[0]), "=&s"(nyw[1]), "=&s"(nyw[2]), "=&s"(nyw[3])
-                         : "s"(p.ymin), "s"(p.ysize), "s"(p.yw), "s"(rr * 4), "s"(off[0]), "s"(off[1]), "s"(off[2]), "s"(off[3]));
-        } else {
-            nym = p.ymin[rr]; nyn = p.ysize[rr];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) nyw[a] = a < p.KY ? p.yw[rr * p.KY + a] : 0.f;
-        }
+        for (int a = 0; a < 4; ++a) off[a] = (rr * p.KY + min(a, p.KY - 1)) * 4;
+        asm volatile("s_load_dword %0, %6, %9\n\ts_load_dword %1, %7, %9\n\ts_load_dword %2, %8, %10\n\ts_load_dword %3, %8, %11\n\t"
+                     "s_load_dword %4, %8, %12\n\ts_load_dword %5, %8, %13\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&s"(nym), "=&s"(nyn), "=&s"(nyw[0]), "=&s"(nyw[1]), "=&s"(nyw[2]), "=&s"(nyw[3])
+                     : "s"(p.ymin), "s"(p.ysize), "s"(p.yw), "s"(rr * 4), "s"(off[0]), "s"(off[1]), "s"(off[2]), "s"(off[3]));
     };
     if constexpr (RESIZE) { if (oy < oy_end) fetch_row_taps(oy); }
 
@@ -233,9 +211,9 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
         const int rr = rok ? row : 0;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            // SW: the channel's plane offset rides in the lane offset (vxc), so one row offset serves the three channels
-            const unsigned vo = SW ? vxc[c] : vx;
-            const int so = SW ? ((b * 3 * H + rr) * W) * 4 : (((b * 3 + c) * H + rr) * W) * 4;
+            // the channel's plane offset rides in the lane offset (vxc), so one row offset serves the three channels
+            const unsigned vo = vxc[c];
+            const int so = ((b * 3 * H + rr) * W) * 4;
             dst[c][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, vo, so, 0));
             if constexpr (PARTS)
                 dst[c][1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsv, vo, so, 0));
@@ -247,11 +225,9 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
                 const int yy = min(max(row + dy - 1, 0), H - 1);
 #pragma unroll
                 for (int c = 0; c < 3; ++c)
-                    // (SW: the constant part of the record offset on the lane side, where it folds into the instruction's offset field)
-                    cd[c][dy] = SW ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                         rcs, vcs + (unsigned)(c * 4 + dy) * 4u, ((b * H + yy) * p.tilesX * 32) * 4, 0))
-                                   : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                         rcs, vcs, ((b * H + yy) * p.tilesX * 32 + c * 4 + dy) * 4, 0));
+                    // (the constant part of the record offset on the lane side, where it folds into the instruction's offset field)
+                    cd[c][dy] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+                        rcs, vcs + (unsigned)(c * 4 + dy) * 4u, ((b * H + yy) * p.tilesX * 32) * 4, 0));
             }
         }
     };
@@ -284,50 +260,28 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
 #pragma unroll
             for (int i = 0; i < 2; ++i)
                 un[buf][c][i] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(
-                    ru, SW ? vuc[c] : vu, SW ? ((b * 3 * Hs + 2 * qq + i) * Ws) * 4 : (((b * 3 + c) * Hs + 2 * qq + i) * Ws) * 4, 0));
+                    ru, vuc[c], ((b * 3 * Hs + 2 * qq + i) * Ws) * 4, 0));
     };
 
-    // ---- !SW: the LDS ring ----
-    const uint32_t wbase = SW ? 0u : lds_addr(wl);
-    f32x4 ring[3][3];
-    auto rd = [&](int g) __attribute__((always_inline)) {       // group g (0..35) or the biases (g = 36: bfu, + bfc in slot [3][..] of `bias`)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[g % 3][j]) : "v"(wbase), "i"((g * 12 + j * 4) * 4));
-    };
-    // bfu (three reads at the top of stage B) and bfc (one read in front of the last group request of stage B: live for one group
-    // instead of for the whole stage)
-    f32x4 bias[4];
-    auto rd_bias = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bias[j]) : "v"(wbase), "i"((432 + j * 4) * 4));
-    };
-    auto rd_bias3 = [&]() __attribute__((always_inline)) {
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bias[3]) : "v"(wbase), "i"((432 + 12) * 4));
-    };
-
-    // ---- SW: the scalar ring.  Group i of the stream above (0..35) lives in slot i % (2 TS_WBATCH).  RULE (below) for SGPR
+    // ---- the scalar ring.  Group i of the stream above (0..35) lives in slot i % (2 TS_WBATCH).  RULE (below) for SGPR
     //      destinations: the wait statement of a batch names every destination of the batch as "+s", so to hipcc the values are
     //      DEFINED at the wait and no reader can be scheduled above it.  Early clobber: the second load of a statement still reads
-    //      the base pointer.  The 15 biases are not part of the ring: they sit in vector registers for the whole band (this arm has
+    //      the base pointer.  The 15 biases are not part of the ring: they sit in vector registers for the whole band (the kernel has
     //      them to spare), as the addend of a row's first FMAs -- from scalar registers they would cost a v_mov each, every row. ----
     constexpr int NS = 2 * TS_WBATCH;
     f32x8 slo[NS];
     f32x4 shi[NS];
     f32x2 bfuv[6];
-    float bfcv[3] = {0.f, 0.f, 0.f};
-    if constexpr (SW) {
+    float bfcv[3];
 #pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            bfuv[j] = f32x2{bfu_arg[2 * j], bfu_arg[2 * j + 1]};
-            asm volatile("" : "+v"(bfuv[j]));
-        }
+    for (int j = 0; j < 6; ++j) {
+        bfuv[j] = f32x2{bfu_arg[2 * j], bfu_arg[2 * j + 1]};
+        asm volatile("" : "+v"(bfuv[j]));
+    }
 #pragma unroll
-        for (int o = 0; o < 3; ++o) {
-            bfcv[o] = bfc_arg[o];
-            asm volatile("" : "+v"(bfcv[o]));
-        }
+    for (int o = 0; o < 3; ++o) {
+        bfcv[o] = bfc_arg[o];
+        asm volatile("" : "+v"(bfcv[o]));
     }
     auto sw_request = [&](int i) __attribute__((always_inline)) {
         if (i < 27)
@@ -353,37 +307,21 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
     };
     // the weight pair j (outputs 2j, 2j+1) of tap g of the 3 -> 12 conv (g = -1: bfu), and weight idx = kx * 4 + o of group g >= 27
     auto wB = [&](int g, int j) __attribute__((always_inline)) -> f32x2 {
-        if constexpr (SW) {
-            if (g < 0) return bfuv[j];
-            const int sl = g % NS;
-            return j < 4 ? f32x2{slo[sl][2 * j], slo[sl][2 * j + 1]} : f32x2{shi[sl][2 * j - 8], shi[sl][2 * j - 7]};
-        } else {
-            const f32x4 wq = g < 0 ? bias[j >> 1] : ring[g % 3][j >> 1];
-            return f32x2{wq[2 * (j & 1)], wq[2 * (j & 1) + 1]};
-        }
+        if (g < 0) return bfuv[j];
+        const int sl = g % NS;
+        return j < 4 ? f32x2{slo[sl][2 * j], slo[sl][2 * j + 1]} : f32x2{shi[sl][2 * j - 8], shi[sl][2 * j - 7]};
     };
     auto wC = [&](int g, int idx) __attribute__((always_inline)) -> float {
-        if constexpr (SW) {
-            const int sl = g % NS;
-            return idx < 8 ? slo[sl][idx] : shi[sl][idx - 8];
-        } else {
-            return ring[g % 3][idx >> 2][idx & 3];
-        }
+        const int sl = g % NS;
+        return idx < 8 ? slo[sl][idx] : shi[sl][idx - 8];
     };
 
     // One LR row: stage B = T(r) from the LR rows r-1, r, r+1 (slots SM, S, SP), zero outside the image (the 3 -> 3 conv zero-pads
     // t1); stage C (doC) = HR rows 2q, 2q+1 of LR row q = r - 1 from t1 rows 2q-1 .. 2q+2 = T(q-1) row 1 (slot SP), T(q) rows 0, 1
     // (slot SM), T(q+1) row 0 (slot S), + upscaled_input (buffer ub) + bias, [clamp], store.
     auto stages = [&](int r, int SM, int S, int SP, bool doC, int ub) __attribute__((always_inline)) {
-        if constexpr (SW) {
 #pragma unroll
-            for (int n = 0; n < TS_WBATCH; ++n) sw_request(n);
-        } else {
-            rd_bias();
-            rd(0); rd(1);
-            lds_wait<6>();
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        for (int n = 0; n < TS_WBATCH; ++n) sw_request(n);
         // RULE for the asynchronous reads: hipcc believes an asm output is written AT the asm statement.  An output that is never
         // used afterwards is dead to it from that point: the register goes to the next value computed, and the data lands on
         // top of that value later.  So every read's destination is "used" (really, or by an empty asm) BEHIND the wait that
@@ -396,16 +334,7 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
         const int slots[3] = {SM, S, SP};
 #pragma unroll
         for (int g = 0; g < 27; ++g) {
-            if constexpr (SW) {
-                sw_step(g);
-            } else {
-                // (the groups of the 3 -> 3 conv are requested whether or not stage C runs: a conditional request costs hipcc's register
-                //  allocation more than the six wasted reads of a band's first two rows)
-                // (request order at g = 26: groups 26 [being waited for], 27, bfc, 28 -- ten reads, the four oldest done = group 26)
-                if (g == 26) rd_bias3();
-                rd(g + 2); lds_wait<6>();
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            sw_step(g);
             const float xo = X[slots[(g / 3) % 3]][g / 9];
             const float v = g % 3 == 0 ? from_left(xo) : g % 3 == 2 ? from_right(xo) : xo;
             const f32x2 vv = {v, v};
@@ -417,22 +346,12 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        // !SW: without stage C the two groups requested ahead (27, 28) are never used: drain, and keep their registers reserved until
-        // then (RULE above; found as wrong first rows of every band but the first -- the last taps' FMAs had been given the
-        // registers of the pending reads).
-        if constexpr (!SW) {
-            if (!doC) {
-                lds_wait<0>();
+        // without stage C the group requested ahead (27) is never used: drain, and keep its registers reserved until then (RULE
+        // above: otherwise the last taps' FMAs may be given the registers of the pending loads)
+        if (!doC) {
+            lds_wait<0>();
 #pragma unroll
-                for (int j = 0; j < 3; ++j) asm volatile("" ::"v"(ring[27 % 3][j]), "v"(ring[28 % 3][j]));      // groups 27, 28: see RULE
-                asm volatile("" ::"v"(bias[3]));                                                                 // ... and bfc
-            }
-        } else {
-            if (!doC) {
-                lds_wait<0>();
-#pragma unroll
-                for (int n = 27; n < SW_AHEAD_END && n < 36; ++n) asm volatile("" ::"s"(slo[n % NS]), "s"(shi[n % NS]));      // see RULE
-            }
+            for (int n = 27; n < SW_AHEAD_END && n < 36; ++n) asm volatile("" ::"s"(slo[n % NS]), "s"(shi[n % NS]));      // see RULE
         }
         __builtin_amdgcn_sched_barrier(0);
         const bool ok = colok && r >= 0 && r < H;
@@ -448,29 +367,13 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
         if (!doC) return;
         const int q = r - 1;
         f32x2 ac[2][3];                 // [HR row][channel] = columns 2x, 2x+1
-        if constexpr (SW) {
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int o = 0; o < 3; ++o) ac[i][o] = un[ub][o][i] + f32x2{bfcv[o], bfcv[o]};
-        } else {
-            lds_wait<3>();                  // outstanding: group 27, bfc, group 28 -> the first two have landed
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int o = 0; o < 3; ++o) ac[i][o] = un[ub][o][i] + f32x2{bias[3][o], bias[3][o]};
-        }
+            for (int o = 0; o < 3; ++o) ac[i][o] = un[ub][o][i] + f32x2{bfcv[o], bfcv[o]};
 #pragma unroll
         for (int g = 27; g < 36; ++g) {
-            if constexpr (SW) {
-                sw_step(g);
-            } else {
-                if (g + 2 < 36) { rd(g + 2); lds_wait<6>(); }
-                else if (g + 1 < 36) lds_wait<3>();
-                else lds_wait<0>();
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            sw_step(g);
             const int c = (g - 27) / 3, ky = (g - 27) % 3;
             // t1 row of (output row i, tap row ky): i = 0 -> T(q-1)[1], T(q)[0], T(q)[1];  i = 1 -> T(q)[0], T(q)[1], T(q+1)[0]
             const int s0 = ky == 0 ? SP : SM, h0 = ky == 0 ? 1 : ky == 1 ? 0 : 1;      // (slot, HR row) of the t1 row under output row 0
@@ -500,8 +403,7 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
                     for (int i = 0; i < 2; ++i) {
                         f32x2 v = ac[i][o];
                         if (p.clamp01) { v[0] = fminf(fmaxf(v[0], 0.f), 1.f); v[1] = fminf(fmaxf(v[1], 0.f), 1.f); }
-                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), ro, SW ? vuc[o] : vu,
-                                                              SW ? ((b * 3 * Hs + 2 * q + i) * Ws) * 4 : (((b * 3 + o) * Hs + 2 * q + i) * Ws) * 4, 0);
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), ro, vuc[o], ((b * 3 * Hs + 2 * q + i) * Ws) * 4, 0);
                     }
             }
         } else {
@@ -541,8 +443,7 @@ __global__ __launch_bounds__(256, 3) void tail_stream_r2_kernel(
 #pragma unroll
                             for (int t = 1; t < 4; ++t) o = __builtin_fmaf(xwt[t], hb[wv][c][xi[pq] + t], o);
                             if (p.clamp01) o = fminf(fmaxf(o, 0.f), 1.f);
-                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o), ro, SW ? voc[pq][c] : (unsigned)oxl[pq] * 4u,
-                                                                  SW ? ((b * 3 * p.Ho + oy) * p.Wo) * 4 : (((b * 3 + c) * p.Ho + oy) * p.Wo) * 4, 0);
+                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o), ro, voc[pq][c], ((b * 3 * p.Ho + oy) * p.Wo) * 4, 0);
                         }
                     }
                 ++oy;
@@ -592,9 +493,6 @@ namespace {
 // the unfinished decoder output (PARTS) in place of x: what tup_decoder_fused_parts_fwd left in HBM
 struct TailParts { const float* part; const float* seamv; const float* cseam; const float* b2; int tilesX; };
 
-// where the kernels take their weights from: 0 = scalar operands (SW = true), 1 = the LDS ring (tup_tail_stream_weight_source)
-int g_weight_source = 0;
-
 int launch_tail_stream(TailStreamParams& p, const float* x, const TailParts* parts, const float* wfu_t, const float* bfu,
                        const float* wfc_t, const float* bfc, const float* ui, float* out, bool resize, void* stream)
 {
@@ -608,23 +506,15 @@ int launch_tail_stream(TailStreamParams& p, const float* x, const TailParts* par
     }
     const dim3 grid((unsigned)((waves + 3) / 4));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool sw = g_weight_source == 0;
     // the scalar loads of the weights are 16-byte reads at 16-byte offsets of these pointers
-    if (sw && ((reinterpret_cast<uintptr_t>(wfu_t) | reinterpret_cast<uintptr_t>(bfu) | reinterpret_cast<uintptr_t>(wfc_t) |
-                reinterpret_cast<uintptr_t>(bfc)) & 15u) != 0)
+    if (((reinterpret_cast<uintptr_t>(wfu_t) | reinterpret_cast<uintptr_t>(bfu) | reinterpret_cast<uintptr_t>(wfc_t) |
+          reinterpret_cast<uintptr_t>(bfc)) & 15u) != 0)
         return (int)hipErrorInvalidValue;
-#define TUP_TAIL_LAUNCH(R, P, S) tail_stream_r2_kernel<R, P, S><<<grid, dim3(256), 0, s>>>(x, wfu_t, bfu, wfc_t, bfc, ui, out, p)
-    if (sw) {
-        if (resize && parts) TUP_TAIL_LAUNCH(true, true, true);
-        else if (resize) TUP_TAIL_LAUNCH(true, false, true);
-        else if (parts) TUP_TAIL_LAUNCH(false, true, true);
-        else TUP_TAIL_LAUNCH(false, false, true);
-    } else {
-        if (resize && parts) TUP_TAIL_LAUNCH(true, true, false);
-        else if (resize) TUP_TAIL_LAUNCH(true, false, false);
-        else if (parts) TUP_TAIL_LAUNCH(false, true, false);
-        else TUP_TAIL_LAUNCH(false, false, false);
-    }
+#define TUP_TAIL_LAUNCH(R, P) tail_stream_r2_kernel<R, P><<<grid, dim3(256), 0, s>>>(x, wfu_t, bfu, wfc_t, bfc, ui, out, p)
+    if (resize && parts) TUP_TAIL_LAUNCH(true, true);
+    else if (resize) TUP_TAIL_LAUNCH(true, false);
+    else if (parts) TUP_TAIL_LAUNCH(false, true);
+    else TUP_TAIL_LAUNCH(false, false);
 #undef TUP_TAIL_LAUNCH
     TUP_CHECK_LAUNCH();
     return 0;
@@ -718,12 +608,9 @@ extern "C" int tup_tail_stream_r2_resize_parts_fwd(const float* part, const floa
                               B, H, W, Ho, Wo, sc, band_h, ext, clamp01, stream);
 }
 
-// Which arm of the streaming tail the four entries above launch from now on: 0 = the weights as scalar operands (the default), 1 = the
-// LDS image and VGPR ring.  Both compute the same bits; the switch exists for same-box A/B runs and the equality tests.  Process-wide,
-// not synchronised with launches in flight on other threads.
+// Kept for ABI 15 only.  It used to choose between the weights as scalar operands (0) and an LDS image of them read through a ring of
+// vector registers (1); the LDS arm is gone, so 0 is a no-op and every other value is refused.
 extern "C" int tup_tail_stream_weight_source(int source)
 {
-    if (source != 0 && source != 1) return (int)hipErrorInvalidValue;
-    g_weight_source = source;
-    return 0;
+    return source == 0 ? 0 : (int)hipErrorInvalidValue;
 }

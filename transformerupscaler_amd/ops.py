@@ -318,16 +318,6 @@ def tail_stream_r2(x, wfu_t, bfu, wfc_t, bfc, ui, clamp=True, out_hw=None, parts
     return out
 
 
-TAIL_STREAM_WEIGHT_SOURCES = ("scalar", "lds")
-
-
-def tail_stream_weight_source(source):
-    """Which arm of the streaming tail (csrc/tail_stream.hip) tail_stream_r2 launches from now on, process-wide: "scalar" = the weights
-    as scalar operands of the packed FMAs (the default), "lds" = the LDS image and vector-register ring.  Both give the same bits; the
-    switch exists for same-box A/B runs and the equality tests."""
-    _lib.call("tup_tail_stream_weight_source", TAIL_STREAM_WEIGHT_SOURCES.index(source))
-
-
 def clamp01(x):
     out = torch.empty_like(x)
     _lib.call("tup_clamp01_fwd", _chk(x, F32, None, "x"), out.data_ptr(), x.numel(), _stream())
