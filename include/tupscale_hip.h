@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-/* library / ABI version, bumped when a signature changes */
+/* library / ABI version, bumped when a signature changes or an entry is removed (16: seven entries removed, none changed) */
 int tup_abi_version(void);
 
 /* conv1: Conv2d(3,64,k3,p1)+ReLU. model.py:202-203,251.
@@ -107,7 +107,9 @@ int tup_resize_aa_fwd(const float* in, float* out, const int* ymin, const int* y
 /* The same output tail for a last stage of r = 2 (scales 2 and 4) WITHOUT the Resize, as a register-streaming stencil (no LDS):
  * final_upscale's last Conv2d(3,12,3)+PixelShuffle(2) utils.py:62-63,74-75, final_upscale_conv + "+ upscaled_input"
  * model.py:316-320 [+ clamp model.py:327].  x fp32 [B][3][H][W]; wfu_t fp32 [27][12], wfc_t fp32 [27][4] tap-major
- * (k = cin*9 + ky*3 + kx; packing.pack_planar_t); bfu [12], bfc [3]; ui / out fp32 [B][3][2H][2W]. */
+ * (k = cin*9 + ky*3 + kx; packing.pack_planar_t); bfu [12], bfc [3]; ui / out fp32 [B][3][2H][2W].
+ * The four tup_tail_stream_r2_* entries take their 420 wave-uniform weights by scalar loads straight from wfu_t / bfu / wfc_t / bfc
+ * into scalar operands of the packed FMAs: these four pointers must be 16-byte aligned, or the entries return hipErrorInvalidValue. */
 int tup_tail_stream_r2_fwd(const float* x, const float* wfu_t, const float* bfu, const float* wfc_t, const float* bfc,
                            const float* ui, float* out, int B, int H, int W, int clamp01, void* stream);
 
@@ -133,12 +135,6 @@ int tup_tail_stream_r2_resize_parts_fwd(const float* part, const float* seamv, c
                                         const float* ui, float* out, const int* ymin, const int* ysize, const float* yw, int KY,
                                         const int* xmin, const int* xsize, const float* xw, int KX, const int* oxb, const int* oyb,
                                         int B, int H, int W, int Ho, int Wo, int sc, int band_h, int ext, int clamp01, void* stream);
-
-/* Kept for ABI 15 only.  The four tup_tail_stream_r2_* entries take their 420 wave-uniform weights by scalar loads straight from
- * wfu_t / bfu / wfc_t / bfc into scalar operands of the packed FMAs: these four pointers must be 16-byte aligned, or the entries
- * return hipErrorInvalidValue.  This entry used to select an LDS image of the weights read through a vector-register ring (1)
- * instead; that arm is gone.  0 is a no-op and returns 0; every other value, 1 included, returns hipErrorInvalidValue. */
-int tup_tail_stream_weight_source(int source);
 
 /* Inference fusion of the output tail (model.py:316-327): last final_upscale stage (Conv2d(3,3rr,3)+PixelShuffle),
  * final_upscale_conv, "+ upscaled_input", Resize (tap tables; identity tables when sizes match) and clamp.
@@ -179,18 +175,6 @@ int tup_window_attn_fwd(const void* qkv, const float* bias_frag, void* out, floa
 int tup_gemm_tokens_fwd(const void* A, int a_dtype, int lda, const void* Wt, const float* bias,
                         const float* res, const void* aux, void* out, int ldo, int M, int N, int K,
                         int epilogue, float drop_p, unsigned int drop_seed, void* stream);
-
-/* norm1 fused into attn.qkv (model.py:163 + :115): out bf16 [M][N] = LayerNorm(x) Wt^T + bias; x fp32 [M][192]. */
-int tup_ln_gemm_fwd(const float* x, const float* gamma, const float* beta, const void* Wt,
-                    const float* bias, void* out, int M, int N, void* stream);
-
-/* Inference fusion of the MLP half of a block: x += mlp.2(GELU(mlp.0(norm2(x)))) (model.py:144-151,168-171);
- * the [M][768] hidden tensor stays in registers.  x fp32 [M][192] in place; w1 bf16 [768][192] = mlp.0.weight / 4 (rows
- * permuted per 64-group AND columns in the kernel's K order) and b1 = mlp.0.bias / 4 (packing.pack_fc1_fused_q: exact powers of
- * two), w2 FP16 [192][768] = 4 mlp.2.weight (rows permuted per 64-group, packing.pack_fc2_h4): erf-GELU (nn.GELU(), model.py:148)
- * is evaluated in packed fp16 on x / 4 and FC2 runs on the fp16 MFMA, the factors of 4 cancel. */
-int tup_fused_mlp_fwd(float* x, const float* gamma, const float* beta, const void* w1, const float* b1,
-                      const void* w2, const float* b2, int M, void* stream);
 
 /* reflect pad + patch_embed Conv2d(64,192,k8,s8) + NHWC permute + zero token pad +
  * window_partition: model.py:256-261,268-285.  feat bf16 NHWC; Wt bf16 [192][4096],
@@ -491,26 +475,6 @@ int tup_window_attn_bwd_h(const void* qkv, const void* gout, const void* att, co
 int tup_relpos_bias_reduce_h(const float* dbias_n, float* dtable, int heads, void* stream);
 int tup_wt_patch_wgrad(const float* P, const void* map, float* out, int B, int H, int W, int NI, void* stream);
 
-/* Inference fusion of norm1 + attn.qkv + the WindowAttention core (models/FastTransformer/model.py:104-130,163): the qkv
- * tensor never exists.  x fp32 [64*nwin][192] (window layout); wh bf16 [12][64][192] = per head the q, k, v weight rows
- * (16 each, natural channel order) + 16 zero rows; bh fp32 [12][48]; bias_frag from tup_relpos_bias_expand;
- * out bf16 [64*nwin][192] (the input of attn.proj). */
-int tup_fused_qkv_attn_fwd(const float* x, const float* gamma, const float* beta, const void* wh, const float* bh,
-                           const float* bias_frag, void* out, int nwin, void* stream);
-
-/* ... and with attn.proj + the residual add as well (the attention half of a block, model.py:163-164), x updated in place.
- * wproj bf16 [192][192] from packing.pack_proj_pairs (rows permuted per 64-group, columns in head-pair K order). */
-int tup_fused_attn_block_fwd(float* x, const float* gamma, const float* beta, const void* wh, const float* bh,
-                             const float* bias_frag, const void* wproj, const float* bproj, int nwin, void* stream);
-
-/* One whole WindowTransformerBlock in place (model.py:153-172): x += proj(attention(qkv(norm1(x)))) followed by
- * x += mlp.2(GELU(mlp.0(norm2(x)))) in ONE kernel: the residual stream of a 128-token tile stays in registers between
- * the two halves.  norm1 / norm2's scale and shift arrive folded into attn.qkv / mlp.0 (packing.fold_layernorm: W diag(gamma),
- * b + W beta): wh / bh = pack_qkv_heads of the folded qkv, w1 / b1 = pack_fc1_fused_q of the folded mlp.0 (x 1/4), w2 = 4 mlp.2.weight
- * in fp16 (pack_fc2_h4); bias_frag, wproj, bproj as in tup_fused_attn_block_fwd. */
-int tup_fused_block_fwd(float* x, const void* wh, const float* bh, const float* bias_frag, const void* wproj, const float* bproj,
-                        const void* w1, const float* b1, const void* w2, const float* b2, int nwin, void* stream);
-
 /* Branch A in TRAINING through its exact composition (r = 2): replaces autograd through `self.up1(feat)` + `self.up1_conv(...)`,
  * model.py:264-265 (Upsampler utils.py:62-63 + BasicConv utils.py:32-40; no non-linearity between the two convs, utils.py:50).
  * compose: wu fp32 [256][64][3][3], bu fp32 [256], w3 fp32 [3][64][3][3] -> the composed 5x5 conv's weights in every layout the
@@ -573,11 +537,18 @@ int tup_quality_loss_reduce(const double* qpartial, const float* l1partial, floa
 int tup_quality_loss_f32_bwd(const float* x, const float* y, const float* gscalar, float* grad, int B, int H, int W,
                              float w_l1, float w_mse, float w_ssim, float data_range, void* stream);
 
-/* nblk (<= 8) consecutive WindowTransformerBlocks in ONE launch (the loop `for block in self.window_blocks`, model.py:288-289), with
- * the default kernel's geometry (two waves per window, two workgroups per CU): between blocks the residual stream passes through
- * memory as each wave's own stores followed by its own loads (L2), so the launch boundaries and their chip-wide load / store bursts
- * disappear.  x fp32 [64*nwin][192] in place; table: HOST array [nblk][9] of device pointers, per block the arguments of
- * tup_fused_block_fwd after x in that order and packing. */
+/* nblk (<= 8) consecutive WindowTransformerBlocks in ONE launch (the loop `for block in self.window_blocks`, model.py:288-289; a block,
+ * model.py:153-172, is x += proj(attention(qkv(norm1(x)))) followed by x += mlp.2(GELU(mlp.0(norm2(x))))), two waves per window (one
+ * window per workgroup at <= 512 windows), two workgroups per CU.  The residual stream of a token tile stays in registers through a block;
+ * between blocks it passes through memory as each wave's own stores followed by its own loads (L2), so the launch boundaries and their
+ * chip-wide load / store bursts disappear.  x fp32 [64*nwin][192] (window layout) in place; table: HOST array [nblk][9] of device
+ * pointers, per block (wh, bh, bias_frag, wproj, bproj, w1, b1, w2, b2).  norm1 / norm2's scale and shift arrive folded into attn.qkv /
+ * mlp.0 (packing.fold_layernorm: W diag(gamma), b + W beta): wh bf16 [12][64][192] / bh fp32 [12][48] = pack_qkv_heads of the folded qkv
+ * (per head the q, k, v weight rows, 16 each, + 16 zero rows); bias_frag from tup_relpos_bias_expand; wproj bf16 [192][192] from
+ * packing.pack_proj_pairs (rows permuted per 64-group, columns in head-pair K order); w1 bf16 [768][192] / b1 = pack_fc1_fused_q of the
+ * folded mlp.0 (x 1/4, exact powers of two; rows permuted per 64-group AND columns in the kernel's K order); w2 FP16 [192][768] =
+ * 4 mlp.2.weight (pack_fc2_h4): erf-GELU (nn.GELU(), model.py:148) is evaluated in packed fp16 on x / 4 and FC2 runs on the fp16 MFMA,
+ * the factors of 4 cancel. */
 int tup_fused_blocks32_fwd(float* x, const void* const* table, int nblk, int nwin, void* stream);
 
 /* The same loop (model.py:288-289; blocks :153-172) as the streamed 32x32x16-MFMA kernel (csrc/block_stream.hip): one workgroup of

@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNELS_BY_MODE = {
     "infer": {
         "stream_block": ("blocks_stream_kernel", "block_stream.hip"),
-        "fused_block": ("fused_qkv_attn_kernel<true, true", "fused_attn.hip"),
+        "fused_block": ("fused_qkv_attn_kernel<false, ", "fused_attn.hip"),
         "conv64": ("conv_c64_persistent_kernel<4, 0, 3>", "conv3x3_c64.hip"),
         "branch_a_5x5": ("bra_rows_persistent_kernel", "conv3x3_c64.hip"),
         "patch_embed": ("patch_embed_kernel<3, 2, 3>", "gemm_tokens.hip"),
@@ -35,7 +35,6 @@ KERNELS_BY_MODE = {
         "patch_wgrad_wide": ("gemm_wgrad_wide_kernel<4, 2, true, 8>", "gemm_wgrad.hip"),
         "window_attn_bwd": ("window_attn_bwd_kernel<12>", "attention_bwd.hip"),
         "window_attn_fwd": ("window_attn_kernel<12", "attention.hip"),
-        "fused_mlp": ("fused_mlp_v2_kernel", "fused_blocks.hip"),
     },
     "rt": {      # ResidualTransformer 6x training step (configs[4] per rank)
         "rt_attn_fwd": ("rt_attention_kernel<true>", "rt_kernels.hip"),

@@ -8,7 +8,7 @@ order, an addressing error changes some output by at least 1, and a bf16 output 
 (common.h's pack_bf16x2).  Unlike the conv cases, the bf16 outputs here are MEANT to exceed 256 (K >= 64 products of variance
 ~ 21**2): test_gemm_exact_cpu.py asserts that between 5 % and 95 % of them do, so the rounding really happens.
 
-The GELU epilogues and ops.ln_gemm are not exact and stay in the tolerance tests of tests/test_hip_kernels.py."""
+The GELU epilogues are not exact and stay in the tolerance tests of tests/test_hip_kernels.py."""
 import torch
 import torch.nn.functional as F
 

@@ -24,6 +24,10 @@ def test_library_exports_every_declared_symbol():
     assert lib.tup_abi_version() == _lib.ABI_VERSION
     for name in declared:
         assert hasattr(lib, name)
+    # ABI 16 removed seven entries (the block kernel's half forms and their helpers); none may linger anywhere
+    for name in ("tup_fused_qkv_attn_fwd", "tup_fused_attn_block_fwd", "tup_fused_block_fwd", "tup_fused_mlp_fwd", "tup_ln_gemm_fwd",
+                 "tup_tail_stream_weight_source", "tup_debug_mlp_stamps"):
+        assert name not in hdr and name not in _lib.SIGNATURES and not hasattr(lib, name), name
 
 
 def test_plugin_surface_matches_reference_contract():
@@ -309,6 +313,49 @@ def test_tail_routing_respects_the_streaming_tails_offset_limits(monkeypatch):
     fits = ops.tail_stream_fits(big.shape[0], big.shape[2], big.shape[3], None)
     (ops.tail_stream_r2 if fits else ops.tail_fused)(big)
     assert calls == ["tiled"]
+
+
+def test_transformer_blocks_has_three_routes(monkeypatch):
+    """engine.transformer_blocks, with the kernels replaced by recorders (no GPU): the streamed kernel from STREAM_MIN_WINDOWS
+    windows on, the 16x16x32 whole-block kernel in one launch below that (and everywhere with stream_blocks off), one kernel per
+    op (blocks_train.blocks_infer) when intermediates are captured or fuse_blocks is off.  The module attributes that bench.py, the
+    smoke run and the GPU tests read or set stay."""
+    import collections
+    from transformerupscaler_amd import engine, ops
+    from transformerupscaler_amd.weights import BLOCKS
+    assert engine.blocks_in_one_launch is True and engine.stream_blocks is True and engine.STREAM_MIN_WINDOWS == 512
+    assert engine.stream_bf16_tokens is True and engine.fuse_blocks is True
+    assert not hasattr(engine, "fuse_attention")
+    calls = []
+    monkeypatch.setattr(ops, "stream_table", lambda blocks: ("stream table", len(blocks)))
+    monkeypatch.setattr(ops, "block_table", lambda blocks: ("block table", len(blocks)))
+    monkeypatch.setattr(ops, "blocks_stream", lambda x, table, out_bf16=False: calls.append(("stream", table, out_bf16)) or x)
+    monkeypatch.setattr(ops, "fused_blocks32", lambda x, table: calls.append(("one launch", table)) or x)
+    monkeypatch.setattr(engine, "blocks_infer", lambda pk, x, keys, attn, nblocks=None, capture=None:
+                        calls.append(("per op", keys, nblocks, capture)) or x)
+    pk = collections.defaultdict(lambda: None)
+    frags = [None] * BLOCKS
+
+    def route(nwin, capture=None, **switches):
+        for k, v in switches.items():
+            monkeypatch.setattr(engine, k, v)
+        del calls[:]
+        x = torch.empty((nwin * 64, 192), device="meta")
+        assert engine.transformer_blocks(pk, x, frags, capture, bf16_out=capture is None) is x
+        for k in switches:
+            monkeypatch.setattr(engine, k, True)
+        assert len(calls) == 1
+        return calls[0]
+
+    assert route(512) == ("stream", ("stream table", BLOCKS), True)
+    assert route(511) == ("one launch", ("block table", BLOCKS))
+    assert route(512, stream_blocks=False) == ("one launch", ("block table", BLOCKS))
+    assert route(512, stream_bf16_tokens=False) == ("stream", ("stream table", BLOCKS), False)
+    for nwin in (511, 512):
+        cap = {}
+        got = route(nwin, capture=cap)
+        assert got[:3] == ("per op", ("qkv", "proj"), BLOCKS) and got[3] is cap
+        assert route(nwin, fuse_blocks=False) == ("per op", ("qkv", "proj"), BLOCKS, None)
 
 
 def test_rt_attention_dropout_on_an_unsupported_token_count_raises_a_clear_error():

@@ -26,7 +26,7 @@ def test_det_entries_are_declared_bound_and_exported():
         assert hasattr(lib, name), name
     assert re.search(r"\blong long\s+tup_conv_wgrad_slab\s*\(", hdr)
     assert "tup_conv_wgrad_slab" in _lib.COUNT_RETURNING
-    assert lib.tup_abi_version() == 15 == _lib.ABI_VERSION
+    assert lib.tup_abi_version() == 16 == _lib.ABI_VERSION
 
 
 @pytest.mark.parametrize("B,H,W", SHAPES)

@@ -44,7 +44,7 @@ def test_det_step_entries_are_declared_bound_and_exported():
     for det, twin in TWINS.items():
         a, b = _lib.SIGNATURES[det], _lib.SIGNATURES[twin]
         assert a[:-2] == b[:-1] and a[-2:] == [_lib.P, _lib.P], (det, twin)
-    assert lib.tup_abi_version() == 15 == _lib.ABI_VERSION
+    assert lib.tup_abi_version() == 16 == _lib.ABI_VERSION
 
 
 @pytest.mark.parametrize("kind,M,NI,NJ", REQUESTS)

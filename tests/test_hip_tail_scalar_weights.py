@@ -25,7 +25,7 @@ import torch
 import torch.nn.functional as F
 
 import _exact_ref as R          # tests/ is on sys.path (rootdir-less test modules)
-from transformerupscaler_amd import _lib, ops, packing
+from transformerupscaler_amd import ops, packing
 
 pytestmark = pytest.mark.gpu
 
@@ -169,14 +169,6 @@ def test_scalar_weight_arm_vs_float64_torch():
     assert got.shape == ref.shape
     err = (got.cpu().double() - ref).abs().max().item()
     assert err <= 2e-5, err
-
-
-def test_weight_source_entry_accepts_only_zero():
-    """tup_tail_stream_weight_source remains for ABI 15 only: the LDS arm it used to select is gone."""
-    assert _lib.load().tup_tail_stream_weight_source(0) == 0
-    for source in (1, 2):
-        with pytest.raises(RuntimeError):
-            _lib.call("tup_tail_stream_weight_source", source)
 
 
 def test_scalar_weight_arm_refuses_misaligned_weight_pointers():

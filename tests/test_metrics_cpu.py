@@ -93,8 +93,8 @@ def test_quality_entries_in_header_and_signatures():
         assert m, name
         assert len(m.group(1).split(",")) == nargs, name
         assert len(_lib.SIGNATURES[name]) == nargs, name
-    assert _lib.ABI_VERSION == 15
-    assert _lib.load().tup_abi_version() == 15
+    assert _lib.ABI_VERSION == 16
+    assert _lib.load().tup_abi_version() == 16
 
 
 def test_metrics_options_and_cpu_tensors_raise():

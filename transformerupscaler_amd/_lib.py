@@ -11,7 +11,7 @@ from ctypes import c_double, c_float, c_int, c_longlong, c_uint, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TUP_LIB_PATH") or os.path.join(_HERE, "libtupscale_hip.so")      # override: A/B of two builds
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 P = c_void_p
 I = c_int
@@ -35,14 +35,11 @@ SIGNATURES = {
     "tup_tail_stream_r2_resize_fwd": [P] * 7 + [P, P, P, I, P, P, P, I, P, P] + [I] * 9 + [P],
     "tup_tail_stream_r2_parts_fwd": [P, P, P, P, I] + [P] * 6 + [I, I, I, I, P],
     "tup_tail_stream_r2_resize_parts_fwd": [P, P, P, P, I] + [P] * 6 + [P, P, P, I, P, P, P, I, P, P] + [I] * 9 + [P],
-    "tup_tail_stream_weight_source": [I],
     "tup_clamp01_fwd": [P, P, c_longlong, P],
     "tup_layernorm_fwd": [P, P, P, P, P, P, I, P],
     "tup_relpos_bias_expand": [P, P, P],
     "tup_window_attn_fwd": [P, P, P, P, I, F, U, P],
     "tup_gemm_tokens_fwd": [P, I, I, P, P, P, P, P, I, I, I, I, I, F, U, P],
-    "tup_ln_gemm_fwd": [P, P, P, P, P, P, I, I, P],
-    "tup_fused_mlp_fwd": [P, P, P, P, P, P, P, I, P],
     "tup_patch_embed_fwd": [P, P, P, P, I, I, I, P],
     "tup_patch_unembed_fwd": [P, I, P, P, P, P, I, I, I, P],
     # ResidualTransformer
@@ -64,9 +61,6 @@ SIGNATURES = {
     "tup_window_attn_fwd_h": [P, P, P, P, I, I, F, U, P],
     "tup_wt_patch_embed_fwd": [P, P, P, P, I, I, I, I, P],
     "tup_wt_patch_unembed_fwd": [P, P, P, P, P, I, I, I, I, P],
-    "tup_fused_qkv_attn_fwd": [P, P, P, P, P, P, P, I, P],
-    "tup_fused_attn_block_fwd": [P, P, P, P, P, P, P, P, I, P],
-    "tup_fused_block_fwd": [P] * 10 + [I, P],
     "tup_fused_blocks32_fwd": [P, P, I, I, P],
     "tup_blocks_stream_fwd": [P, P, P, I, I, P],
     "tup_clock_probe": [P, P],

@@ -144,11 +144,13 @@ def blocks_backward(spec: BlockSpec, pk, blocks, g, ready, g_x, drop_p, seed):
     return g_x
 
 
-def blocks_infer(pk, xw, keys, attn):
-    """The dropout-free, nothing-saved form of blocks_forward for the two 128-wide models: xw is updated in place.
-    attn: (i, qkv) -> att."""
+def blocks_infer(pk, xw, keys, attn, nblocks=None, capture=None):
+    """The dropout-free, nothing-saved form of blocks_forward, one kernel per op: xw is updated in place.  The inference route of the
+    two 128-wide models, and FastTransformer's when engine.fuse_blocks is off or intermediates are captured.
+    attn: (i, qkv) -> att.  nblocks: the block count where pk carries no "nblocks".  capture: a dict that receives, per block,
+    block{i} (a copy of xw after the block), block{i}_qkv and block{i}_attn_out."""
     k_in, k_out = keys
-    for i in range(pk["nblocks"]):
+    for i in range(pk["nblocks"] if nblocks is None else nblocks):
         b = f"b{i}."
         y = ops.layernorm(xw, pk[b + "norm1.w"], pk[b + "norm1.b"])
         qkv = ops.gemm_tokens(y, pk[b + k_in + ".w"], pk[b + k_in + ".b"], "bf16")
@@ -157,6 +159,10 @@ def blocks_infer(pk, xw, keys, attn):
         y = ops.layernorm(xw, pk[b + "norm2.w"], pk[b + "norm2.b"])
         hid = ops.gemm_tokens(y, pk[b + "fc1.w"], pk[b + "fc1.b"], "gelu")
         ops.gemm_tokens(hid, pk[b + "fc2.w"], pk[b + "fc2.b"], "res", res=xw, out=xw)
+        if capture is not None:
+            capture[f"block{i}"] = xw.clone()
+            capture[f"block{i}_qkv"] = qkv
+            capture[f"block{i}_attn_out"] = att
     return xw
 
 

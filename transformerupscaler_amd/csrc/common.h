@@ -154,7 +154,7 @@ TUP_DEVICE void gelu_erf2_batch(f32x2 (&x)[N]) {
     for (int i = 0; i < N; ++i) x[i] = x[i] * (xc[i] * q[i] + 0.5f);
 }
 
-// ---- GELU in packed fp16, for the fused inference MLPs (fused_attn.hip, fused_blocks.hip) ----
+// ---- GELU in packed fp16, for the fused inference MLPs (fused_attn.hip, block_stream.hip) ----
 // mlp.0's weight and bias reach those kernels scaled by 1/4 (exact in bf16 / fp32: packing.pack_fc1_fused_q), so FC1's accumulators
 // hold x' = x / 4.  gelu(x) / 4 = x' (0.5 + xc R(xc^2 - 0.5)), xc = clamp(x', +-1) [i.e. x clamped at +-4], R of degree 6 fitted to
 // (Phi(4 x') - 0.5) / x' with weight x^2 and the clamped tail pinned (C R(C^2 - 0.5) = 0.5); the hidden tile stays fp16 and FC2 runs

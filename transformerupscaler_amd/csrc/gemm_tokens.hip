@@ -17,7 +17,7 @@
 
 namespace {
 
-enum { A_BF16 = 0, A_F32 = 1, A_PATCH = 2, A_LN = 3 };
+enum { A_BF16 = 0, A_F32 = 1, A_PATCH = 2 };
 enum { E_BF16 = 0, E_GELU_BF16 = 1, E_RES_F32 = 2, E_PATCH_EMBED = 3, E_UNEMBED = 4, E_GELU_BWD = 5, E_UNEMBED_MERGE = 6 };
 
 struct GemmParams {
@@ -31,7 +31,6 @@ struct GemmParams {
     float* skip_colsum;                               // E_UNEMBED_MERGE: optional fp32 [16][64] += per-channel sums of `skip` (16 replicas, spread by workgroup)
     int reflect;                 // A_PATCH: 1 = reflect-pad beyond the map, 0 = zeros
     uint32_t drop_thresh, drop_seed; float drop_inv_keep;      // E_RES_F32: dropout on (acc + bias) before "+ res"
-    const float* ln_gamma; const float* ln_beta;               // panel kernel, A_LN: LayerNorm fused into the A load
     int linear_tokens;            // patch modes: token rows are a plain [B][Ht][Wt] grid (ResidualTransformer), not windows
     const float* pos;             // E_PATCH_EMBED with linear tokens: + pos_embed[token][n]
     int M, N, K;
@@ -412,11 +411,11 @@ __global__ __launch_bounds__(256, 2) void gemm_tokens_kernel(const GemmParams p)
 
 // ------------------------------------------------------------------------------------------------
 // A-resident "panel" kernel for K = 192 (every Linear that reads the 192-wide token stream, and patch_unembed): one workgroup =
-// 128 token rows, loaded ONCE -- optionally through a fused LayerNorm (A_LN) -- and kept while the workgroup walks all N/64 weight
+// 128 token rows, loaded ONCE and kept while the workgroup walks all N/64 weight
 // tiles.  The K-streaming kernel above pays a global-load round trip per 16 MFMAs at K = 192 (3 iterations per output tile) and
 // was latency-bound; here it is paid once per 128 rows.
 // The token operand never touches LDS: each lane loads its 32 rows directly in MFMA B-fragment order (token 16tg+pl, channels
-// 32*step + 8g .. +8; A_LN: statistics by two cross-lane-group shuffles) and keeps the 12 bf16x8 fragments in registers for all
+// 32*step + 8g .. +8) and keeps the 12 bf16x8 fragments in registers for all
 // weight tiles.  LDS holds only the weight stream: two 24 KB buffers filled by LDS-DMA one tile ahead, ONE workgroup barrier per
 // tile.  K loop: weight fragments two K-steps ahead, immediate-offset reads.  Epilogue operands are requested before the K loop
 // (epi_prefetch).  48 KB of LDS, <= 256 VGPRs: two 4-wave workgroups per CU.
@@ -459,47 +458,18 @@ __global__ __launch_bounds__(256, 2) void gemm_panel2_kernel(const GemmParams p)
         } else {
             const float* xr = (const float*)p.A + (size_t)m * p.lda + 8 * g;
             f32x4 v[6][2];
-            float sum = 0.f;
 #pragma unroll
             for (int st = 0; st < 6; ++st) {
                 v[st][0] = *reinterpret_cast<const f32x4*>(xr + 32 * st);
                 v[st][1] = *reinterpret_cast<const f32x4*>(xr + 32 * st + 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sum += v[st][0][e] + v[st][1][e];
-            }
-            float mean = 0.f, rstd = 1.f;
-            if constexpr (AMODE == A_LN) {
-                sum += __shfl_xor(sum, 16);
-                sum += __shfl_xor(sum, 32);
-                mean = sum * (1.0f / PK);
-                float ss = 0.f;
-#pragma unroll
-                for (int st = 0; st < 6; ++st)
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { const float d = v[st][h][e] - mean; ss += d * d; }
-                ss += __shfl_xor(ss, 16);
-                ss += __shfl_xor(ss, 32);
-                rstd = rsqrtf(ss * (1.0f / PK) + 1e-5f);
             }
 #pragma unroll
             for (int st = 0; st < 6; ++st) {
                 uint32_t pk[4];
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    float o4[4];
-                    if constexpr (AMODE == A_LN) {
-                        const f32x4 gm = *reinterpret_cast<const f32x4*>(p.ln_gamma + 32 * st + 8 * g + 4 * h);
-                        const f32x4 bt = *reinterpret_cast<const f32x4*>(p.ln_beta + 32 * st + 8 * g + 4 * h);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) o4[e] = (v[st][h][e] - mean) * rstd * gm[e] + bt[e];
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) o4[e] = v[st][h][e];
-                    }
-                    pk[2 * h] = pack_bf16x2(o4[0], o4[1]);
-                    pk[2 * h + 1] = pack_bf16x2(o4[2], o4[3]);
+                    pk[2 * h] = pack_bf16x2(v[st][h][0], v[st][h][1]);
+                    pk[2 * h + 1] = pack_bf16x2(v[st][h][2], v[st][h][3]);
                 }
                 tf[tg][st] = __builtin_bit_cast(bf16x8, u32x4{pk[0], pk[1], pk[2], pk[3]});
             }
@@ -1026,17 +996,6 @@ extern "C" int tup_patch_unembed_fwd(const void* x, int x_bf16, const void* Wt, 
     p.N = 4096; p.K = 192;
     if (x_bf16) return launch_panel<A_BF16, E_UNEMBED>(p, reinterpret_cast<hipStream_t>(stream));
     return launch_panel<A_F32, E_UNEMBED>(p, reinterpret_cast<hipStream_t>(stream));
-}
-
-// LayerNorm fused into a Linear (norm1 -> attn.qkv, model.py:163 + :115): out bf16 [M][N] = LN(x) Wt^T + bias.
-// x fp32 [M][192]; Wt bf16 [N][192] (rows permuted per 64-group).
-extern "C" int tup_ln_gemm_fwd(const float* x, const float* gamma, const float* beta, const void* Wt,
-                               const float* bias, void* out, int M, int N, void* stream)
-{
-    GemmParams p{};
-    p.A = x; p.lda = 192; p.Wt = (const bf16_t*)Wt; p.bias = bias; p.out = out; p.ldo = N;
-    p.M = M; p.N = N; p.K = 192; p.ln_gamma = gamma; p.ln_beta = beta;
-    return launch_panel<A_LN, E_BF16>(p, reinterpret_cast<hipStream_t>(stream));
 }
 
 // Backward of patch_unembed w.r.t. its input tokens (model.py:292-305 under autograd): gather the 8x8

@@ -607,10 +607,3 @@ extern "C" int tup_tail_stream_r2_resize_parts_fwd(const float* part, const floa
     return tail_stream_resize(nullptr, &parts, wfu_t, bfu, wfc_t, bfc, ui, out, ymin, ysize, yw, KY, xmin, xsize, xw, KX, oxb, oyb,
                               B, H, W, Ho, Wo, sc, band_h, ext, clamp01, stream);
 }
-
-// Kept for ABI 15 only.  It used to choose between the weights as scalar operands (0) and an LDS image of them read through a ring of
-// vector registers (1); the LDS arm is gone, so 0 is a no-op and every other value is refused.
-extern "C" int tup_tail_stream_weight_source(int source)
-{
-    return source == 0 ? 0 : (int)hipErrorInvalidValue;
-}

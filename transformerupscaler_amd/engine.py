@@ -15,14 +15,12 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import ops
+from .blocks_train import blocks_infer
 from .weights import BLOCKS, VALID_SCALES, upsampler_layout
 
 
 # Optional per-stage timing hook (bench.py installs one): callable(name) -> context manager.
 stage_timer = None
-# inference fusion level of the attention half: 2 = norm1 + qkv + attention + proj + residual in one kernel,
-# 1 = norm1 + qkv + attention (proj separate), 0 = separate kernels
-fuse_attention = 3      # A/B attribute (tests set 0 .. 3; no environment switch)
 
 
 _NO_TIMER = contextlib.nullcontext()
@@ -48,15 +46,16 @@ def resolve_scale(h: int, w: int, res_out, upscale_factor: Optional[int]):
     return (int(res_out[0]), int(res_out[1])), int(upscale_factor)
 
 
-blocks_in_one_launch = True     # inference (A/B attribute): the six whole-block kernels as one launch
-# inference: the one launch is the streamed 32x32x16 kernel (csrc/block_stream.hip); False = round 3's 16x16x32 kernel (A/B attribute)
+blocks_in_one_launch = True     # constant: both block kernels run the six blocks as one launch; bench.py reads it for its launch count
+# inference (A/B attribute): large launches take the streamed 32x32x16 kernel (csrc/block_stream.hip); False = the 16x16x32 whole-block
+# kernel (csrc/fused_attn.hip) at every size
 stream_blocks = True
 # the streamed kernel's workgroup carries four windows (one workgroup per CU): launches that would leave most CUs without one stay on the
 # 16x16x32 kernel, whose small-launch form runs one window per workgroup (the 720p -> 4K overlay frame: 240 windows; config 4: 540)
 STREAM_MIN_WINDOWS = 512
 # the streamed kernel hands its result to patch_unembed as bf16 tokens (the rounding that GEMM applies on load anyway; A/B attribute)
 stream_bf16_tokens = True
-fuse_blocks = True      # inference: fused MLP half (csrc/fused_blocks.hip); False = one kernel per op
+fuse_blocks = True      # inference: the six blocks in one launch of a whole-block kernel; False = one kernel per op (blocks_infer)
 fuse_tail = True        # inference: fused output tail (csrc/tail_fused.hip)
 stream_tail = True     # A/B attribute; last stage x2: the register-streaming tail (csrc/tail_stream.hip) [+ separable Resize]
 # inference (A/B attribute): decoder_conv1 + decoder_conv2 as one conv with decoder_conv2 in its epilogue plus a finishing launch
@@ -78,54 +77,18 @@ def _block_operands(pk, i, bias_frags):
 
 
 def transformer_blocks(pk: Dict[str, torch.Tensor], x: torch.Tensor, bias_frags, capture=None, bf16_out: bool = False):
-    """x: fp32 [M][192] window layout, updated in place.  model.py:153-172 x6.
+    """x: fp32 [M][192] window layout, updated in place.  model.py:153-172 x6.  Three routes: the streamed kernel for large launches,
+    the 16x16x32 whole-block kernel below that, one kernel per op when fuse_blocks is off or `capture` wants the intermediates.
     bf16_out (the caller feeds the result to patch_unembed, whose GEMM rounds its operand to bf16 anyway): the streamed kernel then
     returns the tokens as a bf16 tensor (the same rounding, half the bytes to write and to read back); every other route ignores it."""
-    if (fuse_blocks and fuse_attention >= 3 and capture is None and "b0.stream.0" in pk and blocks_in_one_launch and stream_blocks
-            and x.shape[0] // 64 >= STREAM_MIN_WINDOWS):
+    if not fuse_blocks or capture is not None:
+        return blocks_infer(pk, x, ("qkv", "proj"), lambda i, qkv: ops.window_attn(qkv, bias_frags[i]), nblocks=BLOCKS, capture=capture)
+    if stream_blocks and x.shape[0] // 64 >= STREAM_MIN_WINDOWS:
         # all six blocks in ONE launch of the streamed kernel (csrc/block_stream.hip)
         table = ops.stream_table([tuple(pk[f"b{i}.stream.{j}"] for j in range(7)) for i in range(BLOCKS)])
         return ops.blocks_stream(x, table, out_bf16=bf16_out and stream_bf16_tokens)
-    if fuse_blocks and fuse_attention >= 3 and capture is None and "b0.proj.wpp" in pk and blocks_in_one_launch:
-        # all six blocks in ONE launch (csrc/fused_attn.hip)
-        table = ops.block_table([_block_operands(pk, i, bias_frags) for i in range(BLOCKS)])
-        return ops.fused_blocks32(x, table)
-    for i in range(BLOCKS):
-        qkv = None
-        if fuse_blocks and fuse_attention >= 3 and capture is None and f"b{i}.proj.wpp" in pk:
-            # the whole block in one kernel: the residual stream of a token tile stays in registers between the halves
-            ops.fused_block(x, *_block_operands(pk, i, bias_frags))
-            continue
-        if fuse_blocks and fuse_attention == 2 and capture is None and f"b{i}.proj.wpp" in pk:
-            # the whole attention half in one kernel, in place: neither the qkv nor the attention-output tensor exists
-            ops.fused_attn_block(x, pk[f"b{i}.norm1.w"], pk[f"b{i}.norm1.b"], pk[f"b{i}.qkv.wh"], pk[f"b{i}.qkv.bh"], bias_frags[i],
-                                 pk[f"b{i}.proj.wpp"], pk[f"b{i}.proj.b"])
-            ops.fused_mlp(x, pk[f"b{i}.norm2.w"], pk[f"b{i}.norm2.b"], pk[f"b{i}.fc1.wfq"], pk[f"b{i}.fc1.bq"],
-                          pk[f"b{i}.fc2.wh4"], pk[f"b{i}.fc2.b"])
-            continue
-        if fuse_blocks and fuse_attention and capture is None and f"b{i}.qkv.wh" in pk:
-            # norm1 + qkv + attention core in one kernel (the qkv tensor never exists)
-            att = ops.fused_qkv_attn(x, pk[f"b{i}.norm1.w"], pk[f"b{i}.norm1.b"], pk[f"b{i}.qkv.wh"], pk[f"b{i}.qkv.bh"], bias_frags[i])
-        else:
-            if fuse_blocks:
-                qkv = ops.ln_gemm(x, pk[f"b{i}.norm1.w"], pk[f"b{i}.norm1.b"], pk[f"b{i}.qkv.w"], pk[f"b{i}.qkv.b"])
-            else:
-                y = ops.layernorm(x, pk[f"b{i}.norm1.w"], pk[f"b{i}.norm1.b"])
-                qkv = ops.gemm_tokens(y, pk[f"b{i}.qkv.w"], pk[f"b{i}.qkv.b"], "bf16")
-            att = ops.window_attn(qkv, bias_frags[i])
-        ops.gemm_tokens(att, pk[f"b{i}.proj.w"], pk[f"b{i}.proj.b"], "res", res=x, out=x)
-        if fuse_blocks and f"b{i}.fc1.wfq" in pk:
-            ops.fused_mlp(x, pk[f"b{i}.norm2.w"], pk[f"b{i}.norm2.b"], pk[f"b{i}.fc1.wfq"], pk[f"b{i}.fc1.bq"],
-                          pk[f"b{i}.fc2.wh4"], pk[f"b{i}.fc2.b"])
-        else:
-            y = ops.layernorm(x, pk[f"b{i}.norm2.w"], pk[f"b{i}.norm2.b"])
-            hid = ops.gemm_tokens(y, pk[f"b{i}.fc1.w"], pk[f"b{i}.fc1.b"], "gelu")
-            ops.gemm_tokens(hid, pk[f"b{i}.fc2.w"], pk[f"b{i}.fc2.b"], "res", res=x, out=x)
-        if capture is not None:
-            capture[f"block{i}"] = x.clone()
-            capture[f"block{i}_qkv"] = qkv
-            capture[f"block{i}_attn_out"] = att
-    return x
+    # all six blocks in ONE launch (csrc/fused_attn.hip)
+    return ops.fused_blocks32(x, ops.block_table([_block_operands(pk, i, bias_frags) for i in range(BLOCKS)]))
 
 
 def forward(pk: Dict[str, torch.Tensor], bias_frags, x: torch.Tensor, scale: int, res_out: Tuple[int, int],

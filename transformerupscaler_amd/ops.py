@@ -420,37 +420,6 @@ def gemm_tokens(a, wt, bias, epilogue, res=None, out=None, aux=None, drop_p=0.0,
     return out
 
 
-def ln_gemm(x, gamma, beta, wt, bias):
-    """bf16 [M][N] = LayerNorm(x) @ wt^T + bias (LN fused into the GEMM's A load)."""
-    M = x.shape[0]
-    N = wt.shape[0]
-    out = torch.empty((M, N), dtype=BF16, device=x.device)
-    _lib.call("tup_ln_gemm_fwd", _chk(x, F32, (M, 192), "x"), _chk(gamma, F32, (192,), "gamma"), _chk(beta, F32, (192,), "beta"),
-              _chk(wt, BF16, (N, 192), "wt"), _chk(bias, F32, (N,), "bias"), out.data_ptr(), M, N, _stream())
-    return out
-
-
-def fused_qkv_attn(x, gamma, beta, wh, bh, bias_frag):
-    """bf16 [M][192] = attention core of qkv(LayerNorm(x)) per 8x8 window (inference fusion; the qkv tensor never exists)."""
-    M = x.shape[0]
-    assert M % 64 == 0
-    out = torch.empty((M, 192), dtype=BF16, device=x.device)
-    _lib.call("tup_fused_qkv_attn_fwd", _chk(x, F32, (M, 192), "x"), _chk(gamma, F32, (192,), "gamma"), _chk(beta, F32, (192,), "beta"),
-              _chk(wh, BF16, (12, 64, 192), "wh"), _chk(bh, F32, (12, 48), "bh"), _chk(bias_frag, F32, (12, 4, 4, 64, 4), "bias"),
-              out.data_ptr(), M // 64, _stream())
-    return out
-
-
-def fused_attn_block(x, gamma, beta, wh, bh, bias_frag, wproj, bproj):
-    """In place: x += proj(attention(qkv(LayerNorm(x)))) + b_proj (the attention half of a block, inference fusion)."""
-    M = x.shape[0]
-    assert M % 64 == 0
-    _lib.call("tup_fused_attn_block_fwd", _chk(x, F32, (M, 192), "x"), _chk(gamma, F32, (192,), "gamma"), _chk(beta, F32, (192,), "beta"),
-              _chk(wh, BF16, (12, 64, 192), "wh"), _chk(bh, F32, (12, 48), "bh"), _chk(bias_frag, F32, (12, 4, 4, 64, 4), "bias"),
-              _chk(wproj, BF16, (192, 192), "wproj"), _chk(bproj, F32, (192,), "bproj"), M // 64, _stream())
-    return x
-
-
 def _pointer_table(blocks, operands, what):
     """(ctypes array of the blocks' device pointers, number of blocks, the tensors -- kept alive by the caller holding the tuple)
     for the multi-block kernels.  operands: per tensor of a block (dtype, shape), or (dtype, element count) for a flat packed one."""
@@ -477,12 +446,18 @@ def block_table(blocks):
 
 
 def fused_blocks32(x, table):
-    """In place: the table's consecutive WindowTransformerBlocks in one launch, two waves per window (the default kernel)."""
+    """In place: the table's consecutive WindowTransformerBlocks (attention half + MLP half each) in one launch of the 16x16x32
+    whole-block kernel (csrc/fused_attn.hip): two waves per window, one window per workgroup at <= 512 windows."""
     M = x.shape[0]
     assert M % 64 == 0
     arr, nblk, _keep = table
     _lib.call("tup_fused_blocks32_fwd", _chk(x, F32, (M, 192), "x"), arr, nblk, M // 64, _stream())
     return x
+
+
+def fused_block(x, *row):
+    """In place: one whole WindowTransformerBlock, the one-block form of fused_blocks32 (`row` = one row of block_table)."""
+    return fused_blocks32(x, block_table([row]))
 
 
 def clock_probe():
@@ -510,29 +485,6 @@ def blocks_stream(x, table, out_bf16=False):
     out = torch.empty((M, 192), dtype=BF16, device=x.device) if out_bf16 else None
     _lib.call("tup_blocks_stream_fwd", _chk(x, F32, (M, 192), "x"), out.data_ptr() if out_bf16 else None, arr, nblk, M // 64, _stream())
     return out if out_bf16 else x
-
-
-def fused_block(x, wh, bh, bias_frag, wproj, bproj, w1, b1, w2, b2):
-    """In place: one whole WindowTransformerBlock (attention half + MLP half) in one kernel (inference fusion).  Operands as the
-    rows of block_table: LayerNorm scale / shift folded into wh / bh and w1 / b1 (packing.fold_layernorm)."""
-    M = x.shape[0]
-    assert M % 64 == 0
-    _lib.call("tup_fused_block_fwd", _chk(x, F32, (M, 192), "x"),
-              _chk(wh, BF16, (12, 64, 192), "wh"), _chk(bh, F32, (12, 48), "bh"), _chk(bias_frag, F32, (12, 4, 4, 64, 4), "bias"),
-              _chk(wproj, BF16, (192, 192), "wproj"), _chk(bproj, F32, (192,), "bproj"),
-              _chk(w1, BF16, (768, 192), "w1"), _chk(b1, F32, (768,), "b1"), _chk(w2, F16, (192, 768), "w2"), _chk(b2, F32, (192,), "b2"),
-              M // 64, _stream())
-    return x
-
-
-def fused_mlp(x, gamma, beta, w1, b1, w2, b2):
-    """In place: x += mlp.2(GELU(mlp.0(LayerNorm(x)))) (inference fusion; hidden tensor stays on chip).
-    w1 / b1 = mlp.0 scaled by 1/4 (packing.pack_fc1_fused_q), w2 = 4 mlp.2.weight in fp16 (packing.pack_fc2_h4)."""
-    M = x.shape[0]
-    _lib.call("tup_fused_mlp_fwd", _chk(x, F32, (M, 192), "x"), _chk(gamma, F32, (192,), "gamma"), _chk(beta, F32, (192,), "beta"),
-              _chk(w1, BF16, (768, 192), "w1"), _chk(b1, F32, (768,), "b1"), _chk(w2, F16, (192, 768), "w2"),
-              _chk(b2, F32, (192,), "b2"), M, _stream())
-    return x
 
 
 def window_geometry(H, W):

@@ -119,21 +119,21 @@ def pack_linear_stack(weights, transpose: bool = False):
 
 
 def pack_fc1_fused(weight: torch.Tensor):
-    """mlp.0 weight for tup_fused_mlp_fwd: pack_linear plus a column permutation.  K-step st of the kernel's FC1, lane
+    """mlp.0 weight for the whole-block kernel (tup_fused_blocks32_fwd): pack_linear plus a column permutation.  K-step st of the kernel's FC1, lane
     group g, element j contracts over channel 64*(st>>1) + 16g + 8*(st&1) + j -- the channels whose residual the same
     lane carries in its FC2 accumulators -- so packed column 32st + 8g + j holds that channel."""
     return pack_linear(weight).index_select(1, _fused_k_order(weight.device)).contiguous()
 
 
 def pack_fc1_fused_q(weight: torch.Tensor, bias: torch.Tensor):
-    """mlp.0 for the fused inference MLPs (tup_fused_mlp_fwd, tup_fused_block_fwd, tup_fused_blocks32_fwd): pack_fc1_fused of
+    """mlp.0 for the whole-block kernel's MLP half (tup_fused_blocks32_fwd; the weight with norm2 folded in): pack_fc1_fused of
     W1 / 4 and b1 / 4.  A power of two, so exact in bf16 / fp32: FC1's accumulators then hold x / 4, the range in which the GELU
     polynomial is evaluated in packed fp16 (csrc/common.h, gelu16_batch)."""
     return pack_fc1_fused(weight.detach() * 0.25), (bias.detach().float() * 0.25).contiguous()
 
 
 def pack_fc2_h4(weight: torch.Tensor):
-    """mlp.2 for the same kernels: 4 W2 in FP16 (rows permuted per 64-group as pack_linear): the hidden tile gelu(x) / 4 stays fp16
+    """mlp.2 for the same kernel: 4 W2 in FP16 (rows permuted per 64-group as pack_linear): the hidden tile gelu(x) / 4 stays fp16
     and FC2 runs on v_mfma_f32_16x16x32_f16; fp16 carries three more mantissa bits than the bf16 tile it replaces."""
     return perm_rows64(weight.detach() * 4.0).contiguous().to(torch.float16)
 
@@ -141,7 +141,7 @@ def pack_fc2_h4(weight: torch.Tensor):
 def fold_layernorm(weight: torch.Tensor, bias: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor):
     """Linear(LayerNorm(x)) with the LayerNorm's scale and shift moved into the Linear (model.py:163 norm1 -> attn.qkv, :168 norm2 ->
     mlp.0): W (xhat * gamma + beta) + b = (W diag(gamma)) xhat + (b + W beta), formed in fp32.  The whole-block kernels
-    (tup_fused_block_fwd, tup_fused_blocks32_fwd) then normalise with one FMA per value and never load gamma / beta."""
+    (tup_fused_blocks32_fwd, tup_blocks_stream_fwd) then normalise with one FMA per value and never load gamma / beta."""
     w = weight.detach().float()
     return w * gamma.detach().float()[None, :], bias.detach().float() + w @ beta.detach().float()
 
@@ -158,7 +158,7 @@ def _fused_k_order(device):
 
 def pack_qkv_heads(weight: torch.Tensor, bias: torch.Tensor, heads: int = 12, natural_k: bool = False):
     """attn.qkv Linear [3*dim][dim] -> per head the 16 q, 16 k, 16 v weight rows + 16 zero rows: bf16 [heads][64][dim], and the
-    matching biases fp32 [heads][48] (tup_fused_qkv_attn_fwd and the kernels built on it).  The K columns are in the order of
+    matching biases fp32 [heads][48] (tup_fused_blocks32_fwd, which takes the weight with norm1 folded in).  The K columns are in the order of
     pack_fc1_fused (LayerNorm1 reads the residual stream in the layout of the accumulators that produce it); natural_k=True
     keeps the channel order (dim = 192 only for the permuted form)."""
     dim = weight.shape[1]
@@ -172,7 +172,7 @@ def pack_qkv_heads(weight: torch.Tensor, bias: torch.Tensor, heads: int = 12, na
 
 
 def pack_proj_pairs(weight: torch.Tensor):
-    """attn.proj weight [dim][dim] for tup_fused_attn_block_fwd: rows permuted per 64-group (as pack_linear) and, inside every
+    """attn.proj weight [dim][dim] for tup_fused_blocks32_fwd: rows permuted per 64-group (as pack_linear) and, inside every
     32-column block (= two heads), columns reordered so that lane group g's eight K values are contiguous:
     new column 32p + 8g + j  <-  old 32p + 4g + j (j < 4, head 2p) | 32p + 16 + 4g + (j - 4) (j >= 4, head 2p + 1)."""
     dim = weight.shape[1]
@@ -425,13 +425,11 @@ def pack_state_dict(sd: Dict[str, torch.Tensor], scale: int, backward: bool = Fa
             wt = pack_linear_stack(ws, transpose=True)
             for i in range(BLOCKS):
                 pk[f"b{i}.{nm}.wd"] = wt[i]
-    if not backward:      # inference fusion of norm1 + qkv + attention
+    if not backward:      # inference: the operands of the two whole-block kernels
         for i in range(BLOCKS):
             p = f"window_blocks.{i}"
-            pk[f"b{i}.qkv.wh"], pk[f"b{i}.qkv.bh"] = pack_qkv_heads(sd[f"{p}.attn.qkv.weight"], sd[f"{p}.attn.qkv.bias"])
+            # the 16x16x32 kernel (csrc/fused_attn.hip): norm1 / norm2 folded into the Linear that follows them
             pk[f"b{i}.proj.wpp"] = pack_proj_pairs(sd[f"{p}.attn.proj.weight"])
-            pk[f"b{i}.fc1.wfq"], pk[f"b{i}.fc1.bq"] = pack_fc1_fused_q(sd[f"{p}.mlp.0.weight"], sd[f"{p}.mlp.0.bias"])
-            # the whole-block kernels: norm1 / norm2 folded into the Linear that follows them
             pk[f"b{i}.qkv.whn"], pk[f"b{i}.qkv.bhn"] = pack_qkv_heads(*fold_layernorm(
                 sd[f"{p}.attn.qkv.weight"], sd[f"{p}.attn.qkv.bias"], sd[f"{p}.norm1.weight"], sd[f"{p}.norm1.bias"]))
             pk[f"b{i}.fc1.wfqn"], pk[f"b{i}.fc1.bqn"] = pack_fc1_fused_q(*fold_layernorm(
