@@ -68,6 +68,13 @@ GUARDED = [
     # one of them into a private array puts scratch latency into the one lane the whole workgroup waits for
     ("png_encode.hip", ["png_filter_kernel", "png_block_kernel", "png_scan_kernel"]),
 ]
+# (source file, mangled-name fragment, registers): instantiations that must also stay within a register budget (VGPRs + AGPRs)
+REG_BUDGET = [
+    # patch_unembed's 8-wave form, __launch_bounds__(512, 1): two waves per SIMD is all its one workgroup per CU asks for, so the
+    # compiler would hand it 512 registers; it must stay what the 4-wave form is, wave for wave (<= 256)
+    ("gemm_tokens.hip", "gemm_panel2_kernelILi0ELi4ELi8E", 256),
+    ("gemm_tokens.hip", "gemm_panel2_kernelILi1ELi4ELi8E", 256),
+]
 # diagnostic template instantiations, never launched by the product path: fused_qkv_attn_kernel<STAMPS = true, TGN>, blocks_stream_kernel<true>
 EXEMPT = re.compile(r"fused_qkv_attn_kernel<true, \d>|fused_qkv_attn_kernelILb1ELi\d+E|blocks_stream_kernel<true>|blocks_stream_kernelILb1E")
 
@@ -108,7 +115,7 @@ def main(argv):
             out_path = a[6:]
         else:
             files.append(a)
-    report, bad = {}, []
+    report, bad, over, seen_budget = {}, [], [], set()
     for f in sorted(files):
         src = os.path.basename(f).replace(".remarks", ".hip")
         recs = parse(f)
@@ -122,6 +129,12 @@ def main(argv):
             report[nice] = rec
             if guarded and rec.get("scratch_bytes_per_lane", 0) > 0:
                 bad.append((src, nice, rec["scratch_bytes_per_lane"]))
+            for bsrc, frag, budget in REG_BUDGET:
+                if src == bsrc and frag in mangled:
+                    seen_budget.add(frag)
+                    rec["register_budget"] = budget
+                    if rec.get("vgprs", 0) + rec.get("agprs", 0) > budget:
+                        over.append((src, nice, rec.get("vgprs", 0) + rec.get("agprs", 0), budget))
     try:
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         ver = subprocess.run([hipcc, "--version"], capture_output=True, text=True).stdout
@@ -137,6 +150,14 @@ def main(argv):
         for src, nice, sc in bad:
             sys.stderr.write(f"check_resources: {src}: {nice} uses {sc} B/lane of scratch; its hand-counted vmcnt waits "
                              "would be wrong (scratch traffic counts on vmcnt). Reduce register pressure; do not ship this build.\n")
+        return 1
+    for src, nice, regs, budget in over:
+        sys.stderr.write(f"check_resources: {src}: {nice} uses {regs} registers, its budget is {budget}. Do not ship this build.\n")
+    srcs = {os.path.basename(f).replace(".remarks", ".hip") for f in files}
+    missing = [frag for bsrc, frag, _ in REG_BUDGET if bsrc in srcs and frag not in seen_budget]
+    for frag in missing:
+        sys.stderr.write(f"check_resources: no kernel matches the register-budget entry {frag}; correct the entry.\n")
+    if over or missing:
         return 1
     n_guard = sum(1 for r in report.values() if r["guarded_no_scratch"])
     print(f"check_resources: {len(report)} kernels, {n_guard} guarded (scratch 0), compiler {compiler}")

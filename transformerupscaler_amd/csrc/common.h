@@ -292,7 +292,9 @@ inline void drop_pair_params(float p, uint32_t& thresh_hi, float& inv_keep) {
             done_ |= 1ull << (dev_ & 63); } } while (0)
 
 // A/B switches, tuning knobs and timing ablations are read from the environment ONLY in the diagnostic library (`make diag`,
-// -DTUP_DIAG); the product library compiles the defaults in and reads no TUP_* variable.
+// -DTUP_DIAG); the product library compiles the defaults in and reads no TUP_* variable -- but for TUP_UNEMBED_WAVES, by which
+// tests/test_hip_unembed_wide.py takes the product library's 8-wave patch_unembed at sizes the router gives to the 4-wave form
+// (gemm_tokens.hip, launch_panel).
 #ifdef TUP_DIAG
 #define TUP_ENV_FLAG(name) (getenv(name) != nullptr)
 #define TUP_ENV_INT(name, dflt) (getenv(name) ? atoi(getenv(name)) : (dflt))

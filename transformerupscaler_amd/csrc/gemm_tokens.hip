@@ -35,6 +35,10 @@ struct GemmParams {
     const float* pos;             // E_PATCH_EMBED with linear tokens: + pos_embed[token][n]
     int M, N, K;
     int H, W, Ht, Wt_, nWx, nWy; // geometry for the patch modes (token rows are in window layout)
+#ifdef TUP_DIAG
+    int ablate;                  // E_UNEMBED panel kernel, timing only (results are wrong): 1 no weight DMA after tile 0, 2 no skip loads,
+                                 // 4 no output stores, 8 no MFMAs
+#endif
 };
 
 constexpr int BM = 128, BN = 64, BK = 64;
@@ -127,10 +131,16 @@ TUP_DEVICE u32x4 global_load_b128_async(const void* ptr) {
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(ptr) : "memory");
     return v;
 }
-TUP_DEVICE u32x4 global_load_b128_async_16(const void* ptr) {
-    u32x4 v;
-    asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=v"(v) : "v"(ptr) : "memory");
-    return v;
+// s_waitcnt vmcnt(n) for a count that is a sum of per-leg constants: in the product build every call site passes a compile-time
+// constant and one instruction is left; the diagnostic build's timing ablations make it a uniform branch.
+TUP_DEVICE void vm_wait_n(int n) {
+    switch (n) {
+#define TUP_VM_CASE(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
+        TUP_VM_CASE(0) TUP_VM_CASE(3) TUP_VM_CASE(4) TUP_VM_CASE(6) TUP_VM_CASE(7) TUP_VM_CASE(8) TUP_VM_CASE(10) TUP_VM_CASE(11)
+        TUP_VM_CASE(12) TUP_VM_CASE(14)
+#undef TUP_VM_CASE
+        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;          // not a sum that occurs: wait for everything
+    }
 }
 
 // The epilogues that READ memory (residual row, skip pixels, saved pre-activation), stated once and in two halves: epi_prefetch
@@ -419,30 +429,43 @@ __global__ __launch_bounds__(256, 2) void gemm_tokens_kernel(const GemmParams p)
 // weight tiles.  LDS holds only the weight stream: two 24 KB buffers filled by LDS-DMA one tile ahead, ONE workgroup barrier per
 // tile.  K loop: weight fragments two K-steps ahead, immediate-offset reads.  Epilogue operands are requested before the K loop
 // (epi_prefetch).  48 KB of LDS, <= 256 VGPRs: two 4-wave workgroups per CU.
+// patch_unembed (E_UNEMBED) has a second form, WAVES = 8: ONE workgroup of 8 waves and 256 rows per CU with one weight double buffer,
+// each thread issuing 3 of a tile's 6 pieces.  Two 4-wave workgroups on a CU fetch every weight tile twice into two buffers that hold
+// the same bytes (1.44 GB of L2 -> LDS traffic at 8 x 720p beside 2.07 GB of HBM traffic, through the same vector-memory path); the
+// 8-wave form fetches it once.  A wave's code is the same in both forms: 32 rows, the same fragments, the same arithmetic in the same
+// order.  launch_panel picks the form.
 // ------------------------------------------------------------------------------------------------
 constexpr int PK = 192, PBM = 128;
 constexpr int PW_BYTES = 3 * 64 * 128;
 // (Measured: the A_F32 / E_UNEMBED instance built for THREE workgroups per CU -- 168 registers, 17 of them spilled -- makes the forward
 // 0.2 ms slower, 4.12 vs 3.91 ms; two workgroups per CU it stays.)
-template <int AMODE, int EPI>
-__global__ __launch_bounds__(256, 2) void gemm_panel2_kernel(const GemmParams p)
+template <int AMODE, int EPI, int WAVES = 4>
+__global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void gemm_panel2_kernel(const GemmParams p)
 {
+    static_assert(WAVES == 4 || (WAVES == 8 && EPI == E_UNEMBED), "the 8-wave form exists for patch_unembed only");
+    constexpr int NPIECE = 24 / WAVES;                                   // weight pieces per thread and tile: 6 | 3
     extern __shared__ __attribute__((aligned(16))) char smem[];          // 2 x PW_BYTES
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, pl = lane & 15;
-    const int m0 = blockIdx.x * PBM;
+    const int m0 = blockIdx.x * (32 * WAVES);
     const int ntiles = p.N / 64;
 
-    // weight tile nt -> LDS buffer: slot s = u*256 + tid -> k-tile u >> 1, row (u & 1)*32 + (tid >> 3), logical chunk
-    // (tid & 7) ^ ((tid >> 4) & 7) (swizzle on the source side); six pieces per thread, compile-time offsets
+    // weight tile nt -> LDS buffer, logical chunk (tid & 7) ^ ((tid >> 4) & 7) (swizzle on the source side), compile-time offsets.
+    // 4 waves: slot s = u*256 + tid -> k-tile u >> 1, row (u & 1)*32 + (tid >> 3), six pieces per thread;
+    // 8 waves: slot s = u*512 + tid -> k-tile u, row tid >> 3, three pieces per thread
     const bf16_t* w_thr = p.Wt + (size_t)(tid >> 3) * PK + ((tid & 7) ^ ((tid >> 4) & 7)) * 8;
     auto dma_w = [&](int nt, int buf) {
         char* dst = smem + buf * PW_BYTES + wave * 1024;
         const bf16_t* src = w_thr + (size_t)nt * 64 * PK;
 #pragma unroll
-        for (int u = 0; u < 6; ++u)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (u & 1) * 32 * PK + (u >> 1) * 64),
-                                             (__attribute__((address_space(3))) void*)(dst + u * 4096), 16, 0, 0);
+        for (int u = 0; u < NPIECE; ++u) {
+            if constexpr (WAVES == 4)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (u & 1) * 32 * PK + (u >> 1) * 64),
+                                                 (__attribute__((address_space(3))) void*)(dst + u * 4096), 16, 0, 0);
+            else
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + u * 64),
+                                                 (__attribute__((address_space(3))) void*)(dst + u * 8192), 16, 0, 0);
+        }
     };
     dma_w(0, 0);
 
@@ -481,39 +504,65 @@ __global__ __launch_bounds__(256, 2) void gemm_panel2_kernel(const GemmParams p)
         // patch_unembed: 64 column tiles (one patch pixel each), every tile reads 16 KB of `skip` and writes 16 KB per workgroup.
         // The `skip` lines of tile nt + 1 are requested at the top of tile nt: requested in their own tile they had one K loop
         // (0.4 us) to arrive, and every tile waited out the HBM latency with only the CU's second workgroup to cover it.  The
-        // loads are asm (untracked), all waits counted: per tile and lane exactly 6 weight pieces, 4 skip loads, 4 stores (rows
-        // outside the map load the map's first pixel / store to the sink).  Two operand sets, the tile loop unrolled by two.
+        // loads are asm (untracked), all waits counted: per tile and lane exactly NPIECE weight pieces, 4 skip loads, 4 stores (rows
+        // outside the map load the map's first pixel / store to the sink; waves of the 8-wave form without a row below M do the same and
+        // take every barrier).  Two operand sets, the tile loop unrolled by two.
+#ifdef TUP_DIAG
+        const int abl = p.ablate;                              // timing ablations (GemmParams::ablate)
+#else
+        constexpr int abl = 0;
+#endif
+        const int wN = (abl & 1) ? 0 : NPIECE, skipN = (abl & 2) ? 0 : 4, storeN = (abl & 4) ? 0 : 4;      // counted per tile and lane
         float bvec[16];
         gemm_load_bias(p, 0, g, true, bvec);                   // [64] base channels: the same for every tile
-        size_t base[2];                                        // element offset of the patch origin (+ this lane's 16 channels)
-        int py0[2], px0[2];
-        bool tok_ok[2];
+        // Lane (g, pl) computes chunks 2g and 2g + 1 (16 B each) of token pl's pixel, but loads and stores chunk 2g + (pl >> 3) of the
+        // pixels of tokens pl & 7 (instruction h = 0) and (pl & 7) + 8 (h = 1): one instruction then covers eight whole 128-byte lines
+        // instead of sixteen half lines at a 32-byte stride.  Lanes pl and pl ^ 8 swap one chunk (DPP row_ror:8, as
+        // store_group_coalesced in conv_thin.hip) after the loads land and before the stores go out.
+        const bool hi = pl >= 8;
+        const int ch_off = (2 * g + (hi ? 1 : 0)) * 8;         // the first channel this lane loads and stores
+        size_t base[2][2];                                     // [tg][h]: element offset of the patch origin (+ ch_off)
+        int py0[2][2], px0[2][2];
+        bool tok_ok[2][2];
 #pragma unroll
-        for (int tg = 0; tg < 2; ++tg) {
-            const int m = m0 + 32 * wave + 16 * tg + pl;
-            const TokPos t = token_of_row(min(m, p.M - 1), p);
-            tok_ok[tg] = t.valid && m < p.M;
-            py0[tg] = t.ty * 8; px0[tg] = t.tx * 8;
-            base[tg] = (((size_t)t.b * p.H) * p.W) * 64 + g * 16;
-        }
-        struct Ops { u32x4 a[2][2]; size_t off[2]; bool ok[2]; };
+        for (int tg = 0; tg < 2; ++tg)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int m = m0 + 32 * wave + 16 * tg + (pl & 7) + 8 * h;
+                const TokPos t = token_of_row(min(m, p.M - 1), p);
+                tok_ok[tg][h] = t.valid && m < p.M;
+                py0[tg][h] = t.ty * 8; px0[tg][h] = t.tx * 8;
+                base[tg][h] = (((size_t)t.b * p.H) * p.W) * 64 + ch_off;
+            }
+        struct Ops { u32x4 a[2][2]; size_t off[2][2]; bool ok[2][2]; };
         auto issue = [&](int nt, Ops& o) {
             const int i = nt >> 3, j = nt & 7;
 #pragma unroll
             for (int tg = 0; tg < 2; ++tg) {
-                const int py = py0[tg] + i, px = px0[tg] + j;
-                o.ok[tg] = tok_ok[tg] && py < p.H && px < p.W;
-                o.off[tg] = base[tg] + ((size_t)py * p.W + px) * 64;
-                const bf16_t* sp = (p.skip ? p.skip : (const bf16_t*)p.out) + (o.ok[tg] ? o.off[tg] : (size_t)(g * 16));
-                o.a[tg][0] = global_load_b128_async(sp);
-                o.a[tg][1] = global_load_b128_async_16(sp);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int py = py0[tg][h] + i, px = px0[tg][h] + j;
+                    o.ok[tg][h] = tok_ok[tg][h] && py < p.H && px < p.W;
+                    o.off[tg][h] = base[tg][h] + ((size_t)py * p.W + px) * 64;
+                }
+                if (abl & 2) { o.a[tg][0] = u32x4{0u, 0u, 0u, 0u}; o.a[tg][1] = u32x4{0u, 0u, 0u, 0u}; continue; }
+                const bf16_t* sm = p.skip ? p.skip : (const bf16_t*)p.out;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) o.a[tg][h] = global_load_b128_async(sm + (o.ok[tg][h] ? o.off[tg][h] : (size_t)ch_off));
             }
         };
+        auto swap8 = [](const u32x4& v) {                      // the value lane pl ^ 8 passes in
+            u32x4 r;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) r[q] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v[q], 0x128, 0xf, 0xf, false);      // row_ror:8
+            return r;
+        };
         auto tile = [&](int nt, Ops& cur, Ops& nx) {
+            const bool has_nx = nt + 1 < ntiles;
             // own pieces of W tile nt (requested a tile ago); younger: the 4 skip loads of tile nt, the 4 stores of tile nt-1
-            if (nt > 0) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            if (nt > 0) vm_wait_n(skipN + storeN);
             __builtin_amdgcn_s_barrier();                      // everyone's pieces landed; everyone finished reading tile nt-1
-            if (nt + 1 < ntiles) { dma_w(nt + 1, (nt + 1) & 1); issue(nt + 1, nx); }
+            if (has_nx) { if (!(abl & 1)) dma_w(nt + 1, (nt + 1) & 1); issue(nt + 1, nx); }
             __builtin_amdgcn_sched_barrier(0);
             f32x4 acc[2][4];
 #pragma unroll
@@ -541,25 +590,33 @@ __global__ __launch_bounds__(256, 2) void gemm_panel2_kernel(const GemmParams p)
 #pragma unroll
                 for (int tg = 0; tg < 2; ++tg)
 #pragma unroll
-                    for (int ct = 0; ct < 4; ++ct) acc[tg][ct] = mfma16x16x32(wf[c3][ct], tf[tg][step], acc[tg][ct]);
+                    for (int ct = 0; ct < 4; ++ct) { if (!(abl & 8)) acc[tg][ct] = mfma16x16x32(wf[c3][ct], tf[tg][step], acc[tg][ct]); }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            // this tile's skip lines, requested a tile ago; younger: the stores of tile nt-1 (4), W pieces (6) + skip loads (4) of nt+1
-            if (nt + 1 < ntiles) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            // this tile's skip lines, requested a tile ago; younger: the stores of tile nt-1 (4), W pieces (6 | 3) + skip loads (4) of nt+1
+            if (has_nx) vm_wait_n(storeN + wN + skipN);
+            else vm_wait_n(storeN);
 #pragma unroll
             for (int tg = 0; tg < 2; ++tg) {
                 asm volatile("" : "+v"(cur.a[tg][0]), "+v"(cur.a[tg][1]));      // the loads' outputs are live only from here
+                // low lanes hold chunk 2g of tokens pl and pl + 8, high lanes chunk 2g + 1 of tokens pl - 8 and pl
+                const u32x4 got = swap8(hi ? cur.a[tg][0] : cur.a[tg][1]);
+                const u32x4 s0 = hi ? got : cur.a[tg][0], s1 = hi ? cur.a[tg][1] : got;      // chunks 2g, 2g + 1 of `skip` at token pl's pixel
                 uint32_t pk[8];
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
-                    uint32_t sw = (q < 4) ? cur.a[tg][0][q & 3] : cur.a[tg][1][q & 3];
+                    uint32_t sw = (q < 4) ? s0[q & 3] : s1[q & 3];
                     if (!p.skip) sw = 0u;                      // the loads then read `out`
                     const int ct = q >> 1, e = (q & 1) * 2;
                     pk[q] = unembed_pair(acc[tg][ct][e], acc[tg][ct][e + 1], bvec[2 * q], bvec[2 * q + 1], sw);
                 }
-                bf16_t* o = cur.ok[tg] ? (bf16_t*)p.out + cur.off[tg] : reinterpret_cast<bf16_t*>(tup_gemm_sink) + lane * 16;
-                store_bf16x16(o, pk);
+                bf16_t* sink = reinterpret_cast<bf16_t*>(tup_gemm_sink) + lane * 16;
+                const u32x4 lo4 = u32x4{pk[0], pk[1], pk[2], pk[3]}, hi4 = u32x4{pk[4], pk[5], pk[6], pk[7]};
+                const u32x4 back = swap8(hi ? lo4 : hi4);
+                if (!(abl & 4)) {
+                    *reinterpret_cast<u32x4*>(cur.ok[tg][0] ? (bf16_t*)p.out + cur.off[tg][0] : sink) = hi ? back : lo4;
+                    *reinterpret_cast<u32x4*>(cur.ok[tg][1] ? (bf16_t*)p.out + cur.off[tg][1] : sink + 8) = hi ? hi4 : back;
+                }
             }
         };
         Ops A, B;
@@ -664,12 +721,48 @@ __global__ __launch_bounds__(256, 2) void gemm_panel2_kernel(const GemmParams p)
     }
 }
 
+// Compute units of the current device, asked once per device.
+int device_cu_count(int& cus)
+{
+    static int cached[64] = {};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return (int)e;
+    int& c = cached[dev & 63];
+    if (c == 0) {
+        e = hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e != hipSuccess) { c = 0; return (int)e; }
+    }
+    cus = c;
+    return 0;
+}
+
 template <int AMODE, int EPI>
 int launch_panel(const GemmParams& p, hipStream_t s)
 {
     if (p.M <= 0) return 0;
     if (p.N % 64 != 0 || p.K != PK) return (int)hipErrorInvalidValue;
-    gemm_panel2_kernel<AMODE, EPI><<<dim3((p.M + PBM - 1) / PBM), dim3(256), 2 * PW_BYTES, s>>>(p);
+    GemmParams q = p;
+#ifdef TUP_DIAG
+    q.ablate = TUP_ENV_INT("TUP_UNEMBED_ABLATE", 0);          // patch_unembed's timing legs (GemmParams::ablate)
+#endif
+    if constexpr (EPI == E_UNEMBED) {
+        // patch_unembed: one 8-wave workgroup of 256 rows per CU (one weight stream per CU instead of two) once there is a workgroup
+        // for every CU; below that (the 240-window overlay frame, small training shapes) the 4-wave form, which fills twice as many.
+        // TUP_UNEMBED_WAVES = 4 | 8 forces a form (read once): the tests reach the 8-wave form at small sizes through it.
+        static const int forced = getenv("TUP_UNEMBED_WAVES") ? atoi(getenv("TUP_UNEMBED_WAVES")) : 0;
+        int cus = 0;
+        if (forced != 4 && forced != 8) {
+            const int e = device_cu_count(cus);
+            if (e != 0) return e;
+        }
+        if (forced == 8 || (forced != 4 && (p.M + 255) / 256 >= cus)) {
+            gemm_panel2_kernel<AMODE, EPI, 8><<<dim3((p.M + 255) / 256), dim3(512), 2 * PW_BYTES, s>>>(q);
+            TUP_CHECK_LAUNCH();
+            return 0;
+        }
+    }
+    gemm_panel2_kernel<AMODE, EPI><<<dim3((p.M + PBM - 1) / PBM), dim3(256), 2 * PW_BYTES, s>>>(q);
     TUP_CHECK_LAUNCH();
     return 0;
 }
