@@ -23,7 +23,10 @@
 extern "C" {
 #endif
 
-/* library / ABI version, bumped when a signature changes or an entry is removed (16: seven entries removed, none changed) */
+/* library / ABI version, bumped when a signature changes or an entry is removed (16: seven entries removed, none changed).
+ * This header is compiled into every translation unit of the library (a definition that drifts from its prototype fails the
+ * build) and the Python binding parses it at import: it is the one place where an entry or the version number is written. */
+#define TUP_ABI_VERSION 16
 int tup_abi_version(void);
 
 /* conv1: Conv2d(3,64,k3,p1)+ReLU. model.py:202-203,251.

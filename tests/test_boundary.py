@@ -11,23 +11,87 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _abi import ABI          # tests/ is on sys.path (rootdir-less test modules)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_library_exports_every_declared_symbol():
+    """The header, the definitions in csrc/*.hip and the built library name the same entries (the compiler holds their argument lists
+    equal: the header is compiled into every translation unit), and the header, the binding, the library and the tests agree on the
+    ABI number."""
     from transformerupscaler_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "tupscale_hip.h")).read()
     declared = set(re.findall(r"\b(?:int|long long)\s+(tup_\w+)\s*\(", hdr))
     assert declared, "no declarations parsed"
-    assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
+    csrc = os.path.join(ROOT, "transformerupscaler_amd", "csrc")
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(".hip")}
+    defined = [n for text in sources.values() for n in re.findall(r'extern\s+"C"\s+(?:int|long long)\s+(tup_\w+)\s*\(', text)]
+    assert len(defined) == len(set(defined)), sorted(n for n in set(defined) if defined.count(n) > 1)
+    product = {n for n in defined if not n.startswith("tup_debug_")}          # tup_debug_*: the diagnostic build only (common.h)
+    assert product == declared, product ^ declared
     lib = _lib.load()                      # raises if the .so or any symbol is missing
-    assert lib.tup_abi_version() == _lib.ABI_VERSION
     for name in declared:
-        assert hasattr(lib, name)
+        assert hasattr(lib, name), name
+    assert re.search(r"^#define TUP_ABI_VERSION %d$" % ABI, hdr, re.M)
+    assert lib.tup_abi_version() == _lib.ABI_VERSION == ABI
     # ABI 16 removed seven entries (the block kernel's half forms and their helpers); none may linger anywhere
     for name in ("tup_fused_qkv_attn_fwd", "tup_fused_attn_block_fwd", "tup_fused_block_fwd", "tup_fused_mlp_fwd", "tup_ln_gemm_fwd",
                  "tup_tail_stream_weight_source", "tup_debug_mlp_stamps"):
         assert name not in hdr and name not in _lib.SIGNATURES and not hasattr(lib, name), name
+        assert not any(name in text for text in sources.values()), name
+
+
+_PARSER_CASES = {          # entry -> (argtypes, restype), written out by hand from include/tupscale_hip.h
+    "tup_grad_guard_finish": ("P I D I P P", "I"),                                  # a double scalar
+    "tup_slab_reduce": ("P L I P L I P", "I"),                                      # long long scalars
+    "tup_window_attn_fwd": ("P P P P I F U P", "I"),                                # float, unsigned int
+    "tup_abi_version": ("", "I"),                                                   # (void)
+    "tup_tail_stream_r2_resize_fwd": ("P P P P P P P P P P I P P P I P P I I I I I I I I I P", "I"),      # wraps over four lines
+    "tup_resize_aa_fwd": ("P P P P P I P P P I I I I I I I P", "I"),                # wraps over three lines
+    "tup_blocks_stream_fwd": ("P P P I I P", "I"),                                  # const void* const*
+    "tup_window_attn_bwd_scratch": ("I I", "L"),                                    # the three counts
+    "tup_conv_wgrad_slab": ("I I I I I", "L"),
+    "tup_wgrad_slab": ("I L I I", "L"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(_PARSER_CASES))
+def test_binding_parser_reads_the_header(name):
+    import ctypes
+    from transformerupscaler_amd import _lib
+    kinds = {"P": ctypes.c_void_p, "I": ctypes.c_int, "L": ctypes.c_longlong, "F": ctypes.c_float, "D": ctypes.c_double,
+             "U": ctypes.c_uint}
+    hdr = open(os.path.join(ROOT, "include", "tupscale_hip.h")).read()
+    signatures, restypes, version = _lib._parse_header(hdr)
+    assert version == ABI and signatures == _lib.SIGNATURES and restypes == _lib.RESTYPES
+    args, ret = _PARSER_CASES[name]
+    assert signatures[name] == [kinds[k] for k in args.split()], name
+    assert restypes[name] is kinds[ret], name
+    lines = {"tup_resize_aa_fwd": 3, "tup_tail_stream_r2_resize_fwd": 4}.get(name)
+    if lines:          # the case is what its comment says it is
+        proto = re.search(r"\bint\s+%s\s*\([^;]*;" % name, hdr).group(0)
+        assert proto.count("\n") == lines - 1
+    assert {n for n, r in restypes.items() if r is ctypes.c_longlong} == {"tup_window_attn_bwd_scratch", "tup_conv_wgrad_slab",
+                                                                           "tup_wgrad_slab"}
+
+
+@pytest.mark.parametrize("text, complaint", [
+    ("#define TUP_ABI_VERSION 16\nint tup_x(const float* a, size_t n, void* stream);", "size_t n"),           # unknown scalar type
+    ("#define TUP_ABI_VERSION 16\nint tup_x(const float* a, unsigned n);", "unsigned n"),
+    ("#define TUP_ABI_VERSION 16\nint tup_x(int);", "'int'"),                                                   # no parameter name
+    ("#define TUP_ABI_VERSION 16\nint tup_x();", "''"),                                                          # not (void)
+    ("#define TUP_ABI_VERSION 16\nfloat tup_x(int n);", "float tup_x"),                                         # unknown return type
+    ("#define TUP_ABI_VERSION 16\nint tup_x(int n) int tup_y(int n);", "tup_y"),                                # a lost semicolon
+    ("#define TUP_ABI_VERSION 16\nint other(int n);", "other"),                                                 # not an entry
+    ("#define TUP_ABI_VERSION 16\n/* int tup_x(int n); */", "no tup_"),                                         # no prototypes at all
+    ("int tup_x(int n);", "TUP_ABI_VERSION"),                                                                    # no version
+])
+def test_binding_parser_refuses_what_it_does_not_know(text, complaint):
+    from transformerupscaler_amd import _lib
+    with pytest.raises(_lib.TupscaleLibraryError) as e:
+        _lib._parse_header(text)
+    assert complaint in str(e.value), str(e.value)
 
 
 def test_plugin_surface_matches_reference_contract():
@@ -243,8 +307,8 @@ def test_pack_plan_maps_on_cpu(det_sd):
 
 def test_integration_md_ctypes_snippet_matches_header():
     """INTEGRATION.md section 2 shows the ctypes stub a maintainer would write.  Its `argtypes` / `restype` lines are executed
-    here against a recording stand-in for the library and compared with _lib.SIGNATURES (held equal to include/tupscale_hip.h
-    by test_library_exports_every_declared_symbol), and the example CALL must pass exactly that many arguments (VERDICT r2 #13:
+    here against a recording stand-in for the library and compared with _lib.SIGNATURES (parsed from include/tupscale_hip.h
+    at import; test_binding_parser_reads_the_header and the per-feature tests pin the parser), and the example CALL must pass exactly that many arguments (VERDICT r2 #13:
     the document had drifted to 4 pointers + 8 ints)."""
     import ctypes
     from transformerupscaler_amd import _lib

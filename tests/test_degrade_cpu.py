@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import _degrade_ref as REF
+from _abi import ABI
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = ((96, 96), (20, 28), (7, 13), (21, 21))
@@ -241,12 +242,12 @@ def test_degrade_is_declared_bound_and_exported():
     assert re.search(r"int tup_degrade_lr\(const float\* in, const void\* recs, int B, int H, int W, float\* out, void\* stream\);", header)
     P, I = _lib.P, _lib.I
     assert _lib.SIGNATURES["tup_degrade_lr"] == [P, P, I, I, I, P, P]
-    assert _lib.ABI_VERSION == 16                       # 16: seven entries removed, none changed
+    assert _lib.ABI_VERSION == ABI
     if not os.path.exists(_lib.LIB_PATH):
         pytest.fail(f"{_lib.LIB_PATH} is not built")
     lib = ctypes.CDLL(_lib.LIB_PATH)
     assert hasattr(lib, "tup_degrade_lr")
-    assert lib.tup_abi_version() == 16
+    assert lib.tup_abi_version() == ABI
     assert _lib.load() is not None                      # every bound symbol resolves
     guard = open(os.path.join(ROOT, "transformerupscaler_amd", "csrc", "check_resources.py")).read()
     assert '("degrade.hip", ["degrade_lr_kernel"])' in guard

@@ -1,10 +1,13 @@
 """CPU checks of the deterministic training mode's surface: the *_det entries and the slab-size query are declared, bound and
 exported, the ABI version is unchanged, the slab sizes are positive and repeatable, and ops.deterministic is explicit-only."""
+import ctypes
 import os
 import re
 
 import pytest
 import torch
+
+from _abi import ABI          # tests/ is on sys.path (rootdir-less test modules)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -25,8 +28,8 @@ def test_det_entries_are_declared_bound_and_exported():
         assert name in _lib.SIGNATURES, name
         assert hasattr(lib, name), name
     assert re.search(r"\blong long\s+tup_conv_wgrad_slab\s*\(", hdr)
-    assert "tup_conv_wgrad_slab" in _lib.COUNT_RETURNING
-    assert lib.tup_abi_version() == 16 == _lib.ABI_VERSION
+    assert _lib.RESTYPES["tup_conv_wgrad_slab"] is ctypes.c_longlong is lib.tup_conv_wgrad_slab.restype          # a count, not a hipError_t
+    assert lib.tup_abi_version() == ABI == _lib.ABI_VERSION
 
 
 @pytest.mark.parametrize("B,H,W", SHAPES)

@@ -2,10 +2,13 @@
 gradient GEMMs, column sums, LayerNorm backward) and their slab-size query are declared, bound and exported, the ABI version is
 unchanged, the slab sizes are positive, repeatable and a function of their arguments only, and ops.deterministic_mode restores
 the previous value."""
+import ctypes
 import os
 import re
 
 import pytest
+
+from _abi import ABI          # tests/ is on sys.path (rootdir-less test modules)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -40,11 +43,11 @@ def test_det_step_entries_are_declared_bound_and_exported():
     for name in DET_ENTRIES:
         assert hasattr(lib, name), name
     assert re.search(r"\blong long\s+tup_wgrad_slab\s*\(", hdr)
-    assert "tup_wgrad_slab" in _lib.COUNT_RETURNING
+    assert _lib.RESTYPES["tup_wgrad_slab"] is ctypes.c_longlong is lib.tup_wgrad_slab.restype          # a count, not a hipError_t
     for det, twin in TWINS.items():
         a, b = _lib.SIGNATURES[det], _lib.SIGNATURES[twin]
         assert a[:-2] == b[:-1] and a[-2:] == [_lib.P, _lib.P], (det, twin)
-    assert lib.tup_abi_version() == 16 == _lib.ABI_VERSION
+    assert lib.tup_abi_version() == ABI == _lib.ABI_VERSION
 
 
 @pytest.mark.parametrize("kind,M,NI,NJ", REQUESTS)

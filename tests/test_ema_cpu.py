@@ -12,6 +12,8 @@ import struct
 import pytest
 import torch
 
+from _abi import ABI          # tests/ is on sys.path (rootdir-less test modules)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -239,11 +241,11 @@ def test_ema_entry_is_declared_bound_and_exported():
     assert re.search(r"int tup_adam_step_ema\(const void\* segs, const int\* chunks, int nchunks, const void\* guard, void\* stream\);", header)
     P, I = _lib.P, _lib.I
     assert _lib.SIGNATURES["tup_adam_step_ema"] == [P, P, I, P, P]
-    assert _lib.ABI_VERSION == 16                                             # 16: seven entries removed, none changed
+    assert _lib.ABI_VERSION == ABI
     if not os.path.exists(_lib.LIB_PATH):
         pytest.fail(f"{_lib.LIB_PATH} is not built")
     lib = ctypes.CDLL(_lib.LIB_PATH)
-    assert hasattr(lib, "tup_adam_step_ema") and lib.tup_abi_version() == 16
+    assert hasattr(lib, "tup_adam_step_ema") and lib.tup_abi_version() == ABI
     assert _lib.load() is not None
     src = open(os.path.join(ROOT, "transformerupscaler_amd", "csrc", "step_guard.hip")).read()
     assert optim._REC_EMA.size == 88 and "sizeof(AdamEmaSeg) == 88" in src

@@ -9,6 +9,7 @@ import pytest
 
 import ab_test
 import _metrics_ref as R          # tests/ is on sys.path (rootdir-less test modules)
+from _abi import ABI
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -93,8 +94,8 @@ def test_quality_entries_in_header_and_signatures():
         assert m, name
         assert len(m.group(1).split(",")) == nargs, name
         assert len(_lib.SIGNATURES[name]) == nargs, name
-    assert _lib.ABI_VERSION == 16
-    assert _lib.load().tup_abi_version() == 16
+    assert _lib.ABI_VERSION == ABI
+    assert _lib.load().tup_abi_version() == ABI
 
 
 def test_metrics_options_and_cpu_tensors_raise():

@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import fast_transformer_oracle as O
+from _abi import ABI
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -23,12 +24,12 @@ def test_grad_accumulate_is_declared_bound_and_exported():
     header = open(os.path.join(ROOT, "include", "tupscale_hip.h")).read()
     assert re.search(r"int tup_grad_accumulate\(const void\* segs, const int\* chunks, int nchunks, void\* stream\);", header)
     assert _lib.SIGNATURES["tup_grad_accumulate"] == [_lib.P, _lib.P, _lib.I, _lib.P]
-    assert _lib.ABI_VERSION == 16                       # 16: seven entries removed, none changed
+    assert _lib.ABI_VERSION == ABI
     if not os.path.exists(_lib.LIB_PATH):
         pytest.fail(f"{_lib.LIB_PATH} is not built")
     lib = ctypes.CDLL(_lib.LIB_PATH)
     assert hasattr(lib, "tup_grad_accumulate")
-    assert lib.tup_abi_version() == 16
+    assert lib.tup_abi_version() == ABI
     assert _lib.load() is not None                      # every bound symbol resolves
     guard = open(os.path.join(ROOT, "transformerupscaler_amd", "csrc", "check_resources.py")).read()
     assert '("grad_accumulate.hip", ["grad_accumulate_kernel"])' in guard

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import _patch_pairs_ref as REF
+from _abi import ABI
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCALES = (2, 3, 4, 6)
@@ -173,12 +174,12 @@ def test_patch_pairs_is_declared_bound_and_exported():
                      r"const int\* k, int ksize,\s+float\* hr, float\* lr, void\* stream\);", header)
     P, I = _lib.P, _lib.I
     assert _lib.SIGNATURES["tup_patch_pairs"] == [P, I, I, I, P, P, P, I, P, P, P]
-    assert _lib.ABI_VERSION == 16                       # 16: seven entries removed, none changed
+    assert _lib.ABI_VERSION == ABI
     if not os.path.exists(_lib.LIB_PATH):
         pytest.fail(f"{_lib.LIB_PATH} is not built")
     lib = ctypes.CDLL(_lib.LIB_PATH)
     assert hasattr(lib, "tup_patch_pairs")
-    assert lib.tup_abi_version() == 16
+    assert lib.tup_abi_version() == ABI
     assert _lib.load() is not None                      # every bound symbol resolves
     guard = open(os.path.join(ROOT, "transformerupscaler_amd", "csrc", "check_resources.py")).read()
     assert '("patch_pairs.hip", ["patch_pairs_kernel"])' in guard

@@ -10,6 +10,7 @@ import torch
 
 import _metrics_ref as M          # tests/ is on sys.path (rootdir-less test modules)
 import _quality_loss_ref as R
+from _abi import ABI
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F64 = torch.float64
@@ -82,7 +83,7 @@ def test_entries_in_header_signatures_and_library():
         assert len(m.group(1).split(",")) == nargs, name
         assert len(_lib.SIGNATURES[name]) == nargs, name
         assert hasattr(lib, name), name
-    assert _lib.ABI_VERSION == 16 and lib.tup_abi_version() == 16          # 16: seven entries removed, none changed
+    assert _lib.ABI_VERSION == ABI and lib.tup_abi_version() == ABI
 
 
 def test_new_kernel_is_on_the_no_scratch_guard_list():

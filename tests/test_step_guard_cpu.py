@@ -10,6 +10,8 @@ import re
 import pytest
 import torch
 
+from _abi import ABI          # tests/ is on sys.path (rootdir-less test modules)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {
     "tup_grad_sumsq_partial": r"int tup_grad_sumsq_partial\(const void\* segs, const int\* chunks, int nchunks, double\* partials, void\* stream\);",
@@ -31,13 +33,13 @@ def test_step_guard_entries_are_declared_bound_and_exported():
     assert _lib.SIGNATURES["tup_grad_guard_finish"] == [P, I, ctypes.c_double, I, P, P]
     assert _lib.SIGNATURES["tup_adam_step_guarded"] == [P, P, I, P, P]
     assert _lib.SIGNATURES["tup_adam_step"] == [P, P, I, P]              # the unguarded entry is untouched
-    assert _lib.ABI_VERSION == 16                                        # 16: seven entries removed, none changed
+    assert _lib.ABI_VERSION == ABI
     if not os.path.exists(_lib.LIB_PATH):
         pytest.fail(f"{_lib.LIB_PATH} is not built")
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in ENTRIES:
         assert hasattr(lib, name), name
-    assert lib.tup_abi_version() == 16
+    assert lib.tup_abi_version() == ABI
     assert _lib.load() is not None                                       # every bound symbol resolves
     guard = open(os.path.join(ROOT, "transformerupscaler_amd", "csrc", "check_resources.py")).read()
     assert '("step_guard.hip", ["grad_sumsq_kernel", "guard_finish_kernel", "adam_guarded_kernel"])' in guard

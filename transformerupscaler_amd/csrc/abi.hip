@@ -1,2 +1,2 @@
-#include <hip/hip_runtime.h>
-extern "C" int tup_abi_version(void) { return 16; }
+#include "tupscale_hip.h"
+extern "C" int tup_abi_version(void) { return TUP_ABI_VERSION; }

@@ -7,6 +7,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include "tupscale_hip.h"      // every exported entry is compiled against its public prototype (-Werror=missing-prototypes)
+
+#ifdef TUP_DIAG                // the diagnostic build's extra entries: not part of the public header
+extern "C" {
+int tup_debug_tail_stamps(unsigned long long* host_out);
+int tup_debug_bs_stamps(unsigned long long* host_out);
+int tup_debug_block32_stamps(unsigned long long* host_out);
+int tup_debug_conv_stamps(unsigned long long* host_out);
+}
+#endif
 
 typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
