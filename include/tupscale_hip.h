@@ -676,8 +676,9 @@ int tup_jpeg_write(const void* frames_u8, const float* frames_f32, int B, int H,
  * All images share H, W, layout (0 = 4:4:4, 2 = 4:2:0, 4 = one component) and restart_interval in MCUs (0 = none).  Three launches,
  * all capturable, no host synchronisation:
  *   tup_jpeg_decode_index   segs int32 [B][S][8] <- the walker's state at the start of every segment (a restart interval, or an MCU
- *                           row where the file has none: found by one serial walk per image); status int32 [B] <- 0, or non-zero for
- *                           a scan that does not decode completely;
+ *                           row where the file has none: found by one serial walk per image, or in parallel by
+ *                           tup_jpeg_decode_index_sync in its place); status int32 [B] <- 0, or non-zero for a scan that does not
+ *                           decode completely;
  *   tup_jpeg_decode_blocks  workspace uint8 [B][ws_bytes] <- the Y (Cb, Cr) sample planes padded to whole MCUs, ws_bytes = their
  *                           bytes for one image; status[b] <- non-zero where a segment's walk stops early;
  *   tup_jpeg_decode_finish  exactly one of out_u8 (uint8 [B][H][W][3], RGB) and out_f32 (fp32 [B][3][H][W] = byte / 255) <- the
@@ -690,6 +691,14 @@ int tup_jpeg_write(const void* frames_u8, const float* frames_f32, int B, int H,
 int tup_jpeg_decode_segments(int H, int W, int layout, int restart_interval);
 int tup_jpeg_decode_index(const void* records, const void* scans, long long scans_bytes, int B, int H, int W, int layout,
                           int restart_interval, int S, int* segs, int* status, void* stream);
+/* tup_jpeg_decode_index for images without a restart interval as a parallel pass (csrc/jpeg_sync.hip): self-synchronising Huffman
+ * decoding over subsequences of 132 raw bytes, a workgroup per image, one launch whatever the data.  segs int32 [B][S][8] with
+ * S = tup_jpeg_decode_segments(H, W, layout, 0) and status are what tup_jpeg_decode_index(restart_interval = 0) gives, except that a
+ * record of an image that decodes completely may hold another reader state (byte, bits, their number) for the same bit of the scan; a
+ * damaged or short scan is walked serially in the same launch and its records are word for word the serial index's.  rounds int32 [B],
+ * or null: the sync rounds each image took, at most its number of subsequences. */
+int tup_jpeg_decode_index_sync(const void* records, const void* scans, long long scans_bytes, int B, int H, int W, int layout, int* segs,
+                               int* status, int* rounds, void* stream);
 int tup_jpeg_decode_blocks(const void* records, const void* scans, long long scans_bytes, int B, int H, int W, int layout,
                            int restart_interval, int S, const int* segs, int* status, void* workspace, long long ws_bytes, void* stream);
 int tup_jpeg_decode_finish(const void* workspace, long long ws_bytes, int B, int H, int W, int layout, void* out_u8, float* out_f32,

@@ -6,8 +6,9 @@ by the GPU encoders: a PNG (lossless, ``ops.png_encode``) where the path ends in
 
 What happens, in the reference's order (inference.py:64-146):
 
-1. the input is decoded once: a baseline JPEG with restart markers on the GPU (``ops.jpeg_decode``), anything else (PNG, progressive
-   or restart-less JPEG) on the host by Pillow and uploaded as uint8;
+1. the input is decoded once: a baseline JPEG on the GPU (``ops.jpeg_decode``; a file without restart markers with ``index="sync"``,
+   DESIGN 7l), anything else (PNG, progressive JPEG) on the host by Pillow and uploaded as uint8; ``--json`` names which
+   (``input_decoder``);
 2. ``Resize(res_in)`` + ``ToTensor`` run on the GPU (``ops.resize_frames``, Pillow-exact BILINEAR; ``ops.frames_to_tensor``);
 3. ``--inp`` (the low-resolution input) and ``bicubic.jpg`` (``Image.resize(.., Image.BICUBIC)`` of it by ``--scale``, in the current
    directory as in the reference; ``ops.resize_frames(resample="bicubic")``, Pillow-exact) are encoded by ``ops.jpeg_encode``;
@@ -81,10 +82,12 @@ def file_format(path):
     return "png" if os.path.splitext(path)[1].lower() == ".png" else "jpeg"
 
 
-def decode_image(path_or_bytes, device, gpu=True):
-    """uint8 [H][W][3] RGB on the GPU.  A baseline JPEG with restart markers (every file this driver writes) is decoded there by
-    ``ops.jpeg_decode``, whose pixels are Pillow's; everything else (PNG, progressive or restart-less JPEG, a damaged file), or
-    everything with gpu=False, is one host decode by Pillow and an upload."""
+def decode_image_named(path_or_bytes, device, gpu=True):
+    """(uint8 [H][W][3] RGB on the GPU, the decoder that made it).  A baseline JPEG is decoded there by ``ops.jpeg_decode``, whose
+    pixels are Pillow's: with restart markers (every file this driver writes) interval by interval ("gpu:restart-intervals"),
+    without them through the self-synchronising index ("gpu:sync-index": ``index="sync"``, measured faster than the host for
+    2160 x 3840 files).  Everything else (PNG, progressive JPEG, a damaged file), or everything with gpu=False, is one
+    host decode by Pillow and an upload ("pillow")."""
     import numpy as np
     import torch
     from PIL import Image
@@ -95,19 +98,26 @@ def decode_image(path_or_bytes, device, gpu=True):
             with open(data, "rb") as f:
                 data = f.read()
         try:
-            fast = ops.jpeg_parse(data)["restart_interval"] > 0
+            index = "serial" if ops.jpeg_parse(data)["restart_interval"] > 0 else "sync"
         except ValueError:
-            fast = False
-        if fast:
+            index = None
+        if index:
             with torch.cuda.device(device):
-                frames, status = ops.jpeg_decode(data)
+                frames, status = ops.jpeg_decode(data, index=index)
             if int(status[0]) == 0:
-                return frames[0]
+                return frames[0], "gpu:sync-index" if index == "sync" else "gpu:restart-intervals"
         path_or_bytes = data
     src = io.BytesIO(path_or_bytes) if isinstance(path_or_bytes, (bytes, bytearray)) else path_or_bytes
     with Image.open(src) as im:
         arr = np.asarray(im.convert("RGB"))
-    return torch.from_numpy(arr.copy()).to(device)
+    return torch.from_numpy(arr.copy()).to(device), "pillow"
+
+
+def decode_image(path_or_bytes, device, gpu=True):
+    """The frame of `decode_image_named`; the decoder's name rides on it as the attribute ``decoder``."""
+    frame, name = decode_image_named(path_or_bytes, device, gpu)
+    frame.decoder = name
+    return frame
 
 
 def forward(model, lr, scale):
@@ -157,6 +167,7 @@ def run(args, device="cuda"):
         return data
 
     original = decode_image(args.image_path, device)
+    input_decoder = getattr(original, "decoder", None)
     lr_u8 = ops.resize_frames(original, res_in)[0] if res_in is not None else original
     files = {"inp": (args.inp, save(lr_u8, args.inp))}
     print(f"Downscaled image saved to: {args.inp}")
@@ -188,7 +199,7 @@ def run(args, device="cuda"):
     print(f"Model has {n_params} trainable parameters")
     sizes = {"inp": [h, w], "bicubic": [h * args.scale, w * args.scale], "out": [int(output.shape[2]), int(output.shape[3])]}
     return {"model": args.model, "checkpoint": checkpoint, "scale": args.scale, "res_in": args.res_in, "n_params": n_params,
-            "quality": args.quality, "subsampling": args.subsampling, "scores": scores,
+            "quality": args.quality, "subsampling": args.subsampling, "scores": scores, "input_decoder": input_decoder,
             "files": {k: {"path": p, "format": file_format(p), "size": sizes[k], "bytes": len(d)} for k, (p, d) in files.items()}}
 
 

@@ -11,14 +11,19 @@ One 2160 x 3840 and one 4320 x 7680 frame, "smooth" and "natural" content (as in
   host       in the same session, what it replaces: Pillow's `Image.open().convert("RGB")` plus `torch.from_numpy().to(device)`,
              wall clock, three runs.
 
-The status and the equality of the pixels with Pillow's are printed too.  Case (b) is one serial walk per image and is reported as it
-is.  inference.py sends a file to the GPU decoder only if it has restart markers; that choice rests on "op" against "host" for case
-(a) at 2160 x 3840.  Needs a GPU."""
+The status and the equality of the pixels with Pillow's are printed too.  --index {serial,sync} chooses launch 1 of case (b): "serial"
+(the default) is one lane's walk per image, "sync" the self-synchronising index (`tup_jpeg_decode_index_sync`), whose sync rounds are
+printed; with "sync" only case (b) is run, since launch 1 of case (a) is the same on either.  Compare the two from one session.
+inference.py sends a file without restart markers to the GPU decoder only if "op" with --index sync lies below "host" for both
+2160 x 3840 files.  Needs a GPU."""
 import os, sys; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import io, statistics, time, numpy as np, torch
+import argparse, io, statistics, time, numpy as np, torch
 from PIL import Image
 from transformerupscaler_amd import _lib, ops
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--index", choices=("serial", "sync"), default="serial", help="launch 1 of the files without restart markers")
+INDEX = ap.parse_args().index
 assert torch.cuda.is_available(), "this measurement needs the GPU"
 dev = "cuda"
 Q, SUB = 75, 2
@@ -80,6 +85,8 @@ for h, w in ((2160, 3840), (4320, 7680)):
     for kind in ("smooth", "natural"):
         pixels = content(h, w, kind)
         for case, rows in (("(a) a restart marker per MCU row", 1), ("(b) no restart markers", 0)):
+            if rows and INDEX == "sync":
+                continue
             buf = io.BytesIO()
             Image.fromarray(pixels).save(buf, "JPEG", quality=Q, subsampling=SUB, restart_marker_rows=rows)
             data = buf.getvalue()
@@ -98,16 +105,21 @@ for h, w in ((2160, 3840), (4320, 7680)):
             out = torch.empty((1, h, w, 3), dtype=torch.uint8, device=dev)
             st = ops._stream
             front = (up.data_ptr(), up.data_ptr() + rec, len(blob) - rec, 1, h, w, layout, interval, S, segs.data_ptr(), status.data_ptr())
-            index = lambda: _lib.call("tup_jpeg_decode_index", *front, st())
+            rounds = torch.zeros((1,), dtype=torch.int32, device=dev)
+            sync = INDEX == "sync" and not rows
+            index_name = "tup_jpeg_decode_index_sync" if sync else "tup_jpeg_decode_index"
+            index = (lambda: _lib.call(index_name, *front[:7], segs.data_ptr(), status.data_ptr(), rounds.data_ptr(), st())) if sync else \
+                (lambda: _lib.call(index_name, *front, st()))
             blocks = lambda: _lib.call("tup_jpeg_decode_blocks", *front, work.data_ptr(), ws, st())
             finish = lambda: _lib.call("tup_jpeg_decode_finish", work.data_ptr(), ws, 1, h, w, layout, out.data_ptr(), None, st())
             arms = {"all": lambda: (index(), blocks(), finish()), "index": index, "blocks": blocks, "finish": finish}
-            res = alternate(arms, n=5, rounds=5, warmup=2) if rows else alternate(arms, n=1, rounds=3, warmup=1)
-            title = f"{h} x {w}, {kind}, {case}"
+            res = alternate(arms, n=5, rounds=5, warmup=2) if rows or sync else alternate(arms, n=1, rounds=3, warmup=1)
+            title = f"{h} x {w}, {kind}, {case}" + (f", index {INDEX}" if not rows else "")
             show(f"{title}, three launches", res["all"], extra=f"  file {len(data) / 1e6:.2f} MB, {S} segments")
-            for name, what in (("index", "tup_jpeg_decode_index"), ("blocks", "tup_jpeg_decode_blocks"), ("finish", "tup_jpeg_decode_finish")):
+            for name, what in (("index", index_name + (f" ({int(rounds[0])} sync rounds, {-(-(end - start) // ops.JPEG_SYNC_BYTES)} subsequences of "
+                                                       f"{ops.JPEG_SYNC_BYTES} bytes)" if sync else "")), ("blocks", "tup_jpeg_decode_blocks"), ("finish", "tup_jpeg_decode_finish")):
                 show(f"{title}, {what}", res[name])
-            show(f"{title}, ops.jpeg_decode(out=...) with parse, upload and a final synchronisation", wall(lambda: ops.jpeg_decode(data, out=out)), unit="ms")
+            show(f"{title}, ops.jpeg_decode(out=...) with parse, upload and a final synchronisation", wall(lambda: ops.jpeg_decode(data, out=out, index=INDEX if not rows else "auto")), unit="ms")
             want = host_decode(data)
             show(f"{title}, Pillow open().convert('RGB') + upload", wall(lambda: host_decode(data)), unit="ms",
                  extra=f"  status {int(status[0])}, pixels equal to Pillow's: {bool(torch.equal(out[0], want))}")

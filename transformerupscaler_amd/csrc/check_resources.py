@@ -64,6 +64,9 @@ GUARDED = [
     # no counted hand-off: the one lane that walks the Huffman codes bounds the decoder, and its reader state, predictors and the IDCT's
     # 8 values a lane must stay in registers and LDS; scratch would put memory latency into every symbol
     ("jpeg_decode.hip", ["jpeg_index_kernel", "jpeg_blocks_kernel", "jpeg_finish_kernel"]),
+    # no counted hand-off: 256 lanes walk the Huffman codes of their subsequences out of LDS, several times over; their reader state and
+    # counts must stay in registers, scratch would put memory latency into every symbol of every lane
+    ("jpeg_sync.hip", ["jpeg_sync_index_kernel"]),
     # no counted hand-off: the Huffman builder, the header's run-length coder and the byte walks index LDS arrays only; a build that moves
     # one of them into a private array puts scratch latency into the one lane the whole workgroup waits for
     ("png_encode.hip", ["png_filter_kernel", "png_block_kernel", "png_scan_kernel"]),

@@ -1808,34 +1808,84 @@ def _jpeg_decode_record(info, data, scan_off):
     return _JPEG_DEC_REC.pack(scan_off, end - start, sel(info["dc_selectors"]), sel(info["ac_selectors"]), qt, spec)
 
 
-def jpeg_decode(files, to_tensor=False, out=None):
+JPEG_SYNC_BYTES = 132                                        # JS_BYTES of csrc/jpeg_sync.h: the raw bytes of a subsequence of the sync index
+_JPEG_INDEX = ("auto", "serial", "sync")
+
+
+def _jpeg_decode_files(who, files, index):
+    """The checks `jpeg_decode` and `jpeg_scan_index` share, ahead of any launch -> (files, infos, (H, W, subsampling, interval), the
+    index that runs)."""
+    if index not in _JPEG_INDEX:
+        raise ValueError(f"{who}: index must be one of {_JPEG_INDEX}, got {index!r}")
+    if isinstance(files, (bytes, bytearray, memoryview)):
+        files = [files]
+    try:
+        files = list(files)
+    except TypeError:
+        raise TypeError(f"{who}: files must be bytes or a sequence of bytes, got {type(files)}") from None
+    B = len(files)
+    if not 1 <= B <= 65535:
+        raise ValueError(f"{who}: {B} images in one call (1..65535)")
+    if any(not isinstance(f, (bytes, bytearray, memoryview)) for f in files):
+        raise TypeError(f"{who}: files must be bytes or a sequence of bytes")
+    infos = [jpeg_parse(f) for f in files]
+    key = lambda s: (s["H"], s["W"], s["subsampling"], s["restart_interval"])
+    for b, s in enumerate(infos):
+        if key(s) != key(infos[0]):
+            raise ValueError(f"{who}: the images of a call share H, W, subsampling and restart interval; image 0 has {key(infos[0])}, "
+                             f"image {b} has {key(s)}")
+    if index == "sync" and key(infos[0])[3]:
+        raise ValueError(f"{who}: index='sync' is for files without restart markers; these have a restart interval of {key(infos[0])[3]} MCUs")
+    # "auto" is what ran before there was a choice: the serial walk.  A test of the three launches pins the entry names of a
+    # restart-less call with default arguments, so the parallel index is asked for by name (inference.py does; DESIGN 7l)
+    return files, infos, key(infos[0]), "sync" if index == "sync" else "serial"
+
+
+def _jpeg_decode_upload(who, files, infos, H, W, layout, interval, dev):
+    """The one upload: the image records, then the scans, each at a multiple of 16 -> (tensor, bytes of scans, segments, workspace
+    bytes per image)."""
+    B = len(files)
+    S, ws = _jpeg_decode_geometry(H, W, layout, interval)
+    offs, at = [], B * _JPEG_DEC_REC.size
+    for s in infos:
+        offs.append(at)
+        at += (s["scan"][1] - s["scan"][0] + 15) & ~15
+    scans_bytes = at - B * _JPEG_DEC_REC.size
+    if scans_bytes > 0x7fff0000:
+        raise ValueError(f"{who}: {scans_bytes} bytes of scans in one call (below 2^31)")
+    lib = _lib.load()
+    if lib.tup_jpeg_decode_segments(H, W, layout, interval) != S:
+        raise RuntimeError(f"{who}: the library counts other segments than the binding")
+    host = bytearray(max(at, 16))
+    for b, (s, f) in enumerate(zip(infos, files)):
+        host[b * _JPEG_DEC_REC.size:(b + 1) * _JPEG_DEC_REC.size] = _jpeg_decode_record(s, f, offs[b] - B * _JPEG_DEC_REC.size)
+        host[offs[b]:offs[b] + s["scan"][1] - s["scan"][0]] = f[s["scan"][0]:s["scan"][1]]
+    return torch.frombuffer(host, dtype=torch.uint8).to(dev), scans_bytes, S, ws
+
+
+def _jpeg_decode_index(route, records, scans, scans_bytes, B, H, W, layout, interval, S, segs, status, rounds):
+    """Launch 1, by either route."""
+    if route == "sync":
+        _lib.call("tup_jpeg_decode_index_sync", records, scans, scans_bytes, B, H, W, layout, segs.data_ptr(), status.data_ptr(),
+                  None if rounds is None else rounds.data_ptr(), _stream())
+    else:
+        _lib.call("tup_jpeg_decode_index", records, scans, scans_bytes, B, H, W, layout, interval, S, segs.data_ptr(), status.data_ptr(), _stream())
+
+
+def jpeg_decode(files, to_tensor=False, out=None, index="auto"):
     """Baseline JPEG files decoded on the GPU in three launches.  files: bytes, or a sequence of bytes whose images share H, W,
     subsampling and restart interval (quantisation and Huffman tables are each image's own).  Returns (frames, status): frames uint8
     [B][H][W][3] RGB, pixel for pixel ``np.asarray(Image.open(io.BytesIO(f)).convert("RGB"))`` (a one-component file gives R = G = B);
     with to_tensor=True fp32 [B][3][H][W], bit-equal to `frames_to_tensor` of the uint8 result and written by the last kernel.
     status int32 [B] on the device: 0 for a scan that decoded completely; otherwise the file is damaged and its pixels are
     unspecified (the other images are unaffected).  out=: the caller's frames tensor.  One upload (the image records and the scans),
-    no read-back, no synchronisation.  Restart markers make a file fast: its intervals are walked in parallel; a file without them
-    costs one serial walk.  Everything is validated before any launch; what `jpeg_parse` refuses is refused here."""
-    if isinstance(files, (bytes, bytearray, memoryview)):
-        files = [files]
-    try:
-        files = list(files)
-    except TypeError:
-        raise TypeError(f"jpeg_decode: files must be bytes or a sequence of bytes, got {type(files)}") from None
-    B = len(files)
-    if not 1 <= B <= 65535:
-        raise ValueError(f"jpeg_decode: {B} images in one call (1..65535)")
-    if any(not isinstance(f, (bytes, bytearray, memoryview)) for f in files):
-        raise TypeError("jpeg_decode: files must be bytes or a sequence of bytes")
-    infos = [jpeg_parse(f) for f in files]
-    key = lambda s: (s["H"], s["W"], s["subsampling"], s["restart_interval"])
-    for b, s in enumerate(infos):
-        if key(s) != key(infos[0]):
-            raise ValueError(f"jpeg_decode: the images of a call share H, W, subsampling and restart interval; image 0 has {key(infos[0])}, "
-                             f"image {b} has {key(s)}")
-    H, W, sub, interval = key(infos[0])
-    layout = _JPEG_LAYOUT[sub]
+    no read-back, no synchronisation.  Restart markers make a file fast: its intervals are walked in parallel.  For a file without
+    them launch 1 finds the start of every MCU row, and `index` says how: "serial", one lane's walk through the whole scan; "sync",
+    self-synchronising decoding of subsequences of JPEG_SYNC_BYTES bytes by a whole workgroup (a ValueError for files with restart
+    markers); "auto", the serial walk.  Frames and status are the same bits on every route.  Everything is validated before any
+    launch; what `jpeg_parse` refuses is refused here."""
+    files, infos, (H, W, sub, interval), route = _jpeg_decode_files("jpeg_decode", files, index)
+    B, layout = len(files), _JPEG_LAYOUT[sub]
     shape, dtype = ((B, 3, H, W), F32) if to_tensor else ((B, H, W, 3), torch.uint8)
     if out is not None:
         if not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
@@ -1844,35 +1894,39 @@ def jpeg_decode(files, to_tensor=False, out=None):
         _nv12_on_gpu("jpeg_decode", out, "out")
     elif not torch.cuda.is_available():
         raise RuntimeError("jpeg_decode: the HIP path needs a GPU (no CPU fallback)")
-    S, ws = _jpeg_decode_geometry(H, W, layout, interval)
-    offs, at = [], B * _JPEG_DEC_REC.size                                 # records, then the scans, each at a multiple of 16
-    for s in infos:
-        offs.append(at)
-        at += (s["scan"][1] - s["scan"][0] + 15) & ~15
-    scans_bytes = at - B * _JPEG_DEC_REC.size
-    if scans_bytes > 0x7fff0000:
-        raise ValueError(f"jpeg_decode: {scans_bytes} bytes of scans in one call (below 2^31)")
-    lib = _lib.load()
-    if lib.tup_jpeg_decode_segments(H, W, layout, interval) != S:
-        raise RuntimeError("jpeg_decode: the library counts other segments than the binding")
-    host = bytearray(max(at, 16))
-    for b, (s, f) in enumerate(zip(infos, files)):
-        host[b * _JPEG_DEC_REC.size:(b + 1) * _JPEG_DEC_REC.size] = _jpeg_decode_record(s, f, offs[b] - B * _JPEG_DEC_REC.size)
-        host[offs[b]:offs[b] + s["scan"][1] - s["scan"][0]] = f[s["scan"][0]:s["scan"][1]]
     dev = out.device if out is not None else torch.device("cuda", _cur_dev())
-    up = torch.frombuffer(host, dtype=torch.uint8).to(dev)                 # the one upload
+    up, scans_bytes, S, ws = _jpeg_decode_upload("jpeg_decode", files, infos, H, W, layout, interval, dev)
     segs = torch.empty((B, S, 8), dtype=torch.int32, device=dev)
     status = torch.empty((B,), dtype=torch.int32, device=dev)
     work = torch.empty((B, ws), dtype=torch.uint8, device=dev)
     if out is None:
         out = torch.empty(shape, dtype=dtype, device=dev)
     records, scans = up.data_ptr(), up.data_ptr() + B * _JPEG_DEC_REC.size
-    _lib.call("tup_jpeg_decode_index", records, scans, scans_bytes, B, H, W, layout, interval, S, segs.data_ptr(), status.data_ptr(), _stream())
+    _jpeg_decode_index(route, records, scans, scans_bytes, B, H, W, layout, interval, S, segs, status, None)
     _lib.call("tup_jpeg_decode_blocks", records, scans, scans_bytes, B, H, W, layout, interval, S, segs.data_ptr(), status.data_ptr(),
               work.data_ptr(), ws, _stream())
     _lib.call("tup_jpeg_decode_finish", work.data_ptr(), ws, B, H, W, layout, None if to_tensor else out.data_ptr(),
               out.data_ptr() if to_tensor else None, _stream())
     return out, status
+
+
+def jpeg_scan_index(files, index="auto"):
+    """Launch 1 of `jpeg_decode` alone -> (segs int32 [B][S][8], status int32 [B], rounds int32 [B]) on the device.  A segment record
+    is {byte, end byte, the bits already read (at the top of the word) and their number, three DC predictors, first MCU}: the reader's
+    state at the start of a restart interval, or of an MCU row where the file has none; a number of bits of -1 marks a segment that
+    was not placed.  rounds: the sync rounds each image took (index="sync"; otherwise zeros).  The records of "serial" and "sync"
+    denote the same bits of the scan with the same predictors and MCU numbers; byte and bits may differ, since a reader that has
+    looked further ahead holds more bits."""
+    files, infos, (H, W, sub, interval), route = _jpeg_decode_files("jpeg_scan_index", files, index)
+    if not torch.cuda.is_available():
+        raise RuntimeError("jpeg_scan_index: the HIP path needs a GPU (no CPU fallback)")
+    B, layout, dev = len(files), _JPEG_LAYOUT[sub], torch.device("cuda", _cur_dev())
+    up, scans_bytes, S, _ = _jpeg_decode_upload("jpeg_scan_index", files, infos, H, W, layout, interval, dev)
+    segs = torch.empty((B, S, 8), dtype=torch.int32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    rounds = torch.zeros((B,), dtype=torch.int32, device=dev)
+    _jpeg_decode_index(route, up.data_ptr(), up.data_ptr() + B * _JPEG_DEC_REC.size, scans_bytes, B, H, W, layout, interval, S, segs, status, rounds)
+    return segs, status, rounds
 
 
 # ---- WindowTransformer (SURVEY 8(f) rank 2): the patch GEMMs in window layout, without reflect padding ----
