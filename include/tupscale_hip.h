@@ -439,6 +439,29 @@ int tup_f32chw_to_nv12(const float* src, void* y, void* uv, long long y_batch_st
                        long long uv_batch_stride, int uv_pitch,
                        int B, int H, int W, int matrix, int full_range, void* stream);
 
+/* P010 video frames (YUV 4:2:0, 10 bit: HEVC Main10, AV1 10-bit, UHD / HDR sources): the NV12 pair above carried to 10 bits
+ * (csrc/p010.hip; definition in DESIGN.md section 3, "P010 frames").
+ * Layout: y u16 [B][H][W]; uv u16 [B][H/2][W/2][2] = (Cb, Cr) pairs; samples little-endian with the 10-bit code in the HIGH bits:
+ * a reader takes code = sample >> 6 and ignores the low six bits, a writer stores code << 6.  The plane pointers are void*.  Each
+ * plane has its own row pitch and batch stride IN BYTES, both even (pitch >= 2 W).  matrix: 0 = BT.601, 1 = BT.709, 2 = BT.2020
+ * (non-constant luminance); full_range: 0 = Y 64..940 / chroma 64..960, 1 = 0..1023.  Chroma sited left, as for NV12.  The transfer
+ * function is not touched: PQ / HLG code values pass through as they are.
+ *   decode  the NV12 upsampling taps, cb = c8(Cb) - 4096, cr = c8(Cr) - 4096, R = clip10((cy (Y - yoff) + 32768 + rv cr) >> 16), ...;
+ *           dst fp32 [B][3][H][W] = code / 1023 (the IEEE quotient; never through 8 bits);
+ *   encode  src fp32 [B][3][H][W] -> codes q_10(x): t = x * 1023, NaN -> 0, clamp to [0, 1023], (int)(t + 0.5f) -- round to nearest,
+ *           where the 8-bit entries truncate -- then Y = clip10((ry R + gy G + by B + (yoff << 16) + 32768) >> 16) and chroma
+ *           clip10((ur sR + ug sG + ub sB + (512 << 19) + (1 << 18)) >> 19) from the [1 2 1] x [1 1] filter.  Samples between W and
+ *           the pitch are left untouched.
+ * One launch each, no allocation, synchronisation or host read (capturable into a hipGraph).  B <= 65535; an empty shape
+ * returns 0; odd H or W, a pitch below 2 W, a null or odd pointer, an odd pitch or batch stride, or an unknown matrix / full_range returns
+ * hipErrorInvalidValue before any launch. */
+int tup_p010_to_f32chw(const void* y, const void* uv, long long y_batch_stride, int y_pitch,
+                       long long uv_batch_stride, int uv_pitch, float* dst,
+                       int B, int H, int W, int matrix, int full_range, void* stream);
+int tup_f32chw_to_p010(const float* src, void* y, void* uv, long long y_batch_stride, int y_pitch,
+                       long long uv_batch_stride, int uv_pitch,
+                       int B, int H, int W, int matrix, int full_range, void* stream);
+
 /* ---- WindowTransformer plugin (models/WindowTransformer/model.py): the FastTransformer window
  * block at embedding width 128 / 8 heads ---- */
 
@@ -726,6 +749,22 @@ int tup_png_offsets(const int* sizes, const int* partials, int B, int H, int W, 
                     int* lengths, int* adlers, void* stream);
 int tup_png_write(const void* frames_u8, const float* frames_f32, int B, int H, int W, int filter, int block_bytes, const void* filters,
                   const int* offsets, const int* lengths, const int* adlers, void* data, long long capacity, void* stream);
+
+/* The same encoder for 16-bit files: IHDR bit depth 16, colour type 2, samples big-endian, bpp = 6, a row of 1 + 6 W filtered bytes
+ * (filters work on bytes, the left neighbour is 6 bytes back), refused from H * (1 + 6 W) = 2^31.  frames_u16 is uint16 [B][H][W][3]
+ * in the machine's byte order (an even address); frames_f32 fp32 [B][3][H][W] is quantised inside the kernels, with no intermediate
+ * frame, by q_16: t = x * 65535, NaN -> 0, clamp to [0, 65535], (int)(t + 0.5f) -- round to nearest, where the 8-bit entries
+ * truncate.  Ranges, tokens, code lengths, block forms, chunks, CRC and Adler are those of the 8-bit file; every other argument,
+ * workspace and refusal is as for its tup_png_* twin (same kernels, instantiated for two-byte samples).  tests/_png16_ref.py states
+ * the file. */
+int tup_png16_blocks(int H, int W, int block_bytes);
+int tup_png16_filters(const void* frames_u16, const float* frames_f32, int B, int H, int W, void* filters, void* stream);
+int tup_png16_sizes(const void* frames_u16, const float* frames_f32, int B, int H, int W, int filter, int block_bytes, const void* filters,
+                    int* sizes, int* partials, void* stream);
+int tup_png16_offsets(const int* sizes, const int* partials, int B, int H, int W, int block_bytes, long long capacity, int* offsets,
+                      int* lengths, int* adlers, void* stream);
+int tup_png16_write(const void* frames_u16, const float* frames_f32, int B, int H, int W, int filter, int block_bytes, const void* filters,
+                    const int* offsets, const int* lengths, const int* adlers, void* data, long long capacity, void* stream);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,11 @@ are PNG files: 8-bit RGB, adaptive filtering, coded by ``ops.png_encode`` (DESIG
 to them, and nothing is decoded for their scores: a PNG holds exactly the uint8 frame that was encoded (``tensor_to_frames`` of the
 output for ``--out``), so that frame is scored.  ``bicubic.jpg`` stays a JPEG.
 
+``--png_bits 16`` makes ``--out``, when it is a ``.png``, a 16-bit file (IHDR depth 16, ``ops.png_encode(.., bits=16)``): the model's
+fp32 output, the one source here with more than 8 bits, quantised by rounding to 0..65535 inside the encoder.  ``--inp`` and
+``bicubic.jpg`` come from uint8 frames and stay as they are; the scores stay on the 8-bit frame (``tensor_to_frames`` of the output),
+which is the reference's metric; the ``--json`` record names the depth of every file (``"bits"``).
+
 The JPEG files are what Pillow's ``save()`` writes for the same pixels at ``--quality`` / ``--subsampling`` (defaults 75 and 4:2:0, Pillow's
 own) with a restart marker after every MCU row; they decode to the same pixels as Pillow's files without restart markers.
 
@@ -75,6 +80,15 @@ def build_parser():
     p.add_argument("--quality", type=int, default=75, help="JPEG quality 1..100 (default 75, Pillow's); ignored for .png files")
     p.add_argument("--subsampling", type=str, default="4:2:0", choices=("4:2:0", "4:4:4"), help="JPEG chroma subsampling (default 4:2:0, Pillow's); ignored for .png files")
     return p
+
+
+def parse_args(argv=None):
+    """What the command line parses with: `build_parser()`, which stays the reference's flags plus the JPEG ones, and `--png_bits`."""
+    p = build_parser()
+    p.add_argument("--png_bits", type=int, default=8, choices=(8, 16),
+                   help="Bit depth of --out when it is a .png: 8 (default), or 16 for the model's fp32 output rounded to 16 bits; --inp and "
+                        "bicubic.jpg are made from 8-bit frames and stay 8-bit")
+    return p.parse_args(argv)
 
 
 def file_format(path):
@@ -157,9 +171,11 @@ def run(args, device="cuda"):
             print(f"--{flag} has no effect: the forward is made of HIP kernels")
     jpeg = dict(quality=args.quality, subsampling=args.subsampling)
 
-    def save(frames, path):
+    out_bits = 16 if getattr(args, "png_bits", 8) == 16 and file_format(args.out) == "png" else 8
+
+    def save(frames, path, bits=8):
         if file_format(path) == "png":
-            data = ops.png_files(*ops.png_encode(frames))[0]
+            data = ops.png_files(*(ops.png_encode(frames, bits=16) if bits == 16 else ops.png_encode(frames)))[0]
         else:
             data = ops.jpeg_files(*ops.jpeg_encode(frames, **jpeg))[0]
         with open(path, "wb") as f:
@@ -186,10 +202,11 @@ def run(args, device="cuda"):
     model = model.to(device).eval()
     with torch.no_grad():
         output = forward(model, ops.frames_to_tensor(lr_u8), args.scale)
-    files["out"] = (args.out, save(output.contiguous(), args.out))
+    files["out"] = (args.out, save(output.contiguous(), args.out, out_bits))
     print(f"Upscaled image saved to: {args.out}")
 
-    # a PNG is lossless: its pixels are the uint8 frame it was made from, so nothing is decoded for it
+    # a PNG is lossless: its pixels are the uint8 frame it was made from, so nothing is decoded for it (a 16-bit --out is scored on
+    # the same 8-bit frame: the reference's metric is an 8-bit one)
     out_u8 = ops.tensor_to_frames(output.contiguous())[0] if file_format(args.out) == "png" else decode_image(files["out"][1], device)
     inp_u8 = lr_u8 if file_format(args.inp) == "png" else decode_image(files["inp"][1], device)
     scores = score(original, out_u8, inp_u8)
@@ -200,11 +217,12 @@ def run(args, device="cuda"):
     sizes = {"inp": [h, w], "bicubic": [h * args.scale, w * args.scale], "out": [int(output.shape[2]), int(output.shape[3])]}
     return {"model": args.model, "checkpoint": checkpoint, "scale": args.scale, "res_in": args.res_in, "n_params": n_params,
             "quality": args.quality, "subsampling": args.subsampling, "scores": scores, "input_decoder": input_decoder,
-            "files": {k: {"path": p, "format": file_format(p), "size": sizes[k], "bytes": len(d)} for k, (p, d) in files.items()}}
+            "files": {k: {"path": p, "format": file_format(p), "size": sizes[k], "bytes": len(d), "bits": out_bits if k == "out" else 8}
+                      for k, (p, d) in files.items()}}
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     record = run(args)
     if args.json:
         with open(args.json, "w") as f:

@@ -10,7 +10,12 @@ launch alone (uint8 input), and the file's length.  Then, wall clock, three runs
               same at compress_level=6 (one run: it takes seconds);
 
 with the three files' lengths, and `ops.jpeg_encode` of the same frame for scale.  The GPU's file is decoded by Pillow and compared with
-the frame.  There is no threshold: nothing earlier does this work.  Needs a GPU."""
+the frame.  There is no threshold: nothing earlier does this work.  Needs a GPU.
+
+`--bits16` runs only the comparison of the two depths instead: per 2160 x 3840 content, an fp32 frame with more than 8 bits in it (the
+8-bit content plus a sub-level dither, so that the low bytes of the 16-bit samples are busy, as a model's output's are) encoded by
+`ops.png_encode(x, out=...)` at bits=8 and at bits=16, default block size, alternating; time and file length of both.  The 16-bit
+stream is twice as long, so about twice the time is the figure to compare with."""
 import os, sys; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import io, statistics, time, numpy as np, torch
 from PIL import Image
@@ -18,6 +23,7 @@ from transformerupscaler_amd import _lib, ops
 
 assert torch.cuda.is_available(), "this measurement needs the GPU"
 dev = "cuda"
+BITS16 = "--bits16" in sys.argv[1:]
 BLOCKS = (4096, 16384, 32768)
 ADAPTIVE = ops.PNG_FILTERS["adaptive"]
 
@@ -70,6 +76,20 @@ def wall(fn, runs):
 
 
 print(f"default block_bytes = {ops.PNG_BLOCK_BYTES}", flush=True)
+if BITS16:
+    h, w = 2160, 3840
+    for kind in ("smooth", "natural"):
+        x8 = ops.frames_to_tensor(torch.from_numpy(content(h, w, kind)).to(dev)[None])
+        x = (x8 + torch.rand(x8.shape, device=dev, generator=torch.Generator(device=dev).manual_seed(1)) / 255.0).clamp_(0.0, 1.0)
+        out = {b: (torch.empty((1, ops.png_max_bytes(h, w, bits=b)), dtype=torch.uint8, device=dev), torch.empty((1,), dtype=torch.int32, device=dev))
+               for b in (8, 16)}
+        res = alternate({b: (lambda b=b: ops.png_encode(x, out=out[b], bits=b)) for b in (8, 16)}, n=3)
+        size = {b: int(out[b][1][0]) for b in (8, 16)}
+        for b in (8, 16):
+            show(f"{h} x {w}, {kind} + dither, ops.png_encode(fp32, out=..., bits={b}), four launches", res[b], extra=f"  file {size[b] / 1e6:.2f} MB")
+        print(f"{h} x {w}, {kind} + dither: 16 / 8 bits = {statistics.median(res[16]) / statistics.median(res[8]):.2f} x the time, "
+              f"{size[16] / size[8]:.2f} x the bytes", flush=True)
+    sys.exit(0)
 for h, w in ((2160, 3840), (4320, 7680)):
     for kind in ("smooth", "natural"):
         host = content(h, w, kind)

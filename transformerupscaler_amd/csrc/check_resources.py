@@ -56,6 +56,8 @@ GUARDED = [
     # no counted hand-off: byte work at 13.5 B of memory traffic per pixel whose small per-lane tables (3 x 3 chroma pairs, 2 x 3 x 5
     # quantised bytes) are indexed by unrolled loops; a build that indexes them dynamically puts them in scratch
     ("image_io.hip", ["nv12_to_f32chw_kernel", "f32chw_to_nv12_kernel"]),
+    # ... and their 10-bit twins at 15 B per pixel, same tables, same reasoning
+    ("p010.hip", ["p010_to_f32chw_kernel", "f32chw_to_p010_kernel"]),
     # no counted hand-off: four 8-point DCT passes hold 8 values a lane in unrolled arrays; a build that indexes them dynamically spills
     ("degrade.hip", ["degrade_lr_kernel"]),
     # no counted hand-off: the DCT passes hold 8 values a lane in unrolled arrays, and the coder's zigzag walk is a loop over LDS; scratch
@@ -70,6 +72,8 @@ GUARDED = [
     # no counted hand-off: the Huffman builder, the header's run-length coder and the byte walks index LDS arrays only; a build that moves
     # one of them into a private array puts scratch latency into the one lane the whole workgroup waits for
     ("png_encode.hip", ["png_filter_kernel", "png_block_kernel", "png_scan_kernel"]),
+    # ... and the same templates (png_kernels.h) instantiated for the two-byte samples of 16-bit files
+    ("png16_encode.hip", ["png_filter_kernel", "png_block_kernel"]),
 ]
 # (source file, mangled-name fragment, registers): instantiations that must also stay within a register budget (VGPRs + AGPRs)
 REG_BUDGET = [

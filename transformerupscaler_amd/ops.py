@@ -995,14 +995,22 @@ def tensor_to_frames(x, bgr=False):
     return out
 
 
-# ---- NV12 video frames (YUV 4:2:0: what a decoder hands over and an encoder takes; definition in DESIGN 3, "NV12 frames") ----
+# ---- NV12 / P010 video frames (YUV 4:2:0 in 8 and 10 bits: what a decoder hands over and an encoder takes; definitions in DESIGN 3,
+# "NV12 frames" and "P010 frames").  One set of helpers for both: a format is its sample dtype, its matrices and its two C entries ----
 _NV12_MATRIX = {"bt601": 0, "bt709": 1}
+_P010_MATRIX = {"bt601": 0, "bt709": 1, "bt2020": 2}          # bt2020 (non-constant luminance) exists for P010 only
+_NV12 = ("NV12", torch.uint8, _NV12_MATRIX, "tup_nv12_to_f32chw", "tup_f32chw_to_nv12")
+_P010 = ("P010", torch.uint16, _P010_MATRIX, "tup_p010_to_f32chw", "tup_f32chw_to_p010")
 
 
-def _nv12_matrix(op, matrix):
-    if matrix not in _NV12_MATRIX:
-        raise ValueError(f"{op}: matrix must be 'bt601' or 'bt709', got {matrix!r}")
-    return _NV12_MATRIX[matrix]
+def _dtype_name(dtype):
+    return str(dtype).split(".")[-1]
+
+
+def _nv12_matrix(op, matrix, table=_NV12_MATRIX):
+    if matrix not in table:
+        raise ValueError(f"{op}: matrix must be {' or '.join(repr(m) for m in table)}, got {matrix!r}")
+    return table[matrix]
 
 
 def _nv12_on_gpu(op, t, name):
@@ -1013,11 +1021,12 @@ def _nv12_on_gpu(op, t, name):
         raise ValueError(f"{op}: {name} lives on {t.device} but the current device is cuda:{_cur_dev()}")
 
 
-def _nv12_plane(op, t, name, tail):
-    """A plane of an NV12 surface as (data_ptr, B, rows, row bytes, pitch, batch stride): uint8 on the current GPU, [B] + rows + `tail`
-    dimensions with the tail contiguous and one stride per row and per frame, which is what a slice of a pitched surface has."""
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
-        raise TypeError(f"{op}: {name} must be a uint8 tensor, got {getattr(t, 'dtype', type(t))}")
+def _nv12_plane(op, t, name, tail, dtype=torch.uint8):
+    """A plane of an NV12 / P010 surface as (data_ptr, B, rows, row samples, pitch, batch stride), pitch and stride in bytes: `dtype`
+    on the current GPU, [B] + rows + `tail` dimensions with the tail contiguous and one stride per row and per frame, which is what a
+    slice of a pitched surface has."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise TypeError(f"{op}: {name} must be a {_dtype_name(dtype)} tensor, got {getattr(t, 'dtype', type(t))}")
     if t.dim() not in (1 + tail, 2 + tail):
         raise ValueError(f"{op}: {name} must have {1 + tail} dimensions (one frame) or {2 + tail} (a batch), got shape {tuple(t.shape)}")
     _nv12_on_gpu(op, t, name)
@@ -1033,17 +1042,18 @@ def _nv12_plane(op, t, name, tail):
     inner = (st[2] == 1 or width <= 1) if tail == 1 else ((st[3] == 1 and st[2] == 2) or width <= 2)
     if not inner:
         raise ValueError(f"{op}: {name}: the innermost dimension{'s' if tail == 2 else ''} must be contiguous, got strides {tuple(st)}")
-    pitch = int(st[1]) if rows > 1 else width
-    if pitch < width or pitch >= 2 ** 31:
-        raise ValueError(f"{op}: {name}: row stride {pitch} must be at least the row's {width} bytes (and below 2^31)")
-    return t.data_ptr(), B, rows, width, pitch, (int(st[0]) if B > 1 else 0)
+    esize = t.element_size()
+    pitch = (int(st[1]) if rows > 1 else width) * esize
+    if pitch < width * esize or pitch >= 2 ** 31:
+        raise ValueError(f"{op}: {name}: row stride {pitch} must be at least the row's {width * esize} bytes (and below 2^31)")
+    return t.data_ptr(), B, rows, width, pitch, (int(st[0]) * esize if B > 1 else 0)
 
 
-def _nv12_geometry(op, y, uv):
-    yp, B, H, W, ypitch, ybs = _nv12_plane(op, y, "y", 1)
-    up, Bu, h2, w2x2, upitch, ubs = _nv12_plane(op, uv, "uv", 2)
+def _nv12_geometry(op, y, uv, fmt=_NV12):
+    yp, B, H, W, ypitch, ybs = _nv12_plane(op, y, "y", 1, fmt[1])
+    up, Bu, h2, w2x2, upitch, ubs = _nv12_plane(op, uv, "uv", 2, fmt[1])
     if H % 2 or W % 2:
-        raise ValueError(f"{op}: y is {H} x {W}; NV12 needs an even height and width")
+        raise ValueError(f"{op}: y is {H} x {W}; {fmt[0]} needs an even height and width")
     if (Bu, h2, w2x2) != (B, H // 2, W):
         raise ValueError(f"{op}: uv must be [{B}][{H // 2}][{W // 2}][2] for a y of [{B}][{H}][{W}], got {tuple(uv.shape)}")
     if B > 65535:
@@ -1051,61 +1061,96 @@ def _nv12_geometry(op, y, uv):
     return yp, up, ybs, ypitch, ubs, upitch, B, H, W
 
 
+def _yuv420_planes(op, fmt, buf, H, W):
+    H, W = int(H), int(W)
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"{op}: H = {H} and W = {W} must be even and at least 2")
+    if not isinstance(buf, torch.Tensor) or buf.dtype != fmt[1]:
+        raise TypeError(f"{op}: buf must be a {_dtype_name(fmt[1])} tensor, got {getattr(buf, 'dtype', type(buf))}")
+    if buf.dim() not in (2, 3) or buf.shape[-2] < H + H // 2 or buf.shape[-1] < W:
+        raise ValueError(f"{op}: buf must be [{H + H // 2}][>= {W}] (or a batch of those), got shape {tuple(buf.shape)}")
+    if buf.stride(-1) != 1:
+        raise ValueError(f"{op}: buf: the innermost dimension must be contiguous, got strides {tuple(buf.stride())}")
+    return buf[..., :H, :W], buf[..., H:H + H // 2, :W].unflatten(-1, (W // 2, 2))
+
+
+def _yuv420_to_tensor(op, fmt, y, uv, matrix, full_range):
+    m = _nv12_matrix(op, matrix, fmt[2])
+    yp, up, ybs, ypitch, ubs, upitch, B, H, W = _nv12_geometry(op, y, uv, fmt)
+    out = torch.empty((B, 3, H, W), dtype=F32, device=y.device)
+    _lib.call(fmt[3], yp, up, ybs, ypitch, ubs, upitch, out.data_ptr(), B, H, W, m, int(bool(full_range)), _stream())
+    return out
+
+
+def _tensor_to_yuv420(op, fmt, x, matrix, full_range, out):
+    m = _nv12_matrix(op, matrix, fmt[2])
+    if not isinstance(x, torch.Tensor) or x.dtype != F32:
+        raise TypeError(f"{op}: x must be a float32 tensor, got {getattr(x, 'dtype', type(x))}")
+    if x.dim() == 3:
+        x = x.unsqueeze(0)
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"{op}: x must be [B][3][H][W], got shape {tuple(x.shape)}")
+    B, _, H, W = (int(v) for v in x.shape)
+    if H % 2 or W % 2:
+        raise ValueError(f"{op}: x is {H} x {W}; {fmt[0]} needs an even height and width")
+    _nv12_on_gpu(op, x, "x")
+    xp = _chk(x, F32, None, f"{op}: x")
+    if out is None:
+        y = torch.empty((B, H, W), dtype=fmt[1], device=x.device)
+        uv = torch.empty((B, H // 2, W // 2, 2), dtype=fmt[1], device=x.device)
+    else:
+        y, uv = out
+    yp, up, ybs, ypitch, ubs, upitch, Bo, Ho, Wo = _nv12_geometry(f"{op}: out", y, uv, fmt)
+    if (Bo, Ho, Wo) != (B, H, W):
+        raise ValueError(f"{op}: out is for [{Bo}][{Ho}][{Wo}] frames, x is [{B}][3][{H}][{W}]")
+    row = W * y.element_size()
+    if B > 1 and (ybs < (H - 1) * ypitch + row or ubs < (H // 2 - 1) * upitch + row):
+        raise ValueError(f"{op}: out: the frames of a plane overlap (batch stride below one frame)")
+    _lib.call(fmt[4], xp, yp, up, ybs, ypitch, ubs, upitch, B, H, W, m, int(bool(full_range)), _stream())
+    return y, uv
+
+
 def nv12_planes(buf, H, W):
     """The (y, uv) views of single-buffer NV12 frames: buf uint8 [3H/2 or more][pitch] or [B][...][pitch] with the Y rows on top and
     the rows of (Cb, Cr) pairs below them -> y [..][H][W], uv [..][H/2][W/2][2].  No copy; rows beyond 3H/2 and bytes beyond W are
     padding."""
-    H, W = int(H), int(W)
-    if H < 2 or W < 2 or H % 2 or W % 2:
-        raise ValueError(f"nv12_planes: H = {H} and W = {W} must be even and at least 2")
-    if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8:
-        raise TypeError(f"nv12_planes: buf must be a uint8 tensor, got {getattr(buf, 'dtype', type(buf))}")
-    if buf.dim() not in (2, 3) or buf.shape[-2] < H + H // 2 or buf.shape[-1] < W:
-        raise ValueError(f"nv12_planes: buf must be [{H + H // 2}][>= {W}] (or a batch of those), got shape {tuple(buf.shape)}")
-    if buf.stride(-1) != 1:
-        raise ValueError(f"nv12_planes: buf: the innermost dimension must be contiguous, got strides {tuple(buf.stride())}")
-    return buf[..., :H, :W], buf[..., H:H + H // 2, :W].unflatten(-1, (W // 2, 2))
+    return _yuv420_planes("nv12_planes", _NV12, buf, H, W)
 
 
 def nv12_to_tensor(y, uv, matrix="bt709", full_range=False):
     """NV12 frames on the GPU -> fp32 [B][3][H][W] RGB in [0, 1], bit-exact "convert to RGB24, then ToTensor" under the integer
     definition of DESIGN 3.  y uint8 [B][H][W] (or [H][W]), uv uint8 [B][H/2][W/2][2] (or [H/2][W/2][2]) = (Cb, Cr), chroma sited
     left; any views with contiguous rows and uniform row / batch strides, e.g. the two halves of `nv12_planes`."""
-    m = _nv12_matrix("nv12_to_tensor", matrix)
-    yp, up, ybs, ypitch, ubs, upitch, B, H, W = _nv12_geometry("nv12_to_tensor", y, uv)
-    out = torch.empty((B, 3, H, W), dtype=F32, device=y.device)
-    _lib.call("tup_nv12_to_f32chw", yp, up, ybs, ypitch, ubs, upitch, out.data_ptr(), B, H, W, m, int(bool(full_range)), _stream())
-    return out
+    return _yuv420_to_tensor("nv12_to_tensor", _NV12, y, uv, matrix, full_range)
 
 
 def tensor_to_nv12(x, matrix="bt709", full_range=False, out=None):
     """fp32 [B][3][H][W] (or [3][H][W]) -> NV12 frames (y uint8 [B][H][W], uv uint8 [B][H/2][W/2][2]): bytes as `tensor_to_frames`
     makes them, then the integer matrix and the [1 2 1] x [1 1] chroma filter of DESIGN 3.  out=(y, uv) writes into such views
     (e.g. of a pitched surface; padding bytes are left alone)."""
-    m = _nv12_matrix("tensor_to_nv12", matrix)
-    if not isinstance(x, torch.Tensor) or x.dtype != F32:
-        raise TypeError(f"tensor_to_nv12: x must be a float32 tensor, got {getattr(x, 'dtype', type(x))}")
-    if x.dim() == 3:
-        x = x.unsqueeze(0)
-    if x.dim() != 4 or x.shape[1] != 3:
-        raise ValueError(f"tensor_to_nv12: x must be [B][3][H][W], got shape {tuple(x.shape)}")
-    B, _, H, W = (int(v) for v in x.shape)
-    if H % 2 or W % 2:
-        raise ValueError(f"tensor_to_nv12: x is {H} x {W}; NV12 needs an even height and width")
-    _nv12_on_gpu("tensor_to_nv12", x, "x")
-    xp = _chk(x, F32, None, "tensor_to_nv12: x")
-    if out is None:
-        y = torch.empty((B, H, W), dtype=torch.uint8, device=x.device)
-        uv = torch.empty((B, H // 2, W // 2, 2), dtype=torch.uint8, device=x.device)
-    else:
-        y, uv = out
-    yp, up, ybs, ypitch, ubs, upitch, Bo, Ho, Wo = _nv12_geometry("tensor_to_nv12: out", y, uv)
-    if (Bo, Ho, Wo) != (B, H, W):
-        raise ValueError(f"tensor_to_nv12: out is for [{Bo}][{Ho}][{Wo}] frames, x is [{B}][3][{H}][{W}]")
-    if B > 1 and (ybs < (H - 1) * ypitch + W or ubs < (H // 2 - 1) * upitch + W):
-        raise ValueError("tensor_to_nv12: out: the frames of a plane overlap (batch stride below one frame)")
-    _lib.call("tup_f32chw_to_nv12", xp, yp, up, ybs, ypitch, ubs, upitch, B, H, W, m, int(bool(full_range)), _stream())
-    return y, uv
+    return _tensor_to_yuv420("tensor_to_nv12", _NV12, x, matrix, full_range, out)
+
+
+def p010_planes(buf, H, W):
+    """The (y, uv) views of single-buffer P010 frames: buf uint16 [3H/2 or more][pitch] or [B][...][pitch] (pitch in samples) with the
+    Y rows on top and the rows of (Cb, Cr) pairs below them -> y [..][H][W], uv [..][H/2][W/2][2].  No copy; rows beyond 3H/2 and
+    samples beyond W are padding."""
+    return _yuv420_planes("p010_planes", _P010, buf, H, W)
+
+
+def p010_to_tensor(y, uv, matrix="bt709", full_range=False):
+    """P010 frames (10-bit YUV 4:2:0) on the GPU -> fp32 [B][3][H][W] RGB in [0, 1] = 10-bit code / 1023, bit-exact with the integer
+    definition of DESIGN 3 ("P010 frames"); never through 8 bits.  y uint16 [B][H][W] (or [H][W]), uv uint16 [B][H/2][W/2][2] (or
+    [H/2][W/2][2]) = (Cb, Cr); a sample carries its code in the high ten bits and the low six are ignored.  matrix 'bt601', 'bt709' or
+    'bt2020'; the transfer function is not touched (PQ / HLG code values pass through; the model was trained on SDR)."""
+    return _yuv420_to_tensor("p010_to_tensor", _P010, y, uv, matrix, full_range)
+
+
+def tensor_to_p010(x, matrix="bt709", full_range=False, out=None):
+    """fp32 [B][3][H][W] (or [3][H][W]) -> P010 frames (y uint16 [B][H][W], uv uint16 [B][H/2][W/2][2]): codes q_10(x) =
+    (int)(clamp(x * 1023, 0, 1023) + 0.5), NaN -> 0 (round to nearest, where the 8-bit paths truncate), then the integer matrix and
+    the [1 2 1] x [1 1] chroma filter of DESIGN 3; samples are code << 6.  out=(y, uv) writes into such views (padding is left alone)."""
+    return _tensor_to_yuv420("tensor_to_p010", _P010, x, matrix, full_range, out)
 
 
 # ---- branch A in training through its composition (csrc/branch_a_train.hip), r = 2 ----
@@ -1546,27 +1591,38 @@ PNG_MIN_BLOCK, PNG_MAX_BLOCK = 256, 32768
 PNG_BLOCK_BYTES = 16384                          # the default range of the filtered stream one workgroup codes (DESIGN 7m has the measurement)
 
 
-def _png_params(op, H, W, block_bytes):
-    """the number of deflate blocks after every check on the geometry"""
+def _png_bps(op, bits):
+    """bytes per sample of a file of `bits` bits"""
+    if isinstance(bits, bool) or bits not in (8, 16):
+        raise ValueError(f"{op}: bits must be 8 or 16, got {bits!r}")
+    return bits // 8
+
+
+def _png_params(op, H, W, block_bytes, bps=1):
+    """the number of deflate blocks after every check on the geometry; a row is 1 + 3 bps W filtered bytes"""
     if isinstance(block_bytes, bool) or not isinstance(block_bytes, int) or not PNG_MIN_BLOCK <= block_bytes <= PNG_MAX_BLOCK:
         raise ValueError(f"{op}: block_bytes must be an integer in {PNG_MIN_BLOCK}..{PNG_MAX_BLOCK}, got {block_bytes!r}")
     if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, int) or not isinstance(W, int) or H < 1 or W < 1:
         raise ValueError(f"{op}: an image is at least 1 x 1, got {H!r} x {W!r}")
-    if H * (1 + 3 * W) >= 2 ** 31:
-        raise ValueError(f"{op}: {H} x {W} has a filtered stream of {H * (1 + 3 * W)} bytes (below 2^31)")
-    return -(-(H * (1 + 3 * W)) // block_bytes)
+    if H * (1 + 3 * bps * W) >= 2 ** 31:
+        raise ValueError(f"{op}: {H} x {W} has a filtered stream of {H * (1 + 3 * bps * W)} bytes (below 2^31)")
+    return -(-(H * (1 + 3 * bps * W)) // block_bytes)
 
 
-def png_max_bytes(H, W, block_bytes=PNG_BLOCK_BYTES):
-    """The length of the file whose blocks are all stored: no file of `png_encode` for this geometry is longer, so rows of this many
-    bytes always fit (`out=`)."""
-    N = _png_params("png_max_bytes", H, W, block_bytes)
-    return 33 + 2 + H * (1 + 3 * W) + (12 + 5) * N + 16 + 12
+def png_max_bytes(H, W, block_bytes=PNG_BLOCK_BYTES, bits=8):
+    """The length of the file whose blocks are all stored: no file of `png_encode` for this geometry and depth is longer, so rows of
+    this many bytes always fit (`out=`)."""
+    bps = _png_bps("png_max_bytes", bits)
+    N = _png_params("png_max_bytes", H, W, block_bytes, bps)
+    return 33 + 2 + H * (1 + 3 * bps * W) + (12 + 5) * N + 16 + 12
 
 
-def png_encode(frames, filter="adaptive", block_bytes=PNG_BLOCK_BYTES, out=None):
+def png_encode(frames, filter="adaptive", block_bytes=PNG_BLOCK_BYTES, out=None, bits=8):
     """PNG files (8-bit RGB, no interlace) of a batch, made on the GPU.  frames: uint8 [B][H][W][3] (or [H][W][3]) RGB, or fp32
-    [B][3][H][W] quantised as `tensor_to_frames` does, trunc(clamp(x * 255, 0, 255)), inside the kernels.  filter: "adaptive" (per row,
+    [B][3][H][W] quantised as `tensor_to_frames` does, trunc(clamp(x * 255, 0, 255)), inside the kernels.  bits=16 writes 16-bit files
+    (IHDR depth 16, samples big-endian, rows of 1 + 6 W filtered bytes, everything else as below; tests/_png16_ref.py states them):
+    frames uint16 [B][H][W][3] (or [H][W][3]), or fp32 [B][3][H][W] quantised inside the kernels by q_16 = (int)(clamp(x * 65535, 0,
+    65535) + 0.5), NaN -> 0, which rounds to nearest; uint8 frames are refused (widen them yourself: v * 257).  filter: "adaptive" (per row,
     the filter with the smallest sum of |residual|) or one of "none", "sub", "up", "average", "paeth" for every row.  The filtered
     stream is cut every `block_bytes` bytes (256..32768) into deflate blocks (literals and runs, the shortest of stored / fixed /
     dynamic Huffman), one IDAT chunk each; the file is byte for byte what tests/_png_ref.py states and does not depend on B or `out`.
@@ -1574,13 +1630,16 @@ def png_encode(frames, filter="adaptive", block_bytes=PNG_BLOCK_BYTES, out=None)
     (the call's one host synchronisation) and `data` is allocated to the longest file.  out=(data, lengths): nothing synchronises; an
     image longer than data's row gets length -1 and none of its bytes (`png_max_bytes` always fits).  Everything is validated before
     any launch."""
-    if not isinstance(frames, torch.Tensor) or frames.dtype not in (torch.uint8, F32):
-        raise TypeError(f"png_encode: frames must be a uint8 or float32 tensor, got {getattr(frames, 'dtype', type(frames))}")
-    if frames.dtype == torch.uint8:
+    bps = _png_bps("png_encode", bits)
+    idt = torch.uint8 if bps == 1 else torch.uint16
+    if not isinstance(frames, torch.Tensor) or frames.dtype not in (idt, F32):
+        raise TypeError(f"png_encode: frames must be a {_dtype_name(idt)} or float32 tensor{'' if bps == 1 else ' for bits=16'}, "
+                        f"got {getattr(frames, 'dtype', type(frames))}")
+    if frames.dtype == idt:
         if frames.dim() == 3:
             frames = frames.unsqueeze(0)
         if frames.dim() != 4 or frames.shape[3] != 3:
-            raise ValueError(f"png_encode: uint8 frames must be [B][H][W][3] or [H][W][3], got shape {tuple(frames.shape)}")
+            raise ValueError(f"png_encode: {_dtype_name(idt)} frames must be [B][H][W][3] or [H][W][3], got shape {tuple(frames.shape)}")
         B, H, W = (int(v) for v in frames.shape[:3])
     else:
         if frames.dim() != 4 or frames.shape[1] != 3:
@@ -1591,7 +1650,7 @@ def png_encode(frames, filter="adaptive", block_bytes=PNG_BLOCK_BYTES, out=None)
     if not isinstance(filter, str) or filter not in PNG_FILTERS:
         raise ValueError(f"png_encode: filter must be one of {', '.join(PNG_FILTERS)}, got {filter!r}")
     ft = PNG_FILTERS[filter]
-    N = _png_params("png_encode", H, W, block_bytes)
+    N = _png_params("png_encode", H, W, block_bytes, bps)
     if not frames.is_contiguous():
         raise ValueError("png_encode: frames must be contiguous")
     if out is not None:
@@ -1609,30 +1668,31 @@ def png_encode(frames, filter="adaptive", block_bytes=PNG_BLOCK_BYTES, out=None)
         _nv12_on_gpu("png_encode", data, "out[0]")
         _nv12_on_gpu("png_encode", lengths, "out[1]")
     dev = frames.device
-    u8 = frames.data_ptr() if frames.dtype == torch.uint8 else None
+    u8 = frames.data_ptr() if frames.dtype == idt else None             # the integer frames: uint8, or uint16 for bits=16
+    e = "tup_png_" if bps == 1 else "tup_png16_"
     f32 = frames.data_ptr() if frames.dtype == F32 else None
     work = torch.empty((3, B, N), dtype=torch.int32, device=dev)            # sizes, offsets, Adler partials
     adlers = torch.empty((B,), dtype=torch.int32, device=dev)
-    if _lib.load().tup_png_blocks(H, W, block_bytes) != N:
+    if getattr(_lib.load(), e + "blocks")(H, W, block_bytes) != N:
         raise RuntimeError("png_encode: the library counts other blocks than the binding")
     rows = None
     if ft == PNG_FILTERS["adaptive"]:
         rows = torch.empty((B, H), dtype=torch.uint8, device=dev)
-        _lib.call("tup_png_filters", u8, f32, B, H, W, rows.data_ptr(), _stream())
+        _lib.call(e + "filters", u8, f32, B, H, W, rows.data_ptr(), _stream())
     rows_ptr = rows.data_ptr() if rows is not None else None
-    _lib.call("tup_png_sizes", u8, f32, B, H, W, ft, block_bytes, rows_ptr, work[0].data_ptr(), work[2].data_ptr(), _stream())
+    _lib.call(e + "sizes", u8, f32, B, H, W, ft, block_bytes, rows_ptr, work[0].data_ptr(), work[2].data_ptr(), _stream())
     if out is None:
         lengths = torch.empty((B,), dtype=torch.int32, device=dev)
-        _lib.call("tup_png_offsets", work[0].data_ptr(), work[2].data_ptr(), B, H, W, block_bytes, 2 ** 31 - 1, work[1].data_ptr(),
+        _lib.call(e + "offsets", work[0].data_ptr(), work[2].data_ptr(), B, H, W, block_bytes, 2 ** 31 - 1, work[1].data_ptr(),
                   lengths.data_ptr(), adlers.data_ptr(), _stream())
         host = lengths.cpu().tolist()                                   # the one synchronisation
         if min(host) < 0:
             raise RuntimeError("png_encode: a file of 2 GiB or more")
         data = torch.empty((B, max(host)), dtype=torch.uint8, device=dev)
     else:
-        _lib.call("tup_png_offsets", work[0].data_ptr(), work[2].data_ptr(), B, H, W, block_bytes, int(data.shape[1]), work[1].data_ptr(),
+        _lib.call(e + "offsets", work[0].data_ptr(), work[2].data_ptr(), B, H, W, block_bytes, int(data.shape[1]), work[1].data_ptr(),
                   lengths.data_ptr(), adlers.data_ptr(), _stream())
-    _lib.call("tup_png_write", u8, f32, B, H, W, ft, block_bytes, rows_ptr, work[1].data_ptr(), lengths.data_ptr(), adlers.data_ptr(),
+    _lib.call(e + "write", u8, f32, B, H, W, ft, block_bytes, rows_ptr, work[1].data_ptr(), lengths.data_ptr(), adlers.data_ptr(),
               data.data_ptr(), int(data.shape[1]), _stream())
     return data, lengths
 
