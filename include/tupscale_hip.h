@@ -431,7 +431,8 @@ int tup_f32chw_to_u8hwc(const float* src, void* dst, int B, int H, int W, int sw
  *           Y = clip8((ry R + gy G + by B + (yoff << 16) + 32768) >> 16), chroma from the [1 2 1] x [1 1] filter around
  *           column 2i of rows 2j, 2j+1 (columns clamped to the image).  Bytes between W and the pitch are left untouched.
  * One launch each, no allocation, synchronisation or host read (capturable into a hipGraph).  B <= 65535; an empty shape
- * returns 0; odd H or W, a pitch below W, or an unknown matrix / full_range returns hipErrorInvalidValue before any launch. */
+ * returns 0; odd H or W, a pitch below W, a null pointer, or an unknown matrix / full_range returns hipErrorInvalidValue before any
+ * launch. */
 int tup_nv12_to_f32chw(const void* y, const void* uv, long long y_batch_stride, int y_pitch,
                        long long uv_batch_stride, int uv_pitch, float* dst,
                        int B, int H, int W, int matrix, int full_range, void* stream);

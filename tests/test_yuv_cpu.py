@@ -157,6 +157,13 @@ def test_bad_geometry_is_refused_on_the_host():
                                    (4, 4, 4, 4, 2, 0, 1), (4, 4, 4, 4, 1, 2, 1), (4, 4, 4, 4, 1, 0, 65536)]:
         assert lib.tup_nv12_to_f32chw(None, None, 24, yp, 24, up, None, B, H, W, m, fr, None) == inval
         assert lib.tup_f32chw_to_nv12(None, None, None, 24, yp, 24, up, B, H, W, m, fr, None) == inval
+    a = 1 << 12                                                             # any non-null address: the checks fail before it is used
+    assert lib.tup_nv12_to_f32chw(None, a, 24, 4, 24, 4, a, 1, 4, 4, 1, 0, None) == inval            # a null pointer with good geometry
+    assert lib.tup_nv12_to_f32chw(a, None, 24, 4, 24, 4, a, 1, 4, 4, 1, 0, None) == inval
+    assert lib.tup_nv12_to_f32chw(a, a, 24, 4, 24, 4, None, 1, 4, 4, 1, 0, None) == inval
+    assert lib.tup_f32chw_to_nv12(None, a, a, 24, 4, 24, 4, 1, 4, 4, 1, 0, None) == inval
+    assert lib.tup_f32chw_to_nv12(a, None, a, 24, 4, 24, 4, 1, 4, 4, 1, 0, None) == inval
+    assert lib.tup_f32chw_to_nv12(a, a, None, 24, 4, 24, 4, 1, 4, 4, 1, 0, None) == inval
     assert lib.tup_nv12_to_f32chw(None, None, 0, 4, 0, 4, None, 0, 4, 4, 1, 0, None) == 0            # empty: nothing to do
     assert lib.tup_f32chw_to_nv12(None, None, None, 0, 4, 0, 4, 1, 0, 4, 1, 0, None) == 0
     y, uv = torch.zeros((4, 8), dtype=torch.uint8), torch.zeros((2, 4, 2), dtype=torch.uint8)

@@ -9,7 +9,8 @@ sizes (DESIGN 5b records exactly that for the whole-block kernel).  The Makefile
     check_resources.py build/*.remarks  ->  build/resource_usage.json, exit 1 if a guarded kernel reports scratch
 
 Diagnostic instantiations (the `STAMPS = true` builds, which spill by design and are never launched by the product path)
-are exempt.  The JSON also records the compiler version, which bench.py copies into its line.
+are exempt.  A GUARDED name or a REG_BUDGET fragment that matches no kernel of its source file (a rename that left the entry
+behind) fails the same way, for the source files that are part of the invocation.  The JSON also records the compiler version, which bench.py copies into its line.
 """
 import json
 import os
@@ -53,11 +54,11 @@ GUARDED = [
     # no counted vmcnt here, but the kernel lives on three waves per SIMD with every row's loads requested a row ahead: scratch reloads
     # queue behind those loads (seen in round 3).  All four instances (RESIZE x PARTS) sit at 133-152 registers of 168
     ("tail_stream.hip", ["tail_stream_r2_kernel"]),
-    # no counted hand-off: byte work at 13.5 B of memory traffic per pixel whose small per-lane tables (3 x 3 chroma pairs, 2 x 3 x 5
-    # quantised bytes) are indexed by unrolled loops; a build that indexes them dynamically puts them in scratch
-    ("image_io.hip", ["nv12_to_f32chw_kernel", "f32chw_to_nv12_kernel"]),
-    # ... and their 10-bit twins at 15 B per pixel, same tables, same reasoning
-    ("p010.hip", ["p010_to_f32chw_kernel", "f32chw_to_p010_kernel"]),
+    # no counted hand-off: the YUV 4:2:0 frame templates of yuv420_kernels.h, byte work at 13.5 B (NV12, image_io.hip) and 15 B (P010,
+    # p010.hip) of memory traffic per pixel whose small per-lane tables (3 x 3 chroma pairs, 2 x 3 x 5 quantised codes) are indexed by
+    # unrolled loops; a build that indexes them dynamically puts them in scratch
+    ("image_io.hip", ["yuv420_to_f32chw_kernel", "f32chw_to_yuv420_kernel"]),
+    ("p010.hip", ["yuv420_to_f32chw_kernel", "f32chw_to_yuv420_kernel"]),
     # no counted hand-off: four 8-point DCT passes hold 8 values a lane in unrolled arrays; a build that indexes them dynamically spills
     ("degrade.hip", ["degrade_lr_kernel"]),
     # no counted hand-off: the DCT passes hold 8 values a lane in unrolled arrays, and the coder's zigzag walk is a loop over LDS; scratch
@@ -122,7 +123,7 @@ def main(argv):
             out_path = a[6:]
         else:
             files.append(a)
-    report, bad, over, seen_budget = {}, [], [], set()
+    report, bad, over, seen_budget, seen_guarded = {}, [], [], set(), set()
     for f in sorted(files):
         src = os.path.basename(f).replace(".remarks", ".hip")
         recs = parse(f)
@@ -130,8 +131,9 @@ def main(argv):
         for mangled, rec in recs.items():
             nice = names.get(mangled, mangled)
             rec["source"] = src
-            guarded = any(src == gsrc and any(fn in mangled for fn in fns) for gsrc, fns in GUARDED) \
-                and not (EXEMPT.search(nice) or EXEMPT.search(mangled))
+            matched = {(gsrc, fn) for gsrc, fns in GUARDED for fn in fns if src == gsrc and fn in mangled}
+            seen_guarded |= matched
+            guarded = bool(matched) and not (EXEMPT.search(nice) or EXEMPT.search(mangled))
             rec["guarded_no_scratch"] = bool(guarded)
             report[nice] = rec
             if guarded and rec.get("scratch_bytes_per_lane", 0) > 0:
@@ -164,7 +166,10 @@ def main(argv):
     missing = [frag for bsrc, frag, _ in REG_BUDGET if bsrc in srcs and frag not in seen_budget]
     for frag in missing:
         sys.stderr.write(f"check_resources: no kernel matches the register-budget entry {frag}; correct the entry.\n")
-    if over or missing:
+    stale = [(gsrc, fn) for gsrc, fns in GUARDED for fn in fns if gsrc in srcs and (gsrc, fn) not in seen_guarded]
+    for gsrc, fn in stale:
+        sys.stderr.write(f"check_resources: no kernel of {gsrc} matches the guarded entry {fn}; correct the entry.\n")
+    if over or missing or stale:
         return 1
     n_guard = sum(1 for r in report.values() if r["guarded_no_scratch"])
     print(f"check_resources: {len(report)} kernels, {n_guard} guarded (scratch 0), compiler {compiler}")

@@ -6,6 +6,7 @@ on the caller's current HIP stream.
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes
 import re
@@ -997,23 +998,23 @@ def tensor_to_frames(x, bgr=False):
 
 # ---- NV12 / P010 video frames (YUV 4:2:0 in 8 and 10 bits: what a decoder hands over and an encoder takes; definitions in DESIGN 3,
 # "NV12 frames" and "P010 frames").  One set of helpers for both: a format is its sample dtype, its matrices and its two C entries ----
-_NV12_MATRIX = {"bt601": 0, "bt709": 1}
-_P010_MATRIX = {"bt601": 0, "bt709": 1, "bt2020": 2}          # bt2020 (non-constant luminance) exists for P010 only
-_NV12 = ("NV12", torch.uint8, _NV12_MATRIX, "tup_nv12_to_f32chw", "tup_f32chw_to_nv12")
-_P010 = ("P010", torch.uint16, _P010_MATRIX, "tup_p010_to_f32chw", "tup_f32chw_to_p010")
+_Yuv420 = collections.namedtuple("_Yuv420", "name dtype matrices decode encode")
+_NV12 = _Yuv420("NV12", torch.uint8, {"bt601": 0, "bt709": 1}, "tup_nv12_to_f32chw", "tup_f32chw_to_nv12")
+# bt2020 (non-constant luminance) exists for P010 only
+_P010 = _Yuv420("P010", torch.uint16, {"bt601": 0, "bt709": 1, "bt2020": 2}, "tup_p010_to_f32chw", "tup_f32chw_to_p010")
 
 
 def _dtype_name(dtype):
     return str(dtype).split(".")[-1]
 
 
-def _nv12_matrix(op, matrix, table=_NV12_MATRIX):
+def _yuv420_matrix(op, matrix, table):
     if matrix not in table:
         raise ValueError(f"{op}: matrix must be {' or '.join(repr(m) for m in table)}, got {matrix!r}")
     return table[matrix]
 
 
-def _nv12_on_gpu(op, t, name):
+def _on_current_gpu(op, t, name):
     if not t.is_cuda:
         raise ValueError(f"{op}: {name} lives on {t.device}; the HIP path needs a GPU tensor (no CPU fallback)")
     if t.device.index != _cur_dev():
@@ -1021,7 +1022,7 @@ def _nv12_on_gpu(op, t, name):
         raise ValueError(f"{op}: {name} lives on {t.device} but the current device is cuda:{_cur_dev()}")
 
 
-def _nv12_plane(op, t, name, tail, dtype=torch.uint8):
+def _yuv420_plane(op, t, name, tail, dtype):
     """A plane of an NV12 / P010 surface as (data_ptr, B, rows, row samples, pitch, batch stride), pitch and stride in bytes: `dtype`
     on the current GPU, [B] + rows + `tail` dimensions with the tail contiguous and one stride per row and per frame, which is what a
     slice of a pitched surface has."""
@@ -1029,7 +1030,7 @@ def _nv12_plane(op, t, name, tail, dtype=torch.uint8):
         raise TypeError(f"{op}: {name} must be a {_dtype_name(dtype)} tensor, got {getattr(t, 'dtype', type(t))}")
     if t.dim() not in (1 + tail, 2 + tail):
         raise ValueError(f"{op}: {name} must have {1 + tail} dimensions (one frame) or {2 + tail} (a batch), got shape {tuple(t.shape)}")
-    _nv12_on_gpu(op, t, name)
+    _on_current_gpu(op, t, name)
     if t.dim() == 1 + tail:
         t = t.unsqueeze(0)
     B, rows = int(t.shape[0]), int(t.shape[1])
@@ -1049,11 +1050,11 @@ def _nv12_plane(op, t, name, tail, dtype=torch.uint8):
     return t.data_ptr(), B, rows, width, pitch, (int(st[0]) * esize if B > 1 else 0)
 
 
-def _nv12_geometry(op, y, uv, fmt=_NV12):
-    yp, B, H, W, ypitch, ybs = _nv12_plane(op, y, "y", 1, fmt[1])
-    up, Bu, h2, w2x2, upitch, ubs = _nv12_plane(op, uv, "uv", 2, fmt[1])
+def _yuv420_geometry(op, y, uv, fmt):
+    yp, B, H, W, ypitch, ybs = _yuv420_plane(op, y, "y", 1, fmt.dtype)
+    up, Bu, h2, w2x2, upitch, ubs = _yuv420_plane(op, uv, "uv", 2, fmt.dtype)
     if H % 2 or W % 2:
-        raise ValueError(f"{op}: y is {H} x {W}; {fmt[0]} needs an even height and width")
+        raise ValueError(f"{op}: y is {H} x {W}; {fmt.name} needs an even height and width")
     if (Bu, h2, w2x2) != (B, H // 2, W):
         raise ValueError(f"{op}: uv must be [{B}][{H // 2}][{W // 2}][2] for a y of [{B}][{H}][{W}], got {tuple(uv.shape)}")
     if B > 65535:
@@ -1065,8 +1066,8 @@ def _yuv420_planes(op, fmt, buf, H, W):
     H, W = int(H), int(W)
     if H < 2 or W < 2 or H % 2 or W % 2:
         raise ValueError(f"{op}: H = {H} and W = {W} must be even and at least 2")
-    if not isinstance(buf, torch.Tensor) or buf.dtype != fmt[1]:
-        raise TypeError(f"{op}: buf must be a {_dtype_name(fmt[1])} tensor, got {getattr(buf, 'dtype', type(buf))}")
+    if not isinstance(buf, torch.Tensor) or buf.dtype != fmt.dtype:
+        raise TypeError(f"{op}: buf must be a {_dtype_name(fmt.dtype)} tensor, got {getattr(buf, 'dtype', type(buf))}")
     if buf.dim() not in (2, 3) or buf.shape[-2] < H + H // 2 or buf.shape[-1] < W:
         raise ValueError(f"{op}: buf must be [{H + H // 2}][>= {W}] (or a batch of those), got shape {tuple(buf.shape)}")
     if buf.stride(-1) != 1:
@@ -1075,15 +1076,15 @@ def _yuv420_planes(op, fmt, buf, H, W):
 
 
 def _yuv420_to_tensor(op, fmt, y, uv, matrix, full_range):
-    m = _nv12_matrix(op, matrix, fmt[2])
-    yp, up, ybs, ypitch, ubs, upitch, B, H, W = _nv12_geometry(op, y, uv, fmt)
+    m = _yuv420_matrix(op, matrix, fmt.matrices)
+    yp, up, ybs, ypitch, ubs, upitch, B, H, W = _yuv420_geometry(op, y, uv, fmt)
     out = torch.empty((B, 3, H, W), dtype=F32, device=y.device)
-    _lib.call(fmt[3], yp, up, ybs, ypitch, ubs, upitch, out.data_ptr(), B, H, W, m, int(bool(full_range)), _stream())
+    _lib.call(fmt.decode, yp, up, ybs, ypitch, ubs, upitch, out.data_ptr(), B, H, W, m, int(bool(full_range)), _stream())
     return out
 
 
 def _tensor_to_yuv420(op, fmt, x, matrix, full_range, out):
-    m = _nv12_matrix(op, matrix, fmt[2])
+    m = _yuv420_matrix(op, matrix, fmt.matrices)
     if not isinstance(x, torch.Tensor) or x.dtype != F32:
         raise TypeError(f"{op}: x must be a float32 tensor, got {getattr(x, 'dtype', type(x))}")
     if x.dim() == 3:
@@ -1092,21 +1093,21 @@ def _tensor_to_yuv420(op, fmt, x, matrix, full_range, out):
         raise ValueError(f"{op}: x must be [B][3][H][W], got shape {tuple(x.shape)}")
     B, _, H, W = (int(v) for v in x.shape)
     if H % 2 or W % 2:
-        raise ValueError(f"{op}: x is {H} x {W}; {fmt[0]} needs an even height and width")
-    _nv12_on_gpu(op, x, "x")
+        raise ValueError(f"{op}: x is {H} x {W}; {fmt.name} needs an even height and width")
+    _on_current_gpu(op, x, "x")
     xp = _chk(x, F32, None, f"{op}: x")
     if out is None:
-        y = torch.empty((B, H, W), dtype=fmt[1], device=x.device)
-        uv = torch.empty((B, H // 2, W // 2, 2), dtype=fmt[1], device=x.device)
+        y = torch.empty((B, H, W), dtype=fmt.dtype, device=x.device)
+        uv = torch.empty((B, H // 2, W // 2, 2), dtype=fmt.dtype, device=x.device)
     else:
         y, uv = out
-    yp, up, ybs, ypitch, ubs, upitch, Bo, Ho, Wo = _nv12_geometry(f"{op}: out", y, uv, fmt)
+    yp, up, ybs, ypitch, ubs, upitch, Bo, Ho, Wo = _yuv420_geometry(f"{op}: out", y, uv, fmt)
     if (Bo, Ho, Wo) != (B, H, W):
         raise ValueError(f"{op}: out is for [{Bo}][{Ho}][{Wo}] frames, x is [{B}][3][{H}][{W}]")
     row = W * y.element_size()
     if B > 1 and (ybs < (H - 1) * ypitch + row or ubs < (H // 2 - 1) * upitch + row):
         raise ValueError(f"{op}: out: the frames of a plane overlap (batch stride below one frame)")
-    _lib.call(fmt[4], xp, yp, up, ybs, ypitch, ubs, upitch, B, H, W, m, int(bool(full_range)), _stream())
+    _lib.call(fmt.encode, xp, yp, up, ybs, ypitch, ubs, upitch, B, H, W, m, int(bool(full_range)), _stream())
     return y, uv
 
 
@@ -1545,10 +1546,10 @@ def jpeg_encode(frames, quality=75, subsampling="4:2:0", restart_rows=1, out=Non
                              f"{tuple(getattr(lengths, 'shape', ()))}")
         if data.shape[1] >= 2 ** 31:
             raise ValueError(f"jpeg_encode: out[0] has rows of {data.shape[1]} bytes (below 2^31)")
-    _nv12_on_gpu("jpeg_encode", frames, "frames")
+    _on_current_gpu("jpeg_encode", frames, "frames")
     if out is not None:
-        _nv12_on_gpu("jpeg_encode", data, "out[0]")
-        _nv12_on_gpu("jpeg_encode", lengths, "out[1]")
+        _on_current_gpu("jpeg_encode", data, "out[0]")
+        _on_current_gpu("jpeg_encode", lengths, "out[1]")
     dev = frames.device
     u8 = frames.data_ptr() if frames.dtype == torch.uint8 else None
     f32 = frames.data_ptr() if frames.dtype == F32 else None
@@ -1663,10 +1664,10 @@ def png_encode(frames, filter="adaptive", block_bytes=PNG_BLOCK_BYTES, out=None,
                              f"{tuple(getattr(lengths, 'shape', ()))}")
         if data.shape[1] >= 2 ** 31:
             raise ValueError(f"png_encode: out[0] has rows of {data.shape[1]} bytes (below 2^31)")
-    _nv12_on_gpu("png_encode", frames, "frames")
+    _on_current_gpu("png_encode", frames, "frames")
     if out is not None:
-        _nv12_on_gpu("png_encode", data, "out[0]")
-        _nv12_on_gpu("png_encode", lengths, "out[1]")
+        _on_current_gpu("png_encode", data, "out[0]")
+        _on_current_gpu("png_encode", lengths, "out[1]")
     dev = frames.device
     u8 = frames.data_ptr() if frames.dtype == idt else None             # the integer frames: uint8, or uint16 for bits=16
     e = "tup_png_" if bps == 1 else "tup_png16_"
@@ -1951,7 +1952,7 @@ def jpeg_decode(files, to_tensor=False, out=None, index="auto"):
         if not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
             raise ValueError(f"jpeg_decode: out must be a contiguous {dtype} tensor of shape {shape}, got {getattr(out, 'dtype', type(out))} "
                              f"{tuple(getattr(out, 'shape', ()))}")
-        _nv12_on_gpu("jpeg_decode", out, "out")
+        _on_current_gpu("jpeg_decode", out, "out")
     elif not torch.cuda.is_available():
         raise RuntimeError("jpeg_decode: the HIP path needs a GPU (no CPU fallback)")
     dev = out.device if out is not None else torch.device("cuda", _cur_dev())
