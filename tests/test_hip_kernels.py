@@ -143,6 +143,7 @@ def test_gemm_tokens(dev, M, N, K):
 
 
 def test_window_attention(dev, det_sd):
+    """The bias map (every offset, every head) and the fragment layouts are checked bit for bit in tests/test_hip_attn_exact.py."""
     from transformerupscaler_amd import ops
     nwin = 5
     qkv = bf(rnd((nwin, 64, 576), 22, 1.5))

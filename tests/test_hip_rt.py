@@ -32,8 +32,9 @@ def test_strided_conv_via_space_to_depth():
     assert (got.float().cpu() - ref).abs().max() <= 1.5e-2 + 1e-2 * ref.abs().max()
 
 
-@pytest.mark.parametrize("B,N", [(1, 3600), (2, 200), (1, 64)])
+@pytest.mark.parametrize("B,N", [(1, 3600), (2, 200), (1, 64), (1, 1), (1, 17), (2, 65), (1, 257)])
 def test_rt_attention(B, N):
+    """Key tails, key placement and the split merge are checked bit for bit in tests/test_hip_attn_exact.py."""
     from transformerupscaler_amd import ops
     qkv = bf(rnd((B, N, 384), 4, 1.5))
     q, k, v = qkv.view(B, N, 3, 8, 16).permute(2, 0, 3, 1, 4)
@@ -89,7 +90,7 @@ def test_rt_rejects_other_sizes(rt_model):
             rt_model(torch.rand(1, 3, 540, 960).cuda())
 
 
-@pytest.mark.parametrize("B,N", [(1, 3600), (2, 200)])
+@pytest.mark.parametrize("B,N", [(1, 3600), (2, 200), (1, 1), (1, 17), (2, 65), (1, 257)])
 def test_rt_attention_backward(B, N):
     from transformerupscaler_amd import ops
     qkv = bf(rnd((B, N, 384), 14, 1.5)).requires_grad_(True)
