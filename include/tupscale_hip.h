@@ -767,6 +767,32 @@ int tup_png16_offsets(const int* sizes, const int* partials, int B, int H, int W
 int tup_png16_write(const void* frames_u16, const float* frames_f32, int B, int H, int W, int filter, int block_bytes, const void* filters,
                     const int* offsets, const int* lengths, const int* adlers, void* data, long long capacity, void* stream);
 
+/* PNG files (8 bits a sample, colour types 0, 2, 3, 4, 6, no interlace) of a whole batch decoded on the GPU (ops.png_decode;
+ * csrc/png_decode.hip).  The pixels of image b are what Pillow's Image.open(file).convert("RGB") returns: grey R = G = B,
+ * alpha dropped, palette looked up (an index past PLTE is black); tests/_png_decode_ref.py states it.  The caller walks the chunks
+ * (ops.png_parse) and passes `records`, B records of 784 bytes {int32 offset of the image's zlib stream in `streams` (a multiple of
+ * 16), int32 its length, int32 colour type, int32 bytes per pixel of the filtered stream (1, 3, 1, 2, 4 for the five types), the
+ * palette as 256 x 3 bytes, zero-filled}, and `streams`, streams_bytes bytes: every image's IDAT payloads joined without chunk
+ * framing, each image's area padded to a multiple of 16.  All images share H and W; `channels` is the most bytes per pixel of any of
+ * them and sizes the workspace.
+ *   tup_png_decode_inflate  workspace uint8 [B][ws_bytes] <- the filtered stream, H rows of 1 + bytes-per-pixel W bytes; status int32
+ *                           [B] <- 0 for a stream that inflates to exactly that many bytes with the right Adler-32, otherwise the
+ *                           first error in stream order: 1 block type 3, 2 stored LEN / NLEN, 3 a code RFC 1951 forbids, 4 bits that are
+ *                           no symbol's code, 5 a distance before the start, 6 input exhausted (or a record that points outside
+ *                           `streams`), 7 output too long, 8 output too short, 10 Adler-32 mismatch.  walk: 0 one token a round, 1 a
+ *                           wave of token candidates a round; frames and status are the same bits;
+ *   tup_png_decode_finish   exactly one of out_u8 (uint8 [B][H][W][3], RGB) and out_f32 (fp32 [B][3][H][W] = byte / 255) <- the
+ *                           pixels, filters undone; status <- 9 where it was 0 or 10 and a row's filter byte is above 4.
+ * The pixels of an image with a non-zero status are unspecified; nothing is read outside its stream or written outside its
+ * workspace and frame.  ws_bytes = tup_png_decode_workspace(H, W, channels) (returns a byte count, not an error code), or -1 for what
+ * the decoder refuses: H or W below 1, channels outside 1..4, H * (1 + 4 W) or ws_bytes from 2^31.  Those, another ws_bytes, B outside 1..65535,
+ * a walk outside 0..1, and both or neither of the outputs are hipErrorInvalidValue before any launch. */
+int tup_png_decode_workspace(int H, int W, int channels);
+int tup_png_decode_inflate(const void* records, const void* streams, long long streams_bytes, int B, int H, int W, int channels, int walk,
+                           void* workspace, long long ws_bytes, int* status, void* stream);
+int tup_png_decode_finish(const void* records, void* workspace, long long ws_bytes, int B, int H, int W, int channels, void* out_u8,
+                          float* out_f32, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

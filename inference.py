@@ -88,7 +88,27 @@ def parse_args(argv=None):
     p.add_argument("--png_bits", type=int, default=8, choices=(8, 16),
                    help="Bit depth of --out when it is a .png: 8 (default), or 16 for the model's fp32 output rounded to 16 bits; --inp and "
                         "bicubic.jpg are made from 8-bit frames and stay 8-bit")
+    p.epilog = "--png_decoder {host,gpu}: " + PNG_DECODER_HELP
     return p.parse_args(argv)
+
+
+PNG_DECODERS = ("host", "gpu")
+PNG_DECODER_HELP = "How a PNG --image_path is decoded: host (Pillow, default) or gpu (ops.png_decode: same pixels, slower for one file)"
+
+
+def png_decoder_parser():
+    """The parser of the one flag that is read ahead of `parse_args`, whose namespace stays the reference's flags plus the JPEG ones
+    and --png_bits (tests pin it)."""
+    p = argparse.ArgumentParser(add_help=False, allow_abbrev=False, prog="inference.py")
+    p.add_argument("--png_decoder", choices=PNG_DECODERS, default="host",
+                   help=PNG_DECODER_HELP)
+    return p
+
+
+def take_png_decoder(argv):
+    """``--png_decoder {host,gpu}`` taken out of the command line -> (the decoder, the other arguments)."""
+    known, rest = png_decoder_parser().parse_known_args(argv)
+    return known.png_decoder, rest
 
 
 def file_format(path):
@@ -96,8 +116,9 @@ def file_format(path):
     return "png" if os.path.splitext(path)[1].lower() == ".png" else "jpeg"
 
 
-def decode_image_named(path_or_bytes, device, gpu=True):
-    """(uint8 [H][W][3] RGB on the GPU, the decoder that made it).  A baseline JPEG is decoded there by ``ops.jpeg_decode``, whose
+def decode_image_named(path_or_bytes, device, gpu=True, png_decoder="host"):
+    """(uint8 [H][W][3] RGB on the GPU, the decoder that made it).  With png_decoder="gpu" a PNG that ``ops.png_parse`` accepts is
+    decoded by ``ops.png_decode`` ("gpu:png"; same pixels as Pillow's; a refused or damaged file goes to the host as before).  A baseline JPEG is decoded there by ``ops.jpeg_decode``, whose
     pixels are Pillow's: with restart markers (every file this driver writes) interval by interval ("gpu:restart-intervals"),
     without them through the self-synchronising index ("gpu:sync-index": ``index="sync"``, measured faster than the host for
     2160 x 3840 files).  Everything else (PNG, progressive JPEG, a damaged file), or everything with gpu=False, is one
@@ -120,6 +141,15 @@ def decode_image_named(path_or_bytes, device, gpu=True):
                 frames, status = ops.jpeg_decode(data, index=index)
             if int(status[0]) == 0:
                 return frames[0], "gpu:sync-index" if index == "sync" else "gpu:restart-intervals"
+        elif png_decoder == "gpu":
+            try:
+                with torch.cuda.device(device):
+                    frames, status = ops.png_decode(data)
+                if int(status[0]) == 0:
+                    return frames[0], "gpu:png"
+            except ValueError as e:                         # what ops.png_parse or ops.png_decode refuses: the host decodes it
+                import warnings
+                warnings.warn(f"inference.py: the PNG is decoded on the host ({e})")
         path_or_bytes = data
     src = io.BytesIO(path_or_bytes) if isinstance(path_or_bytes, (bytes, bytearray)) else path_or_bytes
     with Image.open(src) as im:
@@ -127,9 +157,9 @@ def decode_image_named(path_or_bytes, device, gpu=True):
     return torch.from_numpy(arr.copy()).to(device), "pillow"
 
 
-def decode_image(path_or_bytes, device, gpu=True):
+def decode_image(path_or_bytes, device, gpu=True, png_decoder="host"):
     """The frame of `decode_image_named`; the decoder's name rides on it as the attribute ``decoder``."""
-    frame, name = decode_image_named(path_or_bytes, device, gpu)
+    frame, name = decode_image_named(path_or_bytes, device, gpu, png_decoder)
     frame.decoder = name
     return frame
 
@@ -182,7 +212,8 @@ def run(args, device="cuda"):
             f.write(data)
         return data
 
-    original = decode_image(args.image_path, device)
+    # the keyword only where it was asked for: callers and tests that stand in for decode_image take (path, device)
+    original = decode_image(args.image_path, device, **({"png_decoder": "gpu"} if getattr(args, "png_decoder", "host") == "gpu" else {}))
     input_decoder = getattr(original, "decoder", None)
     lr_u8 = ops.resize_frames(original, res_in)[0] if res_in is not None else original
     files = {"inp": (args.inp, save(lr_u8, args.inp))}
@@ -222,7 +253,9 @@ def run(args, device="cuda"):
 
 
 def main(argv=None):
+    png_decoder, argv = take_png_decoder(argv)
     args = parse_args(argv)
+    args.png_decoder = png_decoder
     record = run(args)
     if args.json:
         with open(args.json, "w") as f:

@@ -117,6 +117,9 @@ def build_parser():
     p.add_argument("--val_images", type=int, default=None, help="Validate on the first K files of --val_dir in sorted order")
     p.add_argument("--val_both", action="store_true", help="With --ema_decay: score the raw weights as well as the averaged ones")
     p.add_argument("--keep_best", choices=("psnr", "ssim", "l1"), default=None, help="Keep best/model_epoch_<N>.pth by this validation metric")
+    p.add_argument("--png_decoder", choices=("host", "gpu"), default="host",
+                   help="host: Pillow decodes an image when it is first used (default); gpu: the training set and --val_dir are decoded "
+                        "into the cache before the first step, in batches, by ops.png_decode (same pixels)")
     return p
 
 
@@ -335,6 +338,12 @@ def run(args):
     else:
         pairs = parse_pairs(args.pairs) if args.pairs else SCALE_PAIRS
         dataset = PairDataset(args.data_dir, pairs, cache_bytes=cache_bytes, device=device)
+    if args.png_decoder == "gpu":                                         # same frames as the host decode, so same samples and losses
+        for cached in (dataset, val_set):
+            if cached is not None:
+                plan = getattr(cached, "plan", None)
+                cached.preload(None if plan is None else sorted({i for i, _ in plan}), decoder="gpu")
+                say(f"Preloaded {cached.gpu_decodes} images of {cached.image_dir} on the GPU ({cached.decodes} on the host)")
     criterion = None
     if not pure_l1(args):
         from transformerupscaler_amd.losses import QualityLoss

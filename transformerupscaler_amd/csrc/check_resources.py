@@ -75,6 +75,9 @@ GUARDED = [
     ("png_encode.hip", ["png_filter_kernel", "png_block_kernel", "png_scan_kernel"]),
     # ... and the same templates (png_kernels.h) instantiated for the two-byte samples of 16-bit files
     ("png16_encode.hip", ["png_filter_kernel", "png_block_kernel"]),
+    # no counted hand-off: one wave walks a zlib stream with its reader state, tables, input window and output ring in registers and LDS;
+    # scratch would put memory latency into every token.  The unfilter pass carries three pixels a lane through 64-step chunks
+    ("png_decode.hip", ["png_inflate_kernel", "png_finish_kernel"]),
 ]
 # (source file, mangled-name fragment, registers): instantiations that must also stay within a register budget (VGPRs + AGPRs)
 REG_BUDGET = [

@@ -59,6 +59,59 @@ def decode_png(path, device):
     return torch.from_numpy(arr.copy()).to(device)
 
 
+PNG_DECODERS = ("host", "gpu")
+PNG_GPU_BATCH = 64          # files per ops.png_decode call
+
+
+def decode_pngs(paths, device, decoder="host"):
+    """[uint8 [H][W][3] on the GPU] for a list of files: what `decode_png` returns for each.  decoder="host": that function, file by
+    file.  decoder="gpu": the files are grouped by (H, W) and decoded by `ops.png_decode` in batches of at most PNG_GPU_BATCH, the
+    status of a batch read back once; a file that `ops.png_parse` refuses (16-bit, interlaced, ...) or whose status is non-zero is
+    decoded on the host instead, with one warning that names it."""
+    return _decode_pngs(paths, device, decoder)[0]
+
+
+def _decode_pngs(paths, device, decoder):
+    """`decode_pngs` -> (frames, how many of them the host decoded)"""
+    if decoder not in PNG_DECODERS:
+        raise ValueError(f"decode_pngs: decoder must be one of {PNG_DECODERS}, got {decoder!r}")
+    paths = list(paths)
+    if decoder == "host":
+        return [decode_png(p, device) for p in paths], len(paths)
+    import warnings
+
+    import torch
+
+    from . import ops
+    frames, groups, on_host = [None] * len(paths), OrderedDict(), 0
+    for i, p in enumerate(paths):
+        with open(p, "rb") as f:
+            data = f.read()
+        try:
+            info = ops.png_parse(data)
+            if info["H"] * (1 + 4 * info["W"]) >= 2 ** 31:
+                raise ValueError(f"an image of {info['H']} x {info['W']}")
+        except ValueError as e:
+            warnings.warn(f"decode_pngs: {p!r} is decoded on the host ({e})")
+            frames[i] = decode_png(p, device)
+            on_host += 1
+            continue
+        groups.setdefault((info["H"], info["W"]), []).append((i, data))
+    with torch.cuda.device(torch.device(device)):
+        for members in groups.values():
+            for at in range(0, len(members), PNG_GPU_BATCH):
+                batch = members[at:at + PNG_GPU_BATCH]
+                out, status = ops.png_decode([d for _, d in batch])
+                for k, ((i, _), st) in enumerate(zip(batch, status.cpu().tolist())):
+                    if st:
+                        warnings.warn(f"decode_pngs: {paths[i]!r} is decoded on the host (status {st}: {ops.PNG_STATUS[st]})")
+                        frames[i] = decode_png(paths[i], device)
+                        on_host += 1
+                    else:
+                        frames[i] = out[k].clone() if len(batch) > 1 else out[k]      # a frame does not keep its batch alive
+    return frames, on_host
+
+
 def parse_pairs(text):
     """``"HxW:HxW,HxW:HxW"`` -> a scale-pair table (LR size : HR size per entry), the form of SCALE_PAIRS."""
     pairs = []
@@ -97,6 +150,30 @@ class FrameCache:
         self._cache: "OrderedDict[int, object]" = OrderedDict()
         self._cached_bytes = 0
         self.decodes = 0          # host decodes so far (a cache hit does none)
+        self.gpu_decodes = 0      # images `preload` decoded with ops.png_decode
+
+    def preload(self, indices=None, decoder="gpu"):
+        """Decode the given images (default: all) into the cache, in index order, until the next one would not fit in `cache_bytes`
+        -> how many were loaded.  decoder="gpu": `decode_pngs`' batches (an image it had to hand to the host counts in `decodes`,
+        the others in `gpu_decodes`); "host": `decode_png`, counted in `decodes`.  Images already cached are skipped."""
+        todo, room = [], self.cache_bytes - self._cached_bytes
+        for i in (range(len(self.files)) if indices is None else sorted(set(indices))):
+            if i in self._cache:
+                continue
+            h, w = png_size(self.files[i])
+            if 3 * h * w > room:
+                break
+            room -= 3 * h * w
+            todo.append(i)
+        for at in range(0, len(todo), PNG_GPU_BATCH):
+            part = todo[at:at + PNG_GPU_BATCH]
+            frames, on_host = _decode_pngs([self.files[i] for i in part], self.device, decoder)
+            self.decodes += on_host
+            self.gpu_decodes += len(part) - on_host
+            for i, f in zip(part, frames):
+                self._cache[i] = f
+                self._cached_bytes += f.numel()
+        return len(todo)
 
     def frame(self, img_idx):
         """The decoded image as uint8 [H][W][3] on the GPU, through the LRU cache."""

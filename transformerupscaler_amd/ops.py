@@ -11,6 +11,7 @@ import contextlib
 import ctypes
 import re
 import struct
+import zlib
 
 import numpy as np
 import torch
@@ -1988,6 +1989,180 @@ def jpeg_scan_index(files, index="auto"):
     rounds = torch.zeros((B,), dtype=torch.int32, device=dev)
     _jpeg_decode_index(route, up.data_ptr(), up.data_ptr() + B * _JPEG_DEC_REC.size, scans_bytes, B, H, W, layout, interval, S, segs, status, rounds)
     return segs, status, rounds
+
+
+# ---- PNG decoding of a batch (csrc/png_decode.hip) ----
+_PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+_PNG_CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}             # colour type -> bytes per pixel of the filtered stream at 8 bits a sample
+_PNG_DEC_REC = struct.Struct("<iiii768s")                  # PngImage: stream offset, length, colour type, channels, palette
+PNG_WALKS = ("auto", "token", "wave")
+# status of an image (PiStatus, csrc/png_inflate.h): 0, or the first thing wrong in stream order
+PNG_STATUS = ("ok", "bad block type", "bad stored length", "invalid code", "symbol without a code", "distance before the start",
+              "input exhausted", "output too long", "output too short", "bad filter byte", "Adler-32 mismatch")
+
+
+def png_parse(data):
+    """The chunks of a PNG file, walked on the host: signature, every chunk's CRC-32, IHDR, PLTE, the IDAT payload ranges, IEND ->
+    a dict of H, W, color_type, channels (bytes per pixel of the filtered stream: 1, 3, 1, 2, 4 for colour types 0, 2, 3, 4, 6),
+    palette (colour type 3: the PLTE entries as bytes, zero-filled to 256 entries; otherwise None), idat [(first byte, end)] in
+    order, and stream_bytes = H (1 + channels W).  Ancillary chunks are skipped.  Everything `png_decode` does not decode is a
+    ValueError that names what was found: a bit depth other than 8, Adam7 interlace, an unknown colour type, compression or filter
+    method, a bad CRC, a cut file, no IDAT, IDAT chunks that are not consecutive, a palette image without PLTE, a zlib header that
+    is not deflate with a window of at most 32 KB and no preset dictionary."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise TypeError(f"png_parse: a file is bytes, got {type(data)}")
+    data = bytes(data)
+    if data[:8] != _PNG_SIGNATURE:
+        raise ValueError("png_parse: not a PNG file (no signature)")
+    at, n = 8, len(data)
+    head, palette, idat, ended, closed = None, None, [], False, False
+    while at < n and not ended:
+        if at + 12 > n:
+            raise ValueError(f"png_parse: the file ends inside a chunk header at byte {at}")
+        size, kind = struct.unpack(">I4s", data[at:at + 8])
+        if at + 12 + size > n:
+            raise ValueError(f"png_parse: the file ends inside the {kind!r} chunk at byte {at}")
+        if zlib.crc32(data[at + 4:at + 8 + size]) != struct.unpack(">I", data[at + 8 + size:at + 12 + size])[0]:
+            raise ValueError(f"png_parse: bad CRC in the {kind!r} chunk at byte {at}")
+        payload = data[at + 8:at + 8 + size]
+        if head is None:
+            if kind != b"IHDR" or size != 13:
+                raise ValueError(f"png_parse: the first chunk is {kind!r} of {size} bytes, not IHDR of 13")
+            W, H, depth, ct, comp, filt, lace = struct.unpack(">IIBBBBB", payload)
+            if ct not in _PNG_CHANNELS:
+                raise ValueError(f"png_parse: colour type {ct}")
+            if depth != 8:
+                raise ValueError(f"png_parse: bit depth {depth} is not decoded, only 8")
+            if lace:
+                raise ValueError(f"png_parse: interlace method {lace} (Adam7) is not decoded")
+            if comp or filt:
+                raise ValueError(f"png_parse: compression method {comp}, filter method {filt} (only 0, 0 exist)")
+            if H < 1 or W < 1 or H >= 2 ** 31 or W >= 2 ** 31:
+                raise ValueError(f"png_parse: an image of {H} x {W}")
+            head = (H, W, ct)
+        elif kind == b"IHDR":
+            raise ValueError("png_parse: two IHDR chunks")
+        elif kind == b"PLTE":
+            if palette is not None or idat or size % 3 or not 3 <= size <= 768:
+                raise ValueError(f"png_parse: a PLTE chunk of {size} bytes, a second one, or one after IDAT")
+            palette = payload + bytes(768 - size)
+        elif kind == b"IDAT":
+            if closed:
+                raise ValueError(f"png_parse: IDAT chunks that are not consecutive (byte {at})")
+            idat.append((at + 8, at + 8 + size))
+        elif kind == b"IEND":
+            ended = True
+        elif not kind[0] & 32:
+            raise ValueError(f"png_parse: unknown critical chunk {kind!r}")
+        if idat and kind != b"IDAT":
+            closed = True
+        at += 12 + size
+    if head is None:
+        raise ValueError("png_parse: no IHDR")
+    if not ended:
+        raise ValueError("png_parse: the file ends before IEND")
+    if not idat:
+        raise ValueError("png_parse: no IDAT")
+    H, W, ct = head
+    if ct == 3 and palette is None:
+        raise ValueError("png_parse: colour type 3 without PLTE")
+    first = b""
+    for a, b in idat:                                       # the header's two bytes may lie in two chunks
+        first = (first + data[a:b][:2])[:2]
+    if len(first) < 2:
+        raise ValueError("png_parse: the IDAT chunks hold less than a zlib header")
+    if first[0] & 15 != 8 or first[0] >> 4 > 7 or first[1] & 32 or (first[0] * 256 + first[1]) % 31:
+        raise ValueError(f"png_parse: zlib header {first.hex()} (deflate with a window up to 32 KB and no preset dictionary is decoded)")
+    ch = _PNG_CHANNELS[ct]
+    return {"H": H, "W": W, "color_type": ct, "channels": ch, "palette": palette if ct == 3 else None, "idat": idat,
+            "stream_bytes": H * (1 + ch * W)}
+
+
+# What "auto" resolves to: the walk that is faster at B = 1 (scripts/microbench_png_decode.py; DESIGN 7n)
+PNG_AUTO_WALK = "wave"
+
+
+def _png_decode_upload(files, infos, dev):
+    """The one upload: the image records, then every image's IDAT payloads joined, each at a multiple of 16 -> (tensor, bytes of
+    streams)."""
+    B = len(files)
+    offs, at = [], B * _PNG_DEC_REC.size
+    for s in infos:
+        offs.append(at)
+        at += (sum(b - a for a, b in s["idat"]) + 15) & ~15
+    streams_bytes = at - B * _PNG_DEC_REC.size
+    if streams_bytes > 0x7fff0000:
+        raise ValueError(f"png_decode: {streams_bytes} bytes of streams in one call (below 2^31)")
+    host = bytearray(at)
+    for b, (s, f) in enumerate(zip(infos, files)):
+        stream = b"".join(bytes(f[a:e]) for a, e in s["idat"])
+        host[b * _PNG_DEC_REC.size:(b + 1) * _PNG_DEC_REC.size] = _PNG_DEC_REC.pack(
+            offs[b] - B * _PNG_DEC_REC.size, len(stream), s["color_type"], s["channels"], s["palette"] or bytes(768))
+        host[offs[b]:offs[b] + len(stream)] = stream
+    return torch.frombuffer(host, dtype=torch.uint8).to(dev), streams_bytes
+
+
+def png_decode(files, to_tensor=False, out=None, walk="auto"):
+    """PNG files (8 bits a sample; grey, RGB, palette, grey + alpha, RGBA; no interlace) decoded on the GPU in two launches.  files:
+    bytes, or a sequence of 1..65535 bytes whose images share H and W with H (1 + 4 W) < 2^31 (colour type and palette are each
+    image's own).  Returns (frames, status): frames uint8 [B][H][W][3] RGB, pixel for pixel
+    ``np.asarray(Image.open(io.BytesIO(f)).convert("RGB"))`` (grey: R = G = B; alpha: dropped; palette: looked up, an index past the
+    file's PLTE entries gives (0, 0, 0)); with to_tensor=True fp32 [B][3][H][W], bit-equal to `frames_to_tensor` of the uint8 result
+    and written by the last kernel.  status int32 [B] on the device: 0 for a stream that inflated to exactly stream_bytes with every
+    filter byte in 0..4 and the right Adler-32, otherwise the index into PNG_STATUS of the first thing wrong; the pixels of such an
+    image are unspecified, the other images are unaffected, and nothing is read or written outside the image's own stream,
+    workspace and frame.  out=: the caller's frames tensor.  One upload (the image records, then every image's IDAT payloads joined,
+    each at a multiple of 16 bytes), no read-back, no synchronisation.  walk: "token", one wave decodes one token a round; "wave",
+    lane i decodes the token that would begin i bits on and the true chain is followed across the wave; "auto", PNG_AUTO_WALK.
+    Frames and status are the same bits on every walk.  Everything is validated before any launch; what `png_parse` refuses is
+    refused here."""
+    if walk not in PNG_WALKS:
+        raise ValueError(f"png_decode: walk must be one of {PNG_WALKS}, got {walk!r}")
+    if isinstance(files, (bytes, bytearray, memoryview)):
+        files = [files]
+    try:
+        files = list(files)
+    except TypeError:
+        raise TypeError(f"png_decode: files must be bytes or a sequence of bytes, got {type(files)}") from None
+    B = len(files)
+    if not 1 <= B <= 65535:
+        raise ValueError(f"png_decode: {B} images in one call (1..65535)")
+    if any(not isinstance(f, (bytes, bytearray, memoryview)) for f in files):
+        raise TypeError("png_decode: files must be bytes or a sequence of bytes")
+    infos = [png_parse(f) for f in files]
+    H, W = infos[0]["H"], infos[0]["W"]
+    for b, s in enumerate(infos):
+        if (s["H"], s["W"]) != (H, W):
+            raise ValueError(f"png_decode: the images of a call share H and W; image 0 is {H} x {W}, image {b} is {s['H']} x {s['W']}")
+    if H * (1 + 4 * W) >= 2 ** 31:
+        raise ValueError(f"png_decode: {H} x {W} has a filtered stream of up to {H * (1 + 4 * W)} bytes (below 2^31)")
+    shape, dtype = ((B, 3, H, W), F32) if to_tensor else ((B, H, W, 3), torch.uint8)
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"png_decode: out must be a contiguous {dtype} tensor of shape {shape}, got {getattr(out, 'dtype', type(out))} "
+                             f"{tuple(getattr(out, 'shape', ()))}")
+        _on_current_gpu("png_decode", out, "out")
+    elif not torch.cuda.is_available():
+        raise RuntimeError("png_decode: the HIP path needs a GPU (no CPU fallback)")
+    dev = out.device if out is not None else torch.device("cuda", _cur_dev())
+    channels = max(s["channels"] for s in infos)
+    ws = ((H * (1 + channels * W) + 15) & ~15) + ((8 * W + 15) & ~15)      # the filtered stream, then two rows of packed pixels
+    if ws >= 2 ** 31:
+        raise ValueError(f"png_decode: {H} x {W} needs a workspace of {ws} bytes an image (below 2^31)")
+    if _lib.load().tup_png_decode_workspace(H, W, channels) != ws:
+        raise RuntimeError("png_decode: the library sizes another workspace than the binding")
+    up, streams_bytes = _png_decode_upload(files, infos, dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    work = torch.empty((B, ws), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=dev)
+    records, streams = up.data_ptr(), up.data_ptr() + B * _PNG_DEC_REC.size
+    route = PNG_AUTO_WALK if walk == "auto" else walk
+    _lib.call("tup_png_decode_inflate", records, streams, streams_bytes, B, H, W, channels, int(route == "wave"), work.data_ptr(), ws,
+              status.data_ptr(), _stream())
+    _lib.call("tup_png_decode_finish", records, work.data_ptr(), ws, B, H, W, channels, None if to_tensor else out.data_ptr(),
+              out.data_ptr() if to_tensor else None, status.data_ptr(), _stream())
+    return out, status
 
 
 # ---- WindowTransformer (SURVEY 8(f) rank 2): the patch GEMMs in window layout, without reflect padding ----
