@@ -668,6 +668,21 @@ int tup_patch_pairs(const void* recs, int B, int P, int p, const int* xmin, cons
  * A null pointer, B, H or W <= 0, B > 65535, or out overlapping in (a tile reads its neighbours): hipErrorInvalidValue. */
 int tup_degrade_lr(const float* in, const void* recs, int B, int H, int W, float* out, void* stream);
 
+/* tup_degrade_lr for records of which some carry flags & 4 (ops.DEGRADE_JPEG_420; csrc/degrade420.hip): the JPEG round trip
+ * of such a sample is baseline 4:2:0, what Pillow's save(quality=q, subsampling=2) and open().convert("RGB") return, bit-exact against
+ * tests/_degrade420_ref.py:
+ *   luma as at 4:4:4; Cb and Cr averaged over 2 x 2 pixels, d = (p00 + p01 + p10 + p11 + 1 + (downsampled column & 1)) >> 2, the last
+ *     pixel column replicated up to the 16-pixel MCU width, pixel rows only from H to H + (H & 1), the downsampled plane then
+ *     replicated downwards to a multiple of 8 (libjpeg's asymmetry); DCT, chroma table and inverse DCT per 8 x 8 block of samples;
+ *   the ceil(H/2) x ceil(W/2) real samples upsampled by the decoder's triangle filter: rows 3 : 1 with the nearer row, then columns
+ *     (3 s + before + 8) >> 4 and (3 s + after + 7) >> 4, neighbours clamped to the real samples; W <= 4: each sample replicated 2 x 2.
+ * Blur and noise are unchanged and come first; the noise index stays the absolute pixel index.  All samples go through ONE launch, a
+ * workgroup per 32 x 32 tile and sample: with the flag it works on the 64 x 64 pixels around its tile (the MCUs the filter reaches into),
+ * without it it runs tup_degrade_lr's stages and writes what tup_degrade_lr writes, bit for bit.  The flag with a quality outside
+ * 1..100 is ignored: validate on the host.  Capturable; one writer per output element, no atomics, no workspace.  Refusals as
+ * tup_degrade_lr: a null pointer, B, H or W <= 0, B > 65535, or out overlapping in: hipErrorInvalidValue. */
+int tup_degrade_lr_sub(const float* in, const void* recs, int B, int H, int W, float* out, void* stream);
+
 /* Baseline JPEG (SOF0) of a whole batch on the GPU (ops.jpeg_encode; csrc/jpeg_encode.hip).  The file of image b is byte
  * for byte what Pillow's save(format="JPEG", quality, subsampling, restart_marker_rows=restart_rows) writes: standard Huffman tables,
  * a restart interval of restart_rows MCU rows; tests/_jpeg_ref.py states it in numpy.  subsampling: 0 = 4:4:4, 2 = 4:2:0.  Exactly

@@ -7,6 +7,9 @@ B = 64 LR patches of side 96 (what `ops.patch_pairs` makes at scale 2 from four 
   jpeg      the JPEG round trip alone, quality 75;
   identity  every stage off: the quantisation to bytes and back.
 
+Then one `tup_degrade_lr_sub` launch (csrc/degrade420.hip) on the same batch in the same alternating rounds: "all" and "jpeg" with
+every record flagged 4:2:0 (`ops.DEGRADE_JPEG_420`), and "all" without the flag, which runs the 4:4:4 stages inside that kernel.
+
 Printed: us per launch and GB/s against the bytes a launch must move, B * 24 * p^2 (fp32 in, fp32 out).  Beside them, for scale, the
 `tup_patch_pairs` launch that builds the same batch, and `ops.degrade` itself (the launch plus the record upload) under "all".
 There is no threshold: nothing earlier does this work.  `--B N` / `--p N` change the batch.  Needs a GPU."""
@@ -72,12 +75,16 @@ ptable = torch.frombuffer(bytearray(b"".join(ops._PATCH_REC.pack(f.data_ptr(), H
 lo, n, k, ks = ops._pil_taps_on(torch.device(dev, torch.cuda.current_device()), P, p)
 
 
-def launch(table):
-    return lambda: _lib.call("tup_degrade_lr", lr.data_ptr(), table.data_ptr(), B, p, p, out.data_ptr(), ops._stream())
+def launch(table, entry="tup_degrade_lr"):
+    return lambda: _lib.call(entry, lr.data_ptr(), table.data_ptr(), B, p, p, out.data_ptr(), ops._stream())
 
 
 assert torch.equal(ops.degrade(lr, [ops.DEGRADE_OFF] * B), lr), "the identity table changes patch_pairs' output"
 arms = {name: launch(t) for name, t in tables.items()}
+sub = ops.DEGRADE_JPEG_420
+arms["all420"] = launch(resident([r[:4] + (r[4] | sub,) for r in every]), "tup_degrade_lr_sub")
+arms["jpeg420"] = launch(resident([(ops.DEGRADE_TAPS_OFF, 0, 0, 75, sub)] * B), "tup_degrade_lr_sub")
+arms["all444sub"] = launch(tables["all"], "tup_degrade_lr_sub")
 arms["pairs"] = lambda: _lib.call("tup_patch_pairs", ptable.data_ptr(), B, P, p, lo.data_ptr(), n.data_ptr(), k.data_ptr(), ks,
                                   hr.data_ptr(), lr.data_ptr(), ops._stream())
 arms["op"] = lambda: ops.degrade(lr, every, out=out)
@@ -87,5 +94,7 @@ title = f"B = {B}, p = {p}"
 for name, what in (("all", "blur + noise + JPEG"), ("jpeg", "JPEG alone"), ("identity", "every stage off")):
     med = statistics.median(res[name])
     show(f"{title}, tup_degrade_lr, {what}", res[name], f"  = {moved / (med * 1e-6) / 1e9:.0f} GB/s of {moved / 1e6:.1f} MB")
+for name, what in (("all420", "blur + noise + JPEG 4:2:0"), ("jpeg420", "JPEG 4:2:0 alone"), ("all444sub", "blur + noise + JPEG, no record flagged")):
+    show(f"{title}, tup_degrade_lr_sub, {what}", res[name], f"  = {statistics.median(res[name]) / statistics.median(res['all']):.2f} x tup_degrade_lr's blur + noise + JPEG")
 show(f"{title}, ops.degrade, blur + noise + JPEG, launch + record upload", res["op"])
 show(f"{title}, tup_patch_pairs at x{scale} (builds the batch)", res["pairs"])

@@ -40,8 +40,10 @@ What differs from the reference driver:
   (``transformerupscaler_amd.data.DegradeSpec``, one ``ops.degrade`` launch per distinct scale; HR is untouched): with probability
   0.5 a Gaussian blur of sigma 0.2-1.5 pixels, with 0.5 noise of sigma 1-10 in 8-bit units (grey in 0.4 of those cases), with 0.7
   a 4:4:4 JPEG round trip at quality 30-95.  ``--degrade_blur LO,HI``, ``--degrade_noise LO,HI``, ``--degrade_jpeg LO,HI`` and
-  ``--degrade_prob PB,PN,PJ`` set the ranges and the three probabilities, and each implies ``--degrade``.  The record of sample g
-  is a function of ``(--seed, g)``, from a stream of its own.  The ``--json`` record gains ``degrade`` (the spec).
+  ``--degrade_prob PB,PN,PJ`` set the ranges and the three probabilities, and each implies ``--degrade``.  ``--degrade_jpeg_420 P``
+  (default 0; implies ``--degrade``) makes that share of the JPEG round trips 4:2:0, chroma subsampled as most JPEG files are:
+  chroma averaged over 2 x 2 pixels, quantised in 16 x 16 pixel blocks and smeared back by the decoder's triangle filter.  The record
+  of sample g is a function of ``(--seed, g)``, from a stream of its own.  The ``--json`` record gains ``degrade`` (the spec).
 * ``--ema_decay D`` keeps an exponential moving average of the weights inside the fused optimizer step (``--ema_warmup``: timm's
   warm-up of the decay); a step skipped by ``--skip_nonfinite`` does not move it.  Every checkpoint then also writes
   ``<checkpoint_dir>/ema/model_epoch_<N>.pth`` (the weight file's format: ``ab_test.py --checkpoint_dir_a .../ema`` loads it) and a
@@ -109,6 +111,7 @@ def build_parser():
     p.add_argument("--degrade_noise", type=str, default=None, help="Noise sigma range LO,HI in 8-bit units (default 1,10; implies --degrade)")
     p.add_argument("--degrade_jpeg", type=str, default=None, help="JPEG quality range LO,HI in 1..100 (default 30,95; implies --degrade)")
     p.add_argument("--degrade_prob", type=str, default=None, help="Probabilities PB,PN,PJ of blur, noise, JPEG (default 0.5,0.5,0.7; implies --degrade)")
+    p.add_argument("--degrade_jpeg_420", type=str, default=None, help="Share P of the JPEG round trips that are 4:2:0 instead of 4:4:4 (default 0; implies --degrade)")
     p.add_argument("--ema_decay", type=float, default=None, help="Keep an exponential moving average of the weights with this decay")
     p.add_argument("--ema_warmup", action="store_true", help="Warm the EMA decay up: min(decay, (1 + n) / (10 + n)) (with --ema_decay)")
     p.add_argument("--val_dir", type=str, default=None, help="Directory of held-out images (.png) scored after an epoch")
@@ -157,7 +160,7 @@ def patch_options(args):
         if args.no_augment or args.patches_per_epoch is not None or args.patch_scales != "2,3,4,6":
             sys.exit("train.py: --patch_scales, --no_augment and --patches_per_epoch need --patch_size")
         if degrade_requested(args):
-            sys.exit("train.py: --degrade, --degrade_blur, --degrade_noise, --degrade_jpeg and --degrade_prob need --patch_size")
+            sys.exit("train.py: --degrade, --degrade_blur, --degrade_noise, --degrade_jpeg, --degrade_prob and --degrade_jpeg_420 need --patch_size")
         return None
     degrade_options(args)
     if args.pairs:
@@ -183,7 +186,7 @@ def patch_options(args):
 
 
 def degrade_requested(args):
-    return bool(args.degrade or args.degrade_blur or args.degrade_noise or args.degrade_jpeg or args.degrade_prob)
+    return bool(args.degrade or args.degrade_blur or args.degrade_noise or args.degrade_jpeg or args.degrade_prob or args.degrade_jpeg_420)
 
 
 def degrade_options(args):
@@ -198,6 +201,8 @@ def degrade_options(args):
         except ValueError:
             values = ()
         if len(values) != count:
+            if count == 1:
+                sys.exit(f"train.py: {flag} {text!r}: expected one number")
             sys.exit(f"train.py: {flag} {text!r}: expected {count} {'integers' if kind is int else 'numbers'} separated by commas")
         return values
     kw = {}
@@ -209,11 +214,13 @@ def degrade_options(args):
         kw["jpeg_quality"] = numbers("--degrade_jpeg", args.degrade_jpeg, 2, int)
     if args.degrade_prob:
         kw["blur_prob"], kw["noise_prob"], kw["jpeg_prob"] = numbers("--degrade_prob", args.degrade_prob, 3, float)
+    if args.degrade_jpeg_420:
+        kw["jpeg_420_prob"], = numbers("--degrade_jpeg_420", args.degrade_jpeg_420, 1, float)
     from transformerupscaler_amd.data import DegradeSpec
     try:
         DegradeSpec(**kw)
     except ValueError as e:
-        flag = {"blur_sigma": "--degrade_blur", "noise_sigma": "--degrade_noise", "jpeg_quality": "--degrade_jpeg"}
+        flag = {"blur_sigma": "--degrade_blur", "noise_sigma": "--degrade_noise", "jpeg_quality": "--degrade_jpeg", "jpeg_420_prob": "--degrade_jpeg_420"}
         name = next((f for k, f in flag.items() if k in str(e)), "--degrade_prob")
         sys.exit(f"train.py: {name}: {e}")
     return kw

@@ -1,7 +1,8 @@
 // Training degradations of a whole batch in one launch: blur, noise and a JPEG round trip on bytes, between `tup_patch_pairs` and the
 // model (data.PatchSampler(degrade=...); the reference trains on clean bilinear downscales only, data_handling/data_class.py:24-75).
 // Everything is integer arithmetic on bytes, stated in numpy in tests/_degrade_ref.py and pinned there to Pillow's 4:4:4 JPEG round
-// trip (DESIGN 7j has the definition in full).
+// trip (DESIGN 7j has the definition in full).  The stages are functions of degrade_stages.h, which degrade420.hip (the launch that
+// also knows the 4:2:0 round trip) runs too; the numbers below name them in the order the kernel calls them.
 //
 // Per sample, a 32-byte record {taps[4], noise_amp, noise_seed, quality, flags}; the input is quantised u = clip(floor(v * 255 + .5)):
 //   blur   separable 7 taps {k3 k2 k1 k0 k1 k2 k3} in Pillow's 22-bit fixed point, horizontal then vertical, each pass rounded to a
@@ -24,42 +25,18 @@
 // neighbouring columns of one row.  No intermediate reaches memory; every output has one writer: no atomics, no workspace.
 // Bound: its own instruction stream.  A batch of 64 patches of side 96 is 576 workgroups, 2.25 per CU and all resident at once, and
 // moves 14 MB: 19 us with every stage on, 12 us with every stage off, against 3 us for the bytes alone.
-#include "common.h"
-#include "jpeg_dct.h"      // colour conversion, both DCTs, tables and quantiser: shared with jpeg_encode.hip and jpeg_decode.hip
+#include "degrade_stages.h"      // the stages themselves, shared with degrade420.hip
+#include "jpeg_dct.h"            // colour conversion, both DCTs, tables and quantiser: shared with jpeg_encode.hip and jpeg_decode.hip
 
-struct DegradeRec {
-    int taps[4];
-    int noise_amp;
-    uint32_t noise_seed;
-    int quality, flags;
-};
 static_assert(sizeof(DegradeRec) == 32, "degrade record = 32 bytes (the host packs it as eight 32-bit words)");
 
 namespace {
-constexpr int DG_TILE = 32;                        // tile side: a multiple of the 8 x 8 JPEG block
-constexpr int DG_HALO = 3;                         // blur radius
-constexpr int DG_WIN = DG_TILE + 2 * DG_HALO;      // 38
-constexpr int DG_WS = 40;                          // byte pitch of a window row
-constexpr int DG_PS = DG_TILE + 1;                 // word pitch of an int tile row (see above)
-constexpr int DG_PRECISION_BITS = 32 - 8 - 2;      // Pillow's PRECISION_BITS for 8-bit images
-constexpr int DG_THREADS = 256;
-constexpr int DG_QUADS = DG_TILE / 4;              // 4-byte groups of a tile row
-
-// one output of a blur pass from its seven inputs, rounded to a byte as Pillow's resampler does
-TUP_DEVICE int dg_blur7(const int (&k)[4], int a0, int a1, int a2, int a3, int a4, int a5, int a6)
-{
-    const int s = ((1 << (DG_PRECISION_BITS - 1)) + k[0] * a3 + k[1] * (a2 + a4) + k[2] * (a1 + a5) + k[3] * (a0 + a6)) >> DG_PRECISION_BITS;
-    // The shift and the clip stay two instructions.  Left to itself hipcc (clang 22, ROCm 7.2) joins two neighbouring results into one
-    // v_ashr_pk_u8_i32 and ORs the other two bytes of the dword on top of it as if the instruction had cleared bits 16-31 of its
-    // destination; it leaves them as they were, and the stale bits came out in bytes 2 and 3 of every dword of the horizontal pass.
-    return dg_clip255((int)opaque_copy((uint32_t)s));
-}
-
 __global__ __launch_bounds__(DG_THREADS) void degrade_lr_kernel(const float* __restrict__ in, const DegradeRec* __restrict__ recs,
                                                                int H, int W, float* __restrict__ out)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t win[3 * DG_WIN * DG_WS];      // [ch][38][40]: the window, then the bytes after blur and noise
-    __shared__ __attribute__((aligned(16))) uint8_t hpass[3 * DG_WIN * DG_TILE];  // [ch][38][32]: the horizontal pass
+    using G = DgWindow<DG_TILE>;
+    __shared__ __attribute__((aligned(16))) uint8_t win[G::WIN_BYTES];            // [ch][38][40]: the window, then the bytes after blur and noise
+    __shared__ __attribute__((aligned(16))) uint8_t hpass[G::HPASS_BYTES];        // [ch][38][32]: the horizontal pass
     __shared__ int pl[3 * DG_TILE * DG_PS];                                       // [ch][32][33]: YCbCr - 128, coefficients, and back
     __shared__ int qt[2][64];                                                     // the quantiser tables: luma, chroma
     __shared__ uint32_t qr[2][64];                                                // floor(2^32 / (8 t)) + 1
@@ -70,187 +47,18 @@ __global__ __launch_bounds__(DG_THREADS) void degrade_lr_kernel(const float* __r
     const int tx0 = (blockIdx.x % ntx) * DG_TILE, ty0 = (blockIdx.x / ntx) * DG_TILE;
     const int tw = min(DG_TILE, W - tx0), th = min(DG_TILE, H - ty0);
     const size_t plane = (size_t)H * W;
-    const float* src = in + (size_t)b * 3 * plane;
     const bool jpeg = rec.quality >= 1 && rec.quality <= 100;
+    const DgBox box = {tx0, ty0, 0, th, 0, tw};
 
-    if (jpeg && tid < 128) {
-        const int t = dg_quant_entry(rec.quality, tid >> 6, tid & 63);
-        qt[tid >> 6][tid & 63] = t;
-        qr[tid >> 6][tid & 63] = dg_quant_rcp(t);
-    }
-
-    // ---- 1. fp32 -> bytes, the tile and its halo; a coordinate outside the image reads the nearest pixel inside ----
-    // Every loop below walks the full tile with constant divisors and skips what a partial tile lacks (no integer division by a
-    // run-time size).  Here all of a lane's loads are issued before the first is used: one memory latency per tile, not 17.
-    {
-        const int nr = th + 2 * DG_HALO, nc = tw + 2 * DG_HALO;
-        constexpr int ITERS = (3 * DG_WIN * DG_WIN + DG_THREADS - 1) / DG_THREADS;
-        float v[ITERS];
-#pragma unroll
-        for (int k = 0; k < ITERS; ++k) {
-            const int i = tid + k * DG_THREADS, c = i % DG_WIN, rc = i / DG_WIN, r = rc % DG_WIN, ch = rc / DG_WIN;
-            const int gy = min(max(ty0 - DG_HALO + r, 0), H - 1), gx = min(max(tx0 - DG_HALO + c, 0), W - 1);
-            v[k] = (ch < 3 && r < nr && c < nc) ? src[ch * plane + (size_t)gy * W + gx] : 0.0f;
-        }
-#pragma unroll
-        for (int k = 0; k < ITERS; ++k) {
-            const int i = tid + k * DG_THREADS, c = i % DG_WIN, rc = i / DG_WIN, r = rc % DG_WIN, ch = rc / DG_WIN;
-            if (ch >= 3 || r >= nr || c >= nc) continue;
-            const float q = floorf(__fadd_rn(__fmul_rn(v[k], 255.0f), 0.5f));      // two roundings, as the definition says: no fma
-            win[(ch * DG_WIN + r) * DG_WS + c] = (uint8_t)(int)fminf(fmaxf(q, 0.0f), 255.0f);
-        }
-    }
+    if (jpeg) dg_load_tables(rec.quality, qt, qr, tid);
+    dg_stage<DG_TILE>(in + (size_t)b * 3 * plane, plane, H, W, box, win, tid);
     __syncthreads();
-
-    // ---- 2a. the horizontal pass over every window row: a lane makes 4 neighbouring bytes from the 10 around them (3 dwords) ----
-    {
-        const int nr = th + 2 * DG_HALO;
-        for (int i = tid; i < 3 * DG_WIN * DG_QUADS; i += DG_THREADS) {
-            const int q = i % DG_QUADS, rc = i / DG_QUADS, r = rc % DG_WIN, ch = rc / DG_WIN;
-            if (r >= nr || 4 * q >= tw) continue;
-            // window columns 4 q .. 4 q + 11 (taps reach 4 q + 9); the row's pitch of 40 covers them for every q.  Past the image's
-            // share of a partial tile the bytes are whatever LDS held: they only reach outputs at x >= tw, which nothing reads.
-            const uint32_t* sp = reinterpret_cast<const uint32_t*>(win + (ch * DG_WIN + r) * DG_WS + 4 * q);
-            const uint32_t w[3] = {sp[0], sp[1], sp[2]};
-            int bt[10];
-#pragma unroll
-            for (int j = 0; j < 10; ++j) bt[j] = (int)((w[j >> 2] >> (8 * (j & 3))) & 255u);
-            uint32_t o = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o |= (uint32_t)dg_blur7(rec.taps, bt[e], bt[e + 1], bt[e + 2], bt[e + 3], bt[e + 4], bt[e + 5], bt[e + 6]) << (8 * e);
-            *reinterpret_cast<uint32_t*>(hpass + (ch * DG_WIN + r) * DG_TILE + 4 * q) = o;
-        }
-    }
+    dg_blur_rows<DG_TILE>(rec.taps, box, win, hpass, tid);
     __syncthreads();
-
-    // ---- 2b. the vertical pass, then the noise: bytes [ch][y][x] at the window's pitch; 4 neighbouring columns a lane ----
-    for (int i = tid; i < 3 * DG_TILE * DG_QUADS; i += DG_THREADS) {
-        const int q = i % DG_QUADS, rc = i / DG_QUADS, y = rc % DG_TILE, ch = rc / DG_TILE;
-        if (y >= th || 4 * q >= tw) continue;
-        const uint32_t* sp = reinterpret_cast<const uint32_t*>(hpass + (ch * DG_WIN + y) * DG_TILE + 4 * q);      // rows y .. y + 6
-        uint32_t w[7];
-#pragma unroll
-        for (int j = 0; j < 7; ++j) w[j] = sp[j * (DG_TILE / 4)];
-        uint32_t o = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int sh = 8 * e;
-            int u = dg_blur7(rec.taps, (int)((w[0] >> sh) & 255u), (int)((w[1] >> sh) & 255u), (int)((w[2] >> sh) & 255u), (int)((w[3] >> sh) & 255u),
-                             (int)((w[4] >> sh) & 255u), (int)((w[5] >> sh) & 255u), (int)((w[6] >> sh) & 255u));
-            if (rec.noise_amp != 0) {
-                const uint32_t pix = (uint32_t)(ty0 + y) * (uint32_t)W + (uint32_t)(tx0 + 4 * q + e);
-                const uint32_t h = drop_hash(rec.noise_seed, (rec.flags & 1) ? pix : pix * 3u + (uint32_t)ch);
-                const int n = (int)(h & 255u) + (int)((h >> 8) & 255u) + (int)((h >> 16) & 255u) + (int)(h >> 24) - 510;
-                u = dg_clip255(u + ((n * rec.noise_amp + (1 << 15)) >> 16));
-            }
-            o |= (uint32_t)u << sh;
-        }
-        *reinterpret_cast<uint32_t*>(win + (ch * DG_WIN + y) * DG_WS + 4 * q) = o;
-    }
+    dg_blur_cols_noise<DG_TILE>(rec, W, box, hpass, win, tid);
     __syncthreads();
-
-    if (jpeg) {
-        const int tw8 = (tw + 7) & ~7, th8 = (th + 7) & ~7;
-        // ---- 3. RGB -> YCbCr - 128, the last column / row replicated into the blocks that leave the image ----
-        for (int i = tid; i < DG_TILE * DG_TILE; i += DG_THREADS) {
-            const int x = i % DG_TILE, y = i / DG_TILE;
-            if (y >= th8 || x >= tw8) continue;
-            const uint8_t* sp = win + min(y, th - 1) * DG_WS + min(x, tw - 1);
-            const int R = sp[0], G = sp[DG_WIN * DG_WS], B = sp[2 * DG_WIN * DG_WS];
-            int* d = pl + y * DG_PS + x;
-            int Y, Cb, Cr;
-            dg_rgb_to_ycc(R, G, B, Y, Cb, Cr);
-            d[0] = Y - 128;
-            d[DG_TILE * DG_PS] = Cb - 128;
-            d[2 * DG_TILE * DG_PS] = Cr - 128;
-        }
-        __syncthreads();
-
-        // ---- 4a. forward DCT, rows: a lane per (channel, row, block column) ----
-        for (int i = tid; i < 3 * DG_TILE * 4; i += DG_THREADS) {
-            const int bx = i & 3, r = (i >> 2) & 31, ch = i >> 7;
-            if (r >= th8 || bx * 8 >= tw8) continue;
-            int* p = pl + (ch * DG_TILE + r) * DG_PS + bx * 8;
-            int d[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) d[k] = p[k];
-            dg_fdct8<true>(d);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) p[k] = d[k];
-        }
-        __syncthreads();
-
-        // ---- 4b. forward DCT, columns; quantise, dequantise; inverse DCT, columns: a lane per (channel, block row, column) ----
-        for (int i = tid; i < 3 * 4 * DG_TILE; i += DG_THREADS) {
-            const int x = i & 31, by = (i >> 5) & 3, ch = i >> 7;
-            if (x >= tw8 || by * 8 >= th8) continue;
-            int* p = pl + (ch * DG_TILE + by * 8) * DG_PS + x;
-            const int* t = qt[ch ? 1 : 0] + (x & 7);
-            const uint32_t* rcp = qr[ch ? 1 : 0] + (x & 7);
-            int d[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) d[k] = p[k * DG_PS];
-            dg_fdct8<false>(d);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                // sign(c) ((|c| + 4 t) / (8 t)) t
-                const int tk = t[k * 8];
-                const int q = dg_quant_div(d[k], tk, rcp[k * 8]) * tk;
-                d[k] = d[k] < 0 ? -q : q;
-            }
-            dg_idct8<true>(d);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) p[k * DG_PS] = d[k];
-        }
-        __syncthreads();
-
-        // ---- 4c. inverse DCT, rows; back to 0..255 ----
-        for (int i = tid; i < 3 * DG_TILE * 4; i += DG_THREADS) {
-            const int bx = i & 3, r = (i >> 2) & 31, ch = i >> 7;
-            if (r >= th8 || bx * 8 >= tw8) continue;
-            int* p = pl + (ch * DG_TILE + r) * DG_PS + bx * 8;
-            int d[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) d[k] = p[k];
-            dg_idct8<false>(d);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) p[k] = dg_clip255(d[k] + 128);
-        }
-        __syncthreads();
-
-        // ---- 5a. YCbCr -> RGB, into the byte tile (a pixel has one lane: in place) ----
-        for (int i = tid; i < DG_TILE * DG_TILE; i += DG_THREADS) {
-            const int x = i % DG_TILE, y = i / DG_TILE;
-            if (y >= th || x >= tw) continue;
-            const int* s = pl + y * DG_PS + x;
-            const int Y = s[0], cb = s[DG_TILE * DG_PS] - 128, cr = s[2 * DG_TILE * DG_PS] - 128;
-            uint8_t* d = win + y * DG_WS + x;
-            d[0] = (uint8_t)dg_clip255(Y + ((dg_fix(1.402) * cr + 32768) >> 16));
-            d[DG_WIN * DG_WS] = (uint8_t)dg_clip255(Y + ((-dg_fix(.34414) * cb + 32768 - dg_fix(.71414) * cr) >> 16));
-            d[2 * DG_WIN * DG_WS] = (uint8_t)dg_clip255(Y + ((dg_fix(1.772) * cb + 32768) >> 16));
-        }
-        __syncthreads();
-    }
-
-    // ---- 5b. bytes -> fp32 ----
-    float* dst = out + (size_t)b * 3 * plane;
-    if ((W & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {               // tx0 and tw are multiples of 4 then
-        for (int i = tid; i < 3 * DG_TILE * DG_QUADS; i += DG_THREADS) {
-            const int q = i % DG_QUADS, rc = i / DG_QUADS, y = rc % DG_TILE, ch = rc / DG_TILE;
-            if (y >= th || 4 * q >= tw) continue;
-            const uint32_t w = *reinterpret_cast<const uint32_t*>(win + (ch * DG_WIN + y) * DG_WS + 4 * q);
-            f32x4 o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = (float)((w >> (8 * j)) & 255u) / 255.0f;
-            *reinterpret_cast<f32x4*>(dst + ch * plane + (size_t)(ty0 + y) * W + tx0 + 4 * q) = o;
-        }
-    } else {
-        for (int i = tid; i < 3 * DG_TILE * DG_TILE; i += DG_THREADS) {
-            const int x = i % DG_TILE, rc = i / DG_TILE, y = rc % DG_TILE, ch = rc / DG_TILE;
-            if (y >= th || x >= tw) continue;
-            dst[ch * plane + (size_t)(ty0 + y) * W + tx0 + x] = (float)win[(ch * DG_WIN + y) * DG_WS + x] / 255.0f;
-        }
-    }
+    if (jpeg) dg_jpeg444(win, pl, qt, qr, tw, th, tid);
+    dg_store<DG_TILE>(win, out + (size_t)b * 3 * plane, (W & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0, plane, W, tx0, ty0, tw, th, tid);
 }
 }  // namespace
 

@@ -238,15 +238,18 @@ class DegradeSpec:
     """What `PatchSampler(degrade=...)` does to an LR patch after the clean downscale, BSRGAN / Real-ESRGAN style: with probability
     `blur_prob` a Gaussian blur of sigma uniform in `blur_sigma` (pixels, at most 3.0: the kernel's radius is 3), with `noise_prob`
     noise of standard deviation uniform in `noise_sigma` (8-bit units; with `grey_noise_prob` of those cases one value per pixel
-    instead of one per channel), with `jpeg_prob` a 4:4:4 JPEG round trip at a quality uniform over the integers of `jpeg_quality`.
+    instead of one per channel), with `jpeg_prob` a JPEG round trip at a quality uniform over the integers of `jpeg_quality`: 4:2:0
+    (chroma subsampled, what most JPEG files are) with `jpeg_420_prob` of those cases, else 4:4:4.
     The stages run in that order (``ops.degrade``).  Validated here; the defaults are the ones ``train.py --degrade`` uses."""
 
     FIELDS = ("blur_prob", "blur_sigma", "noise_prob", "noise_sigma", "grey_noise_prob", "jpeg_prob", "jpeg_quality")
+    OPTIONAL = ("jpeg_420_prob",)          # shown by as_dict() and repr only when they are not zero: the default spec reads as it always did
 
     def __init__(self, blur_prob=0.5, blur_sigma=(0.2, 1.5), noise_prob=0.5, noise_sigma=(1.0, 10.0), grey_noise_prob=0.4,
-                 jpeg_prob=0.7, jpeg_quality=(30, 95)):
+                 jpeg_prob=0.7, jpeg_quality=(30, 95), jpeg_420_prob=0.0):
         from . import ops
-        for name, v in (("blur_prob", blur_prob), ("noise_prob", noise_prob), ("grey_noise_prob", grey_noise_prob), ("jpeg_prob", jpeg_prob)):
+        for name, v in (("blur_prob", blur_prob), ("noise_prob", noise_prob), ("grey_noise_prob", grey_noise_prob), ("jpeg_prob", jpeg_prob),
+                        ("jpeg_420_prob", jpeg_420_prob)):
             try:
                 ok = 0.0 <= float(v) <= 1.0
             except (TypeError, ValueError):
@@ -273,23 +276,27 @@ class DegradeSpec:
             raise ValueError(f"DegradeSpec: jpeg_quality = {jpeg_quality!r} must be integers (lo, hi) with 1 <= lo <= hi <= 100")
         self.jpeg_quality = (lo, hi)
 
+    def _shown(self):
+        return self.FIELDS + tuple(k for k in self.OPTIONAL if getattr(self, k) != 0.0)
+
     def as_dict(self):
-        return {k: (list(v) if isinstance(v, tuple) else v) for k, v in ((k, getattr(self, k)) for k in self.FIELDS)}
+        return {k: (list(v) if isinstance(v, tuple) else v) for k, v in ((k, getattr(self, k)) for k in self._shown())}
 
     def __repr__(self):
-        return "DegradeSpec(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.FIELDS) + ")"
+        return "DegradeSpec(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self._shown()) + ")"
 
     def draw(self, rng):
-        """One ``ops.degrade`` record from a numpy Generator.  Eight values are drawn whatever they decide (blur: coin, sigma; noise:
-        coin, sigma, grey coin, seed; JPEG: coin, quality), so one stage's setting never moves another's."""
+        """One ``ops.degrade`` record from a numpy Generator.  Nine values are drawn whatever they decide (blur: coin, sigma; noise:
+        coin, sigma, grey coin, seed; JPEG: coin, quality; last, the 4:2:0 coin), so one stage's setting never moves another's."""
         from . import ops
         blur_on, blur_sigma = rng.random() < self.blur_prob, float(rng.uniform(*self.blur_sigma))
         noise_on, noise_sigma = rng.random() < self.noise_prob, float(rng.uniform(*self.noise_sigma))
         grey, seed = rng.random() < self.grey_noise_prob, int(rng.integers(1 << 32))
         jpeg_on, quality = rng.random() < self.jpeg_prob, int(rng.integers(self.jpeg_quality[0], self.jpeg_quality[1] + 1))
+        sub = rng.random() < self.jpeg_420_prob
         amp = ops.noise_amp(noise_sigma) if noise_on else 0
         return (ops.blur_taps(blur_sigma) if blur_on else ops.DEGRADE_TAPS_OFF, amp, seed if amp else 0,
-                quality if jpeg_on else 0, ops.DEGRADE_GREY_NOISE if amp and grey else 0)
+                quality if jpeg_on else 0, (ops.DEGRADE_GREY_NOISE if amp and grey else 0) | (ops.DEGRADE_JPEG_420 if jpeg_on and sub else 0))
 
 
 class PatchSampler(FrameCache):

@@ -1322,6 +1322,7 @@ _DEGRADE_REC = struct.Struct("<iiiiiIii")       # DegradeRec: taps[4], noise_amp
 DEGRADE_PRECISION_BITS = 32 - 8 - 2             # Pillow's fixed point for 8-bit images
 DEGRADE_TAPS_OFF = (1 << DEGRADE_PRECISION_BITS, 0, 0, 0)
 DEGRADE_GREY_NOISE = 1                          # flags & 1: one noise value per pixel instead of one per channel
+DEGRADE_JPEG_420 = 4                            # flags & 4: this sample's JPEG round trip is 4:2:0 (csrc/degrade420.hip); bit 2 is not used
 DEGRADE_OFF = (DEGRADE_TAPS_OFF, 0, 0, 0, 0)    # the record that changes nothing but the quantisation to bytes
 DEGRADE_MAX_BLUR_SIGMA = 3.0                    # beyond it the radius-3 truncation is a box, not a Gaussian
 DEGRADE_MAX_NOISE_AMP = 1 << 20                 # 510 * amp + 2^15 stays inside 32 bits (sigma up to ~2300)
@@ -1374,8 +1375,10 @@ def _degrade_record(i, rec):
         raise ValueError(f"degrade: sample {i}: noise_seed {seed} is not a 32-bit unsigned value")
     if not 0 <= quality <= 100:
         raise ValueError(f"degrade: sample {i}: quality {quality} is outside [0, 100] (0 switches the JPEG round trip off)")
-    if flags & ~DEGRADE_GREY_NOISE:
+    if flags & ~(DEGRADE_GREY_NOISE | DEGRADE_JPEG_420):
         raise ValueError(f"degrade: sample {i}: unknown flag bits in {flags:#x}")
+    if flags & DEGRADE_JPEG_420 and quality == 0:
+        raise ValueError(f"degrade: sample {i}: flags {flags:#x} name a JPEG sampling (DEGRADE_JPEG_420) but quality 0 switches the round trip off")
     return k0, k1, k2, k3, amp, seed, quality, flags
 
 
@@ -1390,8 +1393,9 @@ def degrade(x, records, out=None):
     integers and bit-exact against tests/_degrade_ref.py: u = clip(floor(v * 255 + .5)); a separable 7-tap blur with `taps` =
     `blur_taps(sigma)`, rounded to bytes after each pass as Pillow's resampler does; noise of `noise_amp(sigma)` from a hash of
     (noise_seed, element), one value per pixel with flags & DEGRADE_GREY_NOISE; what Pillow's ``save(format="JPEG", quality=q,
-    subsampling=0)`` and ``open().convert("RGB")`` give back (quality 0: off); result = u / 255.  `DEGRADE_OFF` switches every stage
-    off.  Returns fp32 [B][3][H][W]; `out` supplies it and must not overlap x.  Everything is validated on the host before anything
+    subsampling=0)`` and ``open().convert("RGB")`` give back (quality 0: off; with flags & DEGRADE_JPEG_420 ``subsampling=2``, Pillow's
+    default, bit-exact against tests/_degrade420_ref.py); result = u / 255.  `DEGRADE_OFF` switches every stage off.  A batch without
+    a 4:2:0 record is one `tup_degrade_lr` call; any other is one `tup_degrade_lr_sub` call for all its samples.  Returns fp32 [B][3][H][W]; `out` supplies it and must not overlap x.  Everything is validated on the host before anything
     is uploaded: a bad record is a ValueError naming its sample."""
     if not isinstance(x, torch.Tensor) or x.dtype != F32:
         raise TypeError(f"degrade: x must be an fp32 tensor, got {getattr(x, 'dtype', type(x))}")
@@ -1426,7 +1430,8 @@ def degrade(x, records, out=None):
     if stager is None:
         stager = _DEGRADE_STAGERS[x.device] = _RecordStager(x.device)
     table = stager.upload(b"".join(_DEGRADE_REC.pack(*w) for w in words))
-    _lib.call("tup_degrade_lr", x.data_ptr(), table.data_ptr(), B, H, W, out.data_ptr(), _stream())
+    entry = "tup_degrade_lr_sub" if any(w[7] & DEGRADE_JPEG_420 for w in words) else "tup_degrade_lr"
+    _lib.call(entry, x.data_ptr(), table.data_ptr(), B, H, W, out.data_ptr(), _stream())
     return out
 
 
